@@ -1,10 +1,15 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json headline metric on the C2 workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
-    --gpus N ...`, or from a bare shell — bench.py then re-executes itself under torch.distributed.run
-    with N ranks on 127.0.0.1; rank 0 prints the one JSON line either way)
+    --gpus N ...`, or from a bare shell — bench.py then runs itself under torch.distributed.run
+    with N ranks on 127.0.0.1, as a child process; rank 0 prints the one JSON line either way)
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and
+prints the result line.  --full adds what the headline does not need, after the timed steps: the
+roofline / per-kernel figures and the box calibration (--no-roofline drops them), the CPU baseline
+(--no-cpu-baseline drops it) and, with several ranks, the all-reduce timing.
 
 One "step" = one Clipped-PPO iteration of the hot path on every rank: 2048 env-steps (64 synthetic
 Atari-like envs x 32 steps, 84x84x4 uint8 stacked observations) through the vectorised
@@ -53,6 +58,30 @@ def one_step(agent):
         agent.act()
         res = agent.train()
     return res
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, agent, results):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy (float32 / float64) — every
+    network's online weights after the step (weights_<network>.npy) and what the step's train() calls returned
+    (`results`: name -> device tensor).  An array that would take the files past 64 MB in all is replaced by a fixed,
+    seeded sample of its elements (sorted indices, RandomState(0))."""
+    arrays = {"weights_%s" % name: net.params.weights for name, net in agent.networks.items()}
+    arrays.update(results)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        if total + a.nbytes > DUMP_LIMIT_BYTES:
+            keep = max(0, (DUMP_LIMIT_BYTES - total) // a.itemsize - 1024)
+            idx = np.sort(np.random.RandomState(0).choice(a.size, min(keep, a.size), replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------ the other BASELINE configs
@@ -324,24 +353,29 @@ def run_off_policy(args, device, dist):
     agent.phase = RunPhase.TRAIN
 
     fused_step = getattr(agent, "step_and_train", None)      # act() + train() as one record + one graph replay
+    last_loss = [None]                                       # the loss train() returned last (--dump-outputs)
 
     def step():
         for _ in range(vsteps):
             if fused_step is not None:
-                fused_step()
+                loss = fused_step()
             else:
                 agent.act()
-                agent.train()
+                loss = agent.train()
+            if loss is not None:
+                last_loss[0] = loss
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
-    sampler = LoadSampler() if dist.rank == 0 and not args.no_roofline else None
+    sampler = LoadSampler() if dist.rank == 0 and args.full and not args.no_roofline else None
     it0, t0 = agent.training_iteration, time.perf_counter()
     for _ in range(args.steps):
         step()
     torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
     elapsed = dist.max_over_ranks(time.perf_counter() - t0)
     agent.check_status()
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, agent, {} if last_loss[0] is None else {"last_loss": last_loss[0]})
     updates = dist.sum_over_ranks(agent.training_iteration - it0)
     env_steps = dist.world_size * n_env * vsteps * args.steps
     out = {"metric": "env-steps/sec (+ grad-updates/sec), %s" % args.workload.upper(),
@@ -352,11 +386,11 @@ def run_off_policy(args, device, dist):
            "config": {"workload": desc, "env_steps_per_step_per_gpu": n_env * vsteps,
                       "parallelism": "dp%d" % dist.world_size, "hip_graphs": bool(agent.use_graphs)},
            "episode_stats": {k: (v if np.isfinite(v) else None) for k, v in agent.episode_statistics().items()}}
-    if dist.rank == 0 and not args.no_roofline and dist.world_size == 1:
+    if dist.rank == 0 and args.full and not args.no_roofline and dist.world_size == 1:
         out["roofline"] = update_roofline(agent, args.workload)
         out["box"] = box_calibration(device)
         out["box"]["under_load"] = sampler.result() if sampler else None
-    if dist.rank == 0 and dist.world_size == 1 and not args.no_cpu_baseline:
+    if dist.rank == 0 and dist.world_size == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_off_policy(args.workload)
         # the reference's own per-step / per-update code, timed in the build container (tools/time_reference_cpu*.py)
         ref_file = {"c1": "r01_cpu_reference_c1_container.json"}.get(
@@ -791,8 +825,13 @@ def main():
                     help="take the collective path (RCCL) even with one rank: its structural cost at world size 1")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed steps, also measure what it does not need: the roofline / "
+                         "per-kernel figures, the box calibration and load sampler, the CPU baseline, the all-reduce timing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline and box figures")
     ap.add_argument("--shapes", action="store_true", help="print the per-GEMM-shape table to stderr")
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c4", "c5"],
                     help="BASELINE.json config (default c2 = the headline metric's configuration)")
@@ -872,9 +911,10 @@ def main():
         with socket.socket() as s_:
             s_.bind(("127.0.0.1", 0))
             port = s_.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                                   "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
 
     from coach_amd.distributed import GradientSync
     if args.dry_run:
@@ -974,7 +1014,7 @@ def main():
     torch.cuda.synchronize()
     dist.barrier()
     torch.cuda.synchronize()
-    sampler = LoadSampler(min(3.0, 0.06 * args.steps)) if dist.rank == 0 and not args.no_roofline else None
+    sampler = LoadSampler(min(3.0, 0.06 * args.steps)) if dist.rank == 0 and args.full and not args.no_roofline else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         res = one_step(agent)
@@ -983,6 +1023,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = dist.max_over_ranks(time.perf_counter() - t0)
     agent.networks["main"].check_status()
+    if args.dump_outputs and dist.rank == 0:
+        # per-epoch means of [surrogate, entropy, kl, policy-head total, value loss, grad norm, ...] of the last step
+        dump_outputs(args.dump_outputs, agent, {"epoch_losses": torch.stack(res)})
 
     n_updates = EPOCHS * (PLAYING_STEPS // BATCH)
     steps_per_iter = N_ENV * agent.steps_per_phase      # = PLAYING_STEPS when the episodes close on the rollout boundary
@@ -1008,7 +1051,7 @@ def main():
                    "hip_graphs": bool(agent.use_graphs)},
         "final_losses": {k: float(v) for k, v in agent.signals.items()},
     }
-    if dist.enabled:
+    if dist.enabled and args.full:
         # what the collective path looked like in this run, so that a SCALE line explains itself: ranks as the
         # process group reports them, whether the all-reduce is a node of the update's graph, one gradient all-reduce
         # of the update's size timed on its own (device time, back to back)
@@ -1023,7 +1066,7 @@ def main():
                        "late_bucket_bytes": 4 * (net.params.grads.numel() - net.late_gradient_offset()),
                        "allreduce_us": None if us is None else round(us, 1),
                        "allreduces_per_step": n_updates * (2 if agent.overlap_allreduce else 1)}
-    if dist.rank == 0 and not args.no_roofline:
+    if dist.rank == 0 and args.full and not args.no_roofline:
         roof, shapes = gemm_roofline(agent)
         out["roofline"] = roof
         out["box"] = box_calibration(device)
@@ -1041,7 +1084,7 @@ def main():
         if args.shapes:
             for s in shapes:
                 print(json.dumps(s), file=sys.stderr)
-    if dist.rank == 0 and dist.world_size == 1 and not args.no_cpu_baseline:
+    if dist.rank == 0 and dist.world_size == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
         # the REFERENCE's own ClippedPPOAgent code path (kind "reference") cannot run here — /root/reference
         # exists only in the build container — so its committed timing rides along with its provenance

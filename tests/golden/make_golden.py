@@ -1776,8 +1776,33 @@ def gen_csv_columns():
     print("wrote csv_columns.json")
 
 
+# ------------------------------------------------------------------------------------ schedules
+SCHEDULE_LINEAR = [(1.0, 0.1, 1000), (0.4, 1.0, 333), (1, 0.01, 10000), (1.0, 0, 1000000)]
+
+
+def gen_schedules():
+    """LinearSchedule / ExponentialSchedule current_value after every step() (schedules.py), bit for bit:
+    linear_<i> for SCHEDULE_LINEAR[i] over 12000 steps, exponential for (1.0, 0.05, 0.995) over 2000 steps."""
+    from rl_coach import schedules as R
+    out = {}
+    for i, args in enumerate(SCHEDULE_LINEAR):
+        s, vals = R.LinearSchedule(*args), []
+        for _ in range(12000):
+            s.step()
+            vals.append(float(s.current_value))
+        out["linear_%d" % i] = np.array(vals, dtype=np.float64)
+        out["linear_%d_args" % i] = np.array(args, dtype=np.float64)
+    s, vals = R.ExponentialSchedule(1.0, 0.05, 0.995), []
+    for _ in range(2000):
+        s.step()
+        vals.append(float(s.current_value))
+    out["exponential"] = np.array(vals, dtype=np.float64)
+    out["exponential_args"] = np.array([1.0, 0.05, 0.995])
+    _save("schedules", **out)
+
+
 GROUPS = {"csv_columns": gen_csv_columns, "per": gen_per, "er": gen_er, "episodic": gen_episodic, "stack": gen_stack, "filters": gen_filters, "gae": gen_gae,
-          "targets": gen_targets, "explore": gen_explore, "updates": gen_updates, "ppo_update": gen_ppo_update, "cadence": gen_cadence, "defaults": gen_defaults, "presets": gen_presets, "loop": gen_loop, "ppo_loop": gen_ppo_loop, "td3_loop": gen_td3_loop, "ddpg_loop": gen_ddpg_loop, "sac_loop": gen_sac_loop, "ppoc_loop": gen_ppoc_loop, "ppo_image_loop": gen_ppo_image_loop, "dqn_image_loop": gen_dqn_image_loop}
+          "targets": gen_targets, "explore": gen_explore, "updates": gen_updates, "ppo_update": gen_ppo_update, "cadence": gen_cadence, "defaults": gen_defaults, "presets": gen_presets, "loop": gen_loop, "ppo_loop": gen_ppo_loop, "td3_loop": gen_td3_loop, "ddpg_loop": gen_ddpg_loop, "sac_loop": gen_sac_loop, "ppoc_loop": gen_ppoc_loop, "ppo_image_loop": gen_ppo_image_loop, "dqn_image_loop": gen_dqn_image_loop, "schedules": gen_schedules}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(GROUPS)

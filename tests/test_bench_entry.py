@@ -30,3 +30,30 @@ def test_bare_shell_two_ranks():
 def test_single_rank_needs_no_launcher():
     out = _run([])
     assert out["n_gpus"] == 1
+
+
+def test_dump_outputs_writes_float_npy_files_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: every network's online weights and the step's results as DIR/<name>.npy in float32 / float64;
+    past the size limit an array becomes a fixed, seeded sample (identical from call to call)."""
+    import types
+
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+
+    w = torch.arange(50000, dtype=torch.float32)
+    agent = types.SimpleNamespace(networks={"main": types.SimpleNamespace(params=types.SimpleNamespace(weights=w))})
+    losses = torch.ones(10, 8, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), agent, {"epoch_losses": losses, "count": torch.tensor([3], dtype=torch.int32)})
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "weights_main.npy"), w.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "epoch_losses.npy"), losses.numpy())
+    assert np.load(tmp_path / "a" / "count.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), agent, {"epoch_losses": losses})
+    total = sum(os.path.getsize(p) - 128 for p in (tmp_path / "b").iterdir())      # less the .npy headers
+    assert total <= 64 << 10
+    b, c = np.load(tmp_path / "b" / "weights_main.npy"), np.load(tmp_path / "c" / "weights_main.npy")
+    assert 0 < b.size < w.numel() and np.array_equal(b, c) and np.all(np.diff(b) > 0)

@@ -1,7 +1,7 @@
 """CartPole-v0 on the device (coach_amd/csrc/cartpole.hip) and the golden-threshold harness.
 
 CPU : the oracle (oracle/cartpole.py) against hand-checked facts of gym 0.12.5's CartPole; the package's CartPole presets
-      against the UNCHANGED reference preset texts executed through the import layer (build container only); the pass rule
+      against what the UNCHANGED reference preset texts set through the import layer (tests/golden/cartpole_presets.json); the pass rule
       of rl_coach/tests/test_golden.py:103-170 on synthetic CSV rows.
 GPU : rlx_libm_sincos against math.sin / math.cos (bit-exact), the device env against the oracle bit for bit over
       thousands of steps with resets, and the reference's own acceptance bar — CartPole_DQN reaches an averaged
@@ -15,8 +15,7 @@ import os
 import numpy as np
 import pytest
 
-REF = "/root/reference/rl_coach/presets"
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="needs /root/reference (build container)")
+GOLDEN_PRESETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cartpole_presets.json")
 
 
 # ------------------------------------------------------------------------------------------- oracle (CPU)
@@ -111,20 +110,19 @@ def _dump(o, depth=0):
     return d
 
 
-@needs_reference
 @pytest.mark.parametrize("name", ["CartPole_DQN", "CartPole_ClippedPPO"])
 def test_package_presets_equal_the_unchanged_reference_preset_texts(name):
-    """/root/reference does not exist on the GPU box, so the golden tests below run coach_amd/presets/<name>.py; here the
-    reference's own preset TEXT is executed through the import layer and every parameter object the engine reads —
-    agent (algorithm, networks, exploration, memory), schedule, validation thresholds — must be equal, field by field."""
-    from coach_amd.compat import resolve_reference_style
-    from test_preset_dropin import _exec_preset, _text
-    ref = _exec_preset(_text(name))["graph_manager"]
-    resolve_reference_style(ref.agent_params, ref.env_params)
+    """The golden tests below run coach_amd/presets/<name>.py; the reference's own preset TEXT, executed through the
+    import layer, produced the parameter objects recorded in tests/golden/cartpole_presets.json
+    (tests/golden/make_preset_dumps.py), and every parameter object the engine reads — agent (algorithm, networks,
+    exploration, memory), schedule, validation thresholds — must equal that record, field by field."""
+    import json
+    with open(GOLDEN_PRESETS) as f:
+        ref = json.load(f)[name]
     mine = importlib.import_module("coach_amd.presets." + name).graph_manager
-    assert ref.env_params.level_name() == "CartPole-v0" and mine.env_params.level == "CartPole-v0"
+    assert ref["level_name"] == "CartPole-v0" and mine.env_params.level == "CartPole-v0"
     for part in ("agent_params", "schedule", "preset_validation_params"):
-        a, b = _dump(getattr(ref, part)), _dump(getattr(mine, part))
+        a, b = ref[part], _dump(getattr(mine, part))
         if part == "agent_params":
             # carriers the reference preset sets and resolve_reference_style folded into flat fields / the device
             # agent does not read (PPO syncs its target at every training phase, clipped_ppo_agent.py:326)

@@ -1,6 +1,6 @@
-"""Schedules: the reference's own unit vectors (rl_coach/tests/test_schedules.py) and, when
-/root/reference is present (build container only), a step-by-step bit-exact comparison against the
-reference classes themselves."""
+"""Schedules: the reference's own unit vectors (rl_coach/tests/test_schedules.py) and a step-by-step
+bit-exact comparison against the values the reference classes themselves produce (tests/golden/schedules.npz,
+recorded by tests/golden/make_golden.py)."""
 import numpy as np
 import pytest
 
@@ -40,19 +40,18 @@ def test_exponential_reference_behaviour():
         ExponentialSchedule(2, 1, 1.1)
 
 
-@pytest.mark.reference
-def test_bit_exact_against_reference_classes():
-    import os, sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import _refstub
-    _refstub.install()
-    from rl_coach import schedules as R
-    for args in [(1.0, 0.1, 1000), (0.4, 1.0, 333), (1, 0.01, 10000), (1.0, 0, 1000000)]:
-        x, y = LinearSchedule(*args), R.LinearSchedule(*args)
-        for i in range(12000):
-            x.step(); y.step()
-            assert float(x.current_value) == float(y.current_value), (args, i)
-    x, y = ExponentialSchedule(1.0, 0.05, 0.995), R.ExponentialSchedule(1.0, 0.05, 0.995)
+def test_bit_exact_against_reference_classes(golden):
+    g = golden("schedules")
+    for i, args in enumerate([(1.0, 0.1, 1000), (0.4, 1.0, 333), (1, 0.01, 10000), (1.0, 0, 1000000)]):
+        assert list(g["linear_%d_args" % i]) == list(args)
+        x, ref = LinearSchedule(*args), g["linear_%d" % i]
+        assert len(ref) == 12000
+        for t in range(12000):
+            x.step()
+            assert float(x.current_value) == float(ref[t]), (args, t)
+    assert list(g["exponential_args"]) == [1.0, 0.05, 0.995]
+    x, ref = ExponentialSchedule(1.0, 0.05, 0.995), g["exponential"]
+    assert len(ref) == 2000
     for i in range(2000):
-        x.step(); y.step()
-        assert float(x.current_value) == float(y.current_value)
+        x.step()
+        assert float(x.current_value) == float(ref[i])

@@ -12,12 +12,12 @@ grep -q "canary 2097152.0" $O/canary.txt || { echo "BAD BOX: torch itself faults
 timeout 1500 python -m pytest tests -m gpu -q --tb=short --durations=8 -p no:cacheprovider 2>&1 | tail -40 > $O/pytest.txt
 tail -6 $O/pytest.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.txt
-timeout 400 python bench.py --shapes > $O/bench_c2.json 2> $O/bench_c2.err
-for w in c1 c3 c4 c5; do timeout 300 python bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; done
-timeout 300 python bench.py --force-dist --no-cpu-baseline --no-roofline > $O/bench_c2_force_dist.json 2> $O/bench_c2_force_dist.err
-timeout 400 python bench.py --episode-length 1024 --steps 4 --warmup 2 --no-cpu-baseline > $O/bench_c2_L1024.json 2> $O/bench_c2_L1024.err
-timeout 300 python bench.py --fuse-conv 0 --no-cpu-baseline > $O/bench_c2_unfused.json 2> $O/bench_c2_unfused.err
-timeout 300 python bench.py --fuse-conv 1 --no-cpu-baseline > $O/bench_c2_pair_only.json 2> $O/bench_c2_pair_only.err
+timeout 400 python bench.py --full --shapes > $O/bench_c2.json 2> $O/bench_c2.err
+for w in c1 c3 c4 c5; do timeout 300 python bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; done
+timeout 300 python bench.py --full --force-dist --no-cpu-baseline --no-roofline > $O/bench_c2_force_dist.json 2> $O/bench_c2_force_dist.err
+timeout 400 python bench.py --full --episode-length 1024 --steps 4 --warmup 2 --no-cpu-baseline > $O/bench_c2_L1024.json 2> $O/bench_c2_L1024.err
+timeout 300 python bench.py --full --fuse-conv 0 --no-cpu-baseline > $O/bench_c2_unfused.json 2> $O/bench_c2_unfused.err
+timeout 300 python bench.py --full --fuse-conv 1 --no-cpu-baseline > $O/bench_c2_pair_only.json 2> $O/bench_c2_pair_only.err
 python tools/conv23_timeline.py 2>&1 | grep -v amdgpu.ids > $O/conv23_timeline.txt
 python tools/conv23_timeline.py --pair 2>&1 | grep -v amdgpu.ids >> $O/conv23_timeline.txt
 for w in c2 c1 c3 c4 c5 c2_force_dist c2_L1024 c2_unfused c2_pair_only; do python - <<PY
@@ -31,7 +31,7 @@ except Exception as e:
     print('$w', 'ERR', e); print(open('$O/bench_$w.err').read()[-600:])
 PY
 done
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python $R/bench.py --steps 3 --warmup 3 --no-cpu-baseline > $R/$O/prof_c2.log 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python $R/bench.py --full --steps 3 --warmup 3 --no-cpu-baseline > $R/$O/prof_c2.log 2>&1)
 f=$(find /tmp/prof_c2 -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $O/c2_kernel_stats.csv
 tail -1 $O/prof_c2.log | cut -c1-400 > $O/prof_c2_bench_line.json
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c3 -- python $R/bench.py --workload c3 --steps 2 --warmup 2 --no-cpu-baseline --no-roofline > $R/$O/prof_c3.log 2>&1)
