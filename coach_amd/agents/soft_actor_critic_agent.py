@@ -84,6 +84,9 @@ class SoftActorCriticAlgorithmParameters(AlgorithmParameters):   # :103-126
         self.use_deterministic_for_evaluation = True
         self.reward_rescale = 5.0                        # Mujoco_SAC preset: RewardRescaleFilter(5)
         self.resample_noise_per_pass = True
+        # "host": the three per-update normal arrays and the acting sample from np.random; "device": from the agent's
+        # counter-based generator on the GPU (rlx_normal_fill); None: VectorOffPolicyAgent.NOISE_SOURCE
+        self.noise_source = None
 
 
 class SoftActorCriticAgentParameters(object):            # :129-141
@@ -105,6 +108,7 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
         "Policy_mu_avg", "Policy_logsig", "Policy_logp_sampled", "Policy_grads_sumabs", "Q1", "TD err1", "Q2",
         "TD err2", "V_tgt_ns", "V_onl_ys", "actions"]
     continuous = True
+    NOISE_STREAMS = (1, 3)           # device noise: streams 1-3, the update's three normal draws
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         super().__init__(agent_parameters, environment, device, dist, use_graphs)
@@ -135,6 +139,8 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
         self.value_targets = torch.zeros(B, dtype=f32, device=dev)
         self.td_targets = torch.zeros(B, dtype=f32, device=dev)
         self.policy_grads_sumabs = torch.zeros(1, dtype=f32, device=dev)
+        if self.noise_source == "device":
+            self.normals = self._update_noise_buffer(1)[0]
         self._finish_init()
 
     # --------------------------------------------------------------------------------- acting
@@ -147,12 +153,18 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
         """choose_action (:296-322): the squashed sample, or the (un-squashed) mean in TEST."""
         alg = self.ap.algorithm
         det = self.phase == RunPhase.TEST and alg.use_deterministic_for_evaluation
+        if self.noise_source == "device":
+            ev = self._stage_act_event()
+            self._run(("pi", det), lambda: self._pi_forward(states, det, ev))
+            return self.actions
         z = np.random.standard_normal((self.n_env, self.A))
         self.act_normals.copy_(self._to_device("act_z", z, torch.float64))
         self._run(("pi", det), lambda: self._pi_forward(states, det))
         return self.actions
 
-    def _pi_forward(self, states, deterministic):
+    def _pi_forward(self, states, deterministic, act_ev=None):
+        if act_ev is not None:                       # device noise: the acting sample's normals, in the captured body
+            self._fill_act_noise(self.act_normals, act_ev)
         o, _ = self.networks["policy"].forward(states, self.n_env, self.act_normals, tag="act")
         self.actions.copy_(o["mean"] if deterministic else o["actions"])
 
@@ -283,19 +295,30 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
             br.join()
 
     def _update_record_fields(self):
+        if self.noise_source == "device":
+            return [("ev", (1,), torch.int64)]
         return [("z", (3, self.batch_size, self.A), torch.float64)]
 
     def _draw_update_host(self):
+        if self.noise_source == "device":
+            return self._device_noise_event()
         return {"z": np.random.standard_normal((3, self.batch_size, self.A))}
 
     def learn_from_batch(self, batch):
         B = self.batch_size
-        if self._staged is not None:
+        fill_ev = None
+        if self.noise_source == "device":
+            self.normals, fill_ev = self._device_update_noise()
+        elif self._staged is not None:
             self.normals = self._staged["z"]             # shipped with the sampled rows (one record per update)
         else:
             self.normals = self._to_device("sac_z", self._draw_update_host()["z"], torch.float64)     # the staging buffer is the operand
         mix = self._mix_rate
-        self._run(("learn", mix, self._staged is not None), lambda: self._learn_device(batch, mix))
+        if fill_ev is not None:                      # device noise of this update: generated inside the captured body
+            self._run(("learn", mix, self._staged is not None),
+                      lambda: (self._fill_update_noise(1, fill_ev), self._learn_device(batch, mix)))
+        else:
+            self._run(("learn", mix, self._staged is not None), lambda: self._learn_device(batch, mix))
         if mix is not None and self._v_mixes_in_update(batch):     # (decided here, not in the captured body: replays skip that)
             self._mixed = self._mixed | {"v"}
         qn = self.networks["q"]

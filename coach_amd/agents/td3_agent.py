@@ -59,6 +59,9 @@ class TD3AlgorithmParameters(AlgorithmParameters):               # td3_agent.py:
         self.num_q_networks = 2
         self.num_consecutive_playing_steps = EnvironmentSteps(1)
         self.clear_game_over_on_time_limit = True
+        # "host": the smoothing and acting noise from np.random (the reference's stream); "device": from the agent's
+        # counter-based generator on the GPU (rlx_normal_fill); None: VectorOffPolicyAgent.NOISE_SOURCE
+        self.noise_source = None
 
 
 class TD3AgentExplorationParameters(AdditiveNoiseParameters):    # td3_agent.py:114-117
@@ -83,6 +86,7 @@ class TD3AgentParameters(object):                                # td3_agent.py:
 
 
 class TD3Agent(DDPGAgent):
+    NOISE_STREAMS = (0, 1)           # device noise: stream 0, the target-policy smoothing noise
     # The update as five launches (csrc/ac_fused.hip: row-local chains + one weight-gradient / Adam launch per network)
     # instead of ~36 layer-by-layer ones, wherever the networks have the Mujoco_TD3 topology (nn/fused_updates.py
     # FusedTD3.layers); the tests flip it to compare the two paths.
@@ -104,6 +108,15 @@ class TD3Agent(DDPGAgent):
         self.q_min = torch.zeros(B, dtype=torch.float32, device=dev)
         self.zero_go = torch.zeros(self.n_env, dtype=torch.uint8, device=dev)
         self.act2 = torch.zeros(2, B, self.A, dtype=torch.float32, device=dev)   # (batch actions, smoothed a')
+        if self.noise_source == "device":
+            self.noise = self._update_noise_buffer(1)[0][0]
+            self.exploration_policy.noise_fill = self._act_noise_fill
+
+    def _act_noise_fill(self, out):
+        self._fill_act_noise(out, self._stage_act_event())
+
+    def _update_noise_scale(self):
+        return self.ap.algorithm.policy_noise           # np.random.normal(0, sigma) is sigma * z (:162)
 
     def _stored_game_over(self, game_over):
         # the synthetic episodes end on their time limit -> game_over False (:215-227)
@@ -208,15 +221,23 @@ class TD3Agent(DDPGAgent):
         actor.apply_gradients(self._scale("actor"), mix_rate=mix)
 
     def _update_record_fields(self):
+        if self.noise_source == "device":
+            return [("ev", (1,), torch.int64)]
         return [("z", (self.batch_size, self.A), torch.float64)]
 
     def _draw_update_host(self):
+        if self.noise_source == "device":
+            return self._device_noise_event()
         alg = self.ap.algorithm
         return {"z": np.random.normal(0, alg.policy_noise, (self.batch_size, self.A))}    # :162 (host stream)
 
     def learn_from_batch(self, batch):
         alg, B = self.ap.algorithm, self.batch_size
-        if self._staged is not None:
+        fill_ev = None
+        if self.noise_source == "device":
+            noise, fill_ev = self._device_update_noise()
+            self.noise = noise[0]
+        elif self._staged is not None:
             self.noise = self._staged["z"]               # shipped with the sampled rows (one record per update)
         else:
             # the staging buffer IS the noise operand (a static device tensor): no device-to-device copy behind the upload
@@ -224,7 +245,10 @@ class TD3Agent(DDPGAgent):
         run = self._run
         mix = self._mix_rate
         staged = self._staged is not None          # (the captured graphs read the noise at ITS address)
-        run(("critic", mix, staged), lambda: self._critic_device(batch, mix))
+        if fill_ev is not None:                    # device noise of this update: generated inside the captured body
+            run(("critic", mix, staged), lambda: (self._fill_update_noise(1, fill_ev), self._critic_device(batch, mix)))
+        else:
+            run(("critic", mix, staged), lambda: self._critic_device(batch, mix))
         if self.training_iteration % alg.update_policy_every_x_episode_steps == 0:   # :186
             run(("actor", mix, staged), lambda: self._actor_device(batch, mix))
             if mix is not None:

@@ -253,6 +253,7 @@ class VectorOffPolicyAgent(GraphRunner):
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         self.ap = agent_parameters
+        self.noise_source = self._resolve_noise_source()          # (checked before anything touches the device)
         self.env = environment
         self.device = device or environment.device
         self.dist = dist if (dist is not None and dist.enabled) else None
@@ -288,6 +289,12 @@ class VectorOffPolicyAgent(GraphRunner):
         self._stagers = StagerCache(self.device)
         self.debug_draws = None          # tests set these to lists to record every replay draw /
         self.debug_losses = None         # every update's loss (forces a sync per update)
+        if self.noise_source == "device":
+            # key of the agent's noise generator: (noise seed, rank); the acting draws count their own events
+            self._noise_seed = int(self.ap.seed) & 0xFFFFFFFF if self.ap.seed is not None else \
+                int.from_bytes(os.urandom(4), "little")
+            self._noise_rank = int(self.dist.rank) if self.dist is not None else 0
+            self._act_event = 0
 
     # ------------------------------------------------------------------ helpers for subclasses
     def _finish_init(self):
@@ -321,6 +328,71 @@ class VectorOffPolicyAgent(GraphRunner):
     def _to_device(self, key, array, dtype):
         """host draws -> a static device buffer through a ring of pinned staging slots."""
         return self._stagers.push(key, array, dtype)
+
+    # ------------------------------------------------------------------ device noise (noise_source = "device")
+    # Where the Gaussian draws of TD3 / SAC come from: "host" — numpy's legacy stream in the reference's order (the
+    # default: every reference-pinned loop keeps its meaning); "device" — rlx_normal_fill (csrc/noise.hip), a
+    # counter-based generator keyed by (noise seed, rank) and counted by (stream, event): an update's draws are a
+    # function of its training_iteration, the acting draws of the acting counter.  np.random / random then serve only
+    # the replay index draws and the heat-up actions.  Used when algorithm.noise_source is None.
+    NOISE_SOURCE = "host"
+    NOISE_STREAMS = None             # (first stream, number of streams) of an update's draws (subclasses)
+
+    def _resolve_noise_source(self):
+        if not hasattr(self.ap.algorithm, "noise_source"):
+            return "host"                                    # an agent without Gaussian draws of its own
+        v = self.ap.algorithm.noise_source
+        if v is None:
+            v = self.NOISE_SOURCE
+        if v not in ("host", "device"):
+            raise ValueError("algorithm.noise_source must be 'host' or 'device', got %r" % (v,))
+        return v
+
+    def _normal_fill(self, out, events, n_events, stream0, n_streams, n, scale=1.0):
+        self.lib.normal_fill(out, events, n_events, stream0, n_streams, n, self._noise_seed, self._noise_rank,
+                             float(scale), _rlx.current_stream())
+
+    def _stage_act_event(self):
+        """the acting counter of this acting step, staged to a static device word (acting may be a graph replay)"""
+        ev = self._to_device("noise_act_ev", np.array([self._act_event], dtype=np.int64), torch.int64)
+        self._act_event += 1
+        return ev
+
+    def _fill_act_noise(self, out, ev):
+        """standard normals of one acting step (stream 4) into out (fp64, n_env x A)"""
+        self._normal_fill(out, ev, 1, 4, 1, out.numel())
+
+    def _update_noise_scale(self):
+        return 1.0
+
+    def _update_noise_buffer(self, K):
+        """the agent-owned [K][streams][B x A] fp64 buffer of K updates' draws (stable address: the fused descriptors
+        and the captured graphs read it where it is)"""
+        bufs = self.__dict__.setdefault("_noise_bufs", {})
+        b = bufs.get(K)
+        if b is None:
+            s0, ns = self.NOISE_STREAMS
+            b = bufs[K] = torch.zeros(K, ns, self.batch_size, self.A, dtype=torch.float64, device=self.device)
+        return b
+
+    def _fill_update_noise(self, K, events):
+        s0, ns = self.NOISE_STREAMS
+        buf = self._update_noise_buffer(K)
+        self._normal_fill(buf, events, K, s0, ns, self.batch_size * self.A, self._update_noise_scale())
+        return buf
+
+    _chunk_slot = None        # k while the k-th update of a chunk runs (its draws were filled for the whole chunk)
+
+    def _device_update_noise(self):
+        """device mode: this update's draws [streams][B][A] and whether learn_from_batch must fill them inside its
+        captured body (per-update path: the event is the staged record's, or training_iteration staged on its own)"""
+        if self._chunk_slot is not None:
+            return self._update_noise_buffer(self.__dict__["_chunk_K"])[self._chunk_slot], None
+        if self._staged is not None:
+            ev = self._staged["ev"]
+        else:
+            ev = self._to_device("noise_update_ev", np.array([self.training_iteration], dtype=np.int64), torch.int64)
+        return self._update_noise_buffer(1)[0], ev
 
     # --------------------------------------------------------------------------------- acting
     def random_actions(self):
@@ -498,6 +570,11 @@ class VectorOffPolicyAgent(GraphRunner):
         """{name: array} — the host draws of ONE update, made exactly as learn_from_batch makes them."""
         return {}
 
+    def _device_noise_event(self):
+        """device mode: the record of one update is its event counter instead of its normals — the update's
+        training_iteration (the loops draw before they advance the counter) — and no host RNG call"""
+        return {"ev": np.array([self.training_iteration + 1], dtype=np.int64)}
+
     def _update_record(self):
         """A RecordStager [rows | the update's host draws] when the agent has per-update draws and the memory takes
         device rows (uniform / episodic replay; prioritized replay samples on the device), else None."""
@@ -549,7 +626,8 @@ class VectorOffPolicyAgent(GraphRunner):
         # prioritized one launches its descent: excluded), no store happens
         # inside train(), and nothing else touches the host streams until the last update has its draws
         ahead = _HostDrawsAhead(host_items(), total) \
-            if rec is not None and self.HOST_DRAWS_AHEAD and total >= 8 and type(self.memory).draw is ExperienceReplay.draw else None
+            if rec is not None and self.HOST_DRAWS_AHEAD and self.noise_source == "host" and total >= 8 and \
+            type(self.memory).draw is ExperienceReplay.draw else None
         source = ahead if ahead is not None else host_items()
         K = int(self.UPDATE_CHUNK or 0)
         chunked = 0
@@ -631,6 +709,9 @@ class VectorOffPolicyAgent(GraphRunner):
             mixes.append(bool(has_target and self._should_update_online_weights_to_target()))
         crec.stager.push(crec.host)
         views = crec.views
+        device_noise = self.noise_source == "device"
+        if device_noise:
+            self._update_noise_buffer(K)          # (allocated before the capture)
         rate = alg.rate_for_copying_weights_to_target
         key = ("chunk", K, tuple(mixes), self._schedule_phase(it0))
         cache = self.__dict__.setdefault("_chunk_loss", {})
@@ -638,8 +719,12 @@ class VectorOffPolicyAgent(GraphRunner):
         def body():
             self._inline_run = True
             try:
+                if device_noise:                  # the draws of all K updates: one launch on the record's K events
+                    self._fill_update_noise(K, views["ev"])
+                    self._chunk_K = K
                 for k in range(K):
                     self.training_iteration = it0 + k + 1
+                    self._chunk_slot = k if device_noise else None
                     self._staged = {n: v[k] for n, v in views.items()}
                     batch = self.memory.collate(ds[k], B, rows_dev=self._staged["rows"])
                     self._mix_rate = rate if mixes[k] else None
@@ -652,6 +737,7 @@ class VectorOffPolicyAgent(GraphRunner):
                     self._mix_rate = None
             finally:
                 self._inline_run = False
+                self._chunk_slot = None
         self._run(key, body)
         self.training_iteration = it0 + K
         self._staged = None

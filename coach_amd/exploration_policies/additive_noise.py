@@ -42,6 +42,8 @@ class AdditiveNoise(object):
         from ..staging import Stager
         self._z = Stager((n_env, self.A), torch.float64, device)
         self.d_z = self._z.dst
+        # noise_source = "device": the agent's generator fills d_z (n_env x A standard normals) at its acting counter
+        self.noise_fill = None
 
     def current_std(self):
         noise = self.evaluation_noise if self.phase == RunPhase.TEST else self.noise_schedule.current_value
@@ -55,10 +57,12 @@ class AdditiveNoise(object):
         if self.phase != RunPhase.TEST:
             for _ in range(self.n_env):
                 self.noise_schedule.step()                                    # :99-100
-            z = np.random.standard_normal((self.n_env, self.A))              # np.random.normal (:106)
+            if self.noise_fill is not None:
+                self.noise_fill(self.d_z)
+            else:
+                self._z.push(np.random.standard_normal((self.n_env, self.A)))    # np.random.normal (:106)
         else:
-            z = np.zeros((self.n_env, self.A))
-        self._z.push(z)
+            self._z.push(np.zeros((self.n_env, self.A)))
         self.d_std.copy_(torch.from_numpy(std), non_blocking=True)
         self.lib.gaussian_action(action_means, self.d_std, None, self.d_z, None, None,
                                  self.n_env, self.A, out_actions, _rlx.current_stream())

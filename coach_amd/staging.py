@@ -109,4 +109,5 @@ class StagerCache(object):
         return st.push(a.astype(_NP[dtype], copy=False))
 
 
-_NP = {torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
+_NP = {torch.float64: np.float64, torch.float32: np.float32, torch.int64: np.int64, torch.int32: np.int32,
+       torch.uint8: np.uint8}

@@ -861,6 +861,18 @@ int rlx_synth_env_step_lengths(int kind, void *next_obs, void *reset_obs, float 
                                const int *episode_len_per_env, unsigned int seed, unsigned int env_id0,
                                void *stream);
 
+/* Standard normals from a counter-based generator, for the agents' noise_source = "device" mode (no reference
+ * counterpart: the reference draws this noise with np.random.normal, td3_agent.py:162, additive_noise.py:106, and in
+ * SAC's TF sampling op).  out[e][s][i] (n_events x n_streams x n doubles) = scale * z, z the i-th value of stream
+ * stream0 + s at event events[e]: Philox4x32-10 with key (seed, rank) and counter (i / 2, stream, event low word,
+ * event high word ^ a fixed tag that keeps it apart from the synthetic environment's streams), one Box-Muller pair
+ * per call computed with correctly rounded IEEE operations only (csrc/noise.hip; bit-exact numpy twin:
+ * tests/noise_ref.py).  Streams 0..4: 0 TD3 smoothing noise, 1-3 SAC's three per-update draws, 4 acting.  The event
+ * indices are READ FROM DEVICE MEMORY (events: n_events int64), so a captured graph replayed after they were
+ * rewritten draws new values. */
+int rlx_normal_fill(double *out, const long long *events, int n_events, int stream0, int n_streams, int n,
+                    unsigned int seed, unsigned int rank, double scale, void *stream);
+
 /* ------------------------------------------------------------ CartPole-v0 / -v1 -- */
 /* N CartPole environments per GPU: gym 0.12.5's physics (gym/envs/classic_control/cartpole.py `step`, fp64, Euler)
  * behind gym's TimeLimit (max_episode_steps), i.e. what `GymVectorEnvironment(level='CartPole-v0')` steps through
