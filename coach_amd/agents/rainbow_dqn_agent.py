@@ -1,0 +1,11 @@
+"""Rainbow DQN (rl_coach/agents/rainbow_dqn_agent.py) is not implemented by this engine.
+
+The module exists so that preset texts which import the name without using it — the reference's
+presets/CartPole_QR_DQN.py does (line 2) — run unchanged through coach_amd.compat.install().
+"""
+
+
+class RainbowDQNAgentParameters(object):
+    def __init__(self):
+        raise NotImplementedError("Rainbow DQN is not implemented by this engine (categorical heads, noisy nets and "
+                                  "n-step prioritized replay are out of its scope)")

@@ -31,3 +31,13 @@ class DuelingQHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='dueling_q_head_params',
                  rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class QuantileRegressionQHeadParameters(HeadParameters):
+    """QuantileRegressionQHeadParameters (head_parameters.py:204-212): one Dense layer of A * atoms outputs, read as
+    [batch, A, atoms] (heads/quantile_regression_q_head.py:40-81); the atom count is the algorithm's `atoms`."""
+    head_type = "QuantileRegressionQHead"
+
+    def __init__(self, activation_function='relu', name='quantile_regression_q_head_params',
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

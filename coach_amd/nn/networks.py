@@ -620,3 +620,57 @@ class DQNNet(_NetBase):
             sync.all_reduce_sum(self.params.grads)
         self.apply_gradients(grad_scale, with_norm=not clipped)
         return self.loss
+
+
+class QRDQNNet(DQNNet):
+    """QuantileRegressionDQNNetworkParameters (agents/qr_dqn_agent.py:28-33): the DQN torso (vector or image) under a
+    QuantileRegressionQHead — ONE Dense(feat, A * atoms) whose output column a * atoms + j is atom j of action a
+    (heads/quantile_regression_q_head.py:45-50).  Forward and backward go through the torso's and the Dense layer's
+    generic launches; the quantile Huber loss and its gradient come from rlx_qr_dqn_head_loss (csrc/qr_dqn.hip).
+    The fused small-MLP update / acting kernels are DQN's alone: _fused and _act stay None."""
+    FUSED_MLP = False
+    FUSED_ACT = False
+    HEAD_LOSS_BACKWARD_ONE_LAUNCH = False
+
+    def __init__(self, device, obs_shape, n_actions, atoms, huber_loss_interval=1.0, **kw):
+        kw.pop("replace_mse_with_huber_loss", None)
+        kw.pop("dueling", None)
+        super().__init__(device, obs_shape, n_actions * atoms, dueling=False, **kw)
+        self.A, self.N, self.AN = n_actions, int(atoms), n_actions * int(atoms)
+        self.kappa = float(huber_loss_interval)
+        self._fused, self._act = None, None
+        self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)      # per-row loss partials
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def quantiles(self, obs, B, use_target=False, tag="q"):
+        """the head output [B, A * atoms] (a Tensor; .data is the buffer)."""
+        return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag)
+
+    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount, grad_scale=1.0,
+                         sync=None, states_pair=None, targets_out=None, tau_out=None, target_actions_out=None):
+        """QuantileRegressionDQNAgent.learn_from_batch (agents/qr_dqn_agent.py:99-137), all on device: target(s') and
+        online(s) quantiles, rlx_qr_dqn_head_loss (target action, TD targets, midpoints, loss, dtheta), backward, Adam."""
+        ctx, AN = self.ctx, self.AN
+        if states_pair is not None:
+            # parallel_prediction (qr_dqn_agent.py:103-106): online(s) and target(s') as two towers of the same launches
+            cols = int(np.prod(self.obs_shape))
+            x = G.Tensor(states_pair.view(2, B, cols), B, cols, 2, u8=self.image, div=255.0 if self.image else 1.0)
+            acts2 = self.torso.forward(ctx, x, tag="pair", pair=True)
+            q2 = self.q_head.forward(ctx, acts2[-1], tag="pair", pair=True)
+            q_next = q2.data[1].view(B, AN)
+            acts = [x.tower_view(0)] + [a.tower(0) for a in acts2[1:]]
+            q = q2.tower(0)
+        else:
+            q_next = self.quantiles(next_obs, B, use_target=True, tag="next_t").data.view(B, AN)
+            acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+            q = self.q_head.forward(ctx, acts[-1], tag="train")
+        dq = q.ensure_grad()
+        self.lib.qr_dqn_head_loss(q.data, AN, q_next, AN, actions, rewards, game_overs, float(discount), self.kappa,
+                                  self.N, self.A, B, 1.0, dq, AN, self.loss_ws, self.ticket, self.loss, self.status,
+                                  targets_out, tau_out, target_actions_out, ctx.stream)
+        self._backward_from_q(acts, q, None, B)
+        clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
+        if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
+            sync.all_reduce_sum(self.params.grads)
+        self.apply_gradients(grad_scale, with_norm=not clipped)
+        return self.loss

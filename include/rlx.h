@@ -843,6 +843,29 @@ int rlx_gaussian_action(const float *mean, const float *std_per_dim, const float
                         const float *action_high, int n_env, int action_dim, float *actions,
                         void *stream);                              /* exploration_policies/additive_noise.py:75-111 */
 
+/* ------------------------------------------------------------- Quantile-Regression DQN -- */
+/* QuantileRegressionDQNAgent.learn_from_batch + the QuantileRegressionQHead loss (agents/qr_dqn_agent.py:99-137,
+ * heads/quantile_regression_q_head.py:55-74) in ONE launch, one workgroup per batch row.  theta / theta_next_target:
+ * the online / target head outputs [batch][A*N] (column a*N + j = atom j of action a).  Per row: a* = argmax of the
+ * target's fp64 atom means (first maximum), T_j = fp32(r + (1 - done) * discount * theta'[a*, j]) in fp64, the
+ * midpoints tau[i] = fp32(tau_hat[argsort(theta[a_b])[i]]) (the reference's indexing, stable ties), then
+ * loss = sum_b sum_i sum_j |tau_i - 1{e_ij < 0}| * huber_kappa(e_ij) / N with e_ij = T_j - theta_i (a SUM over the batch),
+ * dtheta[b][a_b*N + i] = -grad_scale / N * sum_j |tau_i - 1{e_ij < 0}| * sign(e_ij) * min(|e_ij|, kappa), zero elsewhere.
+ * row_partials: [batch] floats of workspace; ticket: one zero-initialised word (left at zero); the loss is summed in a
+ * fixed order (bit-identical run to run).  status |= 1 for an action outside [0, A).  targets_out / tau_out [batch][N]
+ * and target_actions_out [batch] are optional (null).  N <= 256, A <= 18, batch <= 256. */
+int rlx_qr_dqn_head_loss(const float *theta, long long ld_theta, const float *theta_next_target, long long ld_next,
+                         const int *actions, const float *rewards, const unsigned char *game_overs, double discount,
+                         float kappa, int n_atoms, int n_actions, int batch, float grad_scale, float *dtheta,
+                         long long ld_dtheta, float *row_partials, unsigned int *ticket, float *loss_scalar,
+                         int *status, float *targets_out, float *tau_out, int *target_actions_out, void *stream);
+/* get_q_values (qr_dqn_agent.py:75-76: fp64 means of the atoms, summed in atom order) + rlx_egreedy's choice on them
+ * with the isclose tie test in fp64 (e_greedy.py:84-101).  quantiles: [n_env][ld], ld >= A*N; the draws as rlx_egreedy
+ * takes them; q_out [n_env][A] fp64 is optional (null). */
+int rlx_quantile_egreedy(const float *quantiles, long long ld, int n_atoms, const double *explore_uniforms,
+                         const int *random_actions, const double *tie_break_uniforms, double epsilon, int n_env,
+                         int n_actions, double *q_out, int *actions, void *stream);
+
 /* ------------------------------------------------ synthetic vector environment -- */
 /* Device-resident stand-in for Environment.step (environments/environment.py:276-327) on the
  * BASELINE workloads: fixed-length episodes, Philox4x32-10 observations/rewards keyed by
