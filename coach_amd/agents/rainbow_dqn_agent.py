@@ -7,5 +7,6 @@ presets/CartPole_QR_DQN.py does (line 2) — run unchanged through coach_amd.com
 
 class RainbowDQNAgentParameters(object):
     def __init__(self):
-        raise NotImplementedError("Rainbow DQN is not implemented by this engine (categorical heads, noisy nets and "
-                                  "n-step prioritized replay are out of its scope)")
+        raise NotImplementedError("Rainbow DQN is not implemented by this engine (noisy nets and the n-step "
+                                  "prioritized replay of its categorical head are out of its scope; the categorical "
+                                  "head itself is coach_amd.agents.categorical_dqn_agent)")

@@ -41,3 +41,14 @@ class QuantileRegressionQHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='quantile_regression_q_head_params',
                  rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class CategoricalQHeadParameters(HeadParameters):
+    """CategoricalQHeadParameters (head_parameters.py:76-85): one Dense layer of A * atoms logits, read as
+    [batch, A, atoms] with a softmax over the atoms (heads/categorical_q_head.py:42-58); the support is the algorithm's
+    np.linspace(v_min, v_max, atoms)."""
+    head_type = "CategoricalQHead"
+
+    def __init__(self, activation_function='relu', name='categorical_q_head_params',
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

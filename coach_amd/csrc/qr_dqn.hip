@@ -12,6 +12,7 @@
 //   q = sum_{j = 0 .. N-1, in this order} (double)theta[a*N + j] * (1.0 / N)
 // (numpy's BLAS dot may associate differently: the means agree to a few ulp, the decisions on them exactly unless two
 // actions are within that distance).  Compiled with -ffp-contract=off so the fp64 arithmetic rounds like numpy.
+#include "egreedy_choice.hpp"
 #include "rlx_common.hpp"
 
 namespace {
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(kQrThreads) qr_dqn_head_loss_kernel(const QrAr
 }
 
 // One wave per env: lanes a < A form the fp64 means (order above), lane 0 makes the epsilon-greedy choice on them
-// with numpy's isclose in fp64: |q - max| <= 1e-8 + 1e-5 * |max| (e_greedy.py:93-94).
+// (egreedy_choice.hpp: numpy's isclose in fp64, e_greedy.py:93-94).
 __global__ void __launch_bounds__(64) quantile_egreedy_kernel(const float *__restrict__ quant, long long ld, int n_atoms,
                                                               const double *__restrict__ explore_u,
                                                               const int *__restrict__ random_act,
@@ -169,20 +170,8 @@ __global__ void __launch_bounds__(64) quantile_egreedy_kernel(const float *__res
     }
     __syncthreads();
     if (t != 0) return;
-    if (explore_u[e] < epsilon) {                          // e_greedy.py:88
-        actions[e] = random_act[e];
-        return;
-    }
-    double mx = q[0];
-    for (int k = 1; k < n_actions; ++k) mx = fmax(mx, q[k]);
-    const double tol = 1e-8 + 1e-5 * fabs(mx);
-    int best = 0;
-    double bv = -1.0;
-    for (int k = 0; k < n_actions; ++k) {
-        const double v = fabs(q[k] - mx) <= tol ? tie_rand[(size_t)e * n_actions + k] : 0.0;
-        if (v > bv) { bv = v; best = k; }
-    }
-    actions[e] = best;
+    actions[e] = rlx::egreedy_choice_f64(q, n_actions, explore_u[e], random_act[e], tie_rand + (size_t)e * n_actions,
+                                         epsilon);
 }
 
 }  // namespace

@@ -674,3 +674,62 @@ class QRDQNNet(DQNNet):
             sync.all_reduce_sum(self.params.grads)
         self.apply_gradients(grad_scale, with_norm=not clipped)
         return self.loss
+
+
+class C51Net(DQNNet):
+    """CategoricalDQNNetworkParameters (agents/categorical_dqn_agent.py:29-32): the DQN torso (vector or image) under a
+    CategoricalQHead — ONE Dense(feat, A * atoms) whose output column a * atoms + j is the logit of atom j of action a
+    (heads/categorical_q_head.py:42-47).  Forward and backward go through the torso's and the Dense layer's generic
+    launches; the softmaxes, the projection, the cross entropy and its gradient come from rlx_c51_head_loss
+    (csrc/c51.hip).  The fused small-MLP update / acting kernels are DQN's alone: _fused and _act stay None."""
+    FUSED_MLP = False
+    FUSED_ACT = False
+    HEAD_LOSS_BACKWARD_ONE_LAUNCH = False
+
+    def __init__(self, device, obs_shape, n_actions, atoms, v_min=-10.0, v_max=10.0, **kw):
+        kw.pop("replace_mse_with_huber_loss", None)
+        kw.pop("dueling", None)
+        super().__init__(device, obs_shape, n_actions * atoms, dueling=False, **kw)
+        self.A, self.N, self.AN = n_actions, int(atoms), n_actions * int(atoms)
+        self._fused, self._act = None, None
+        # the support, as the reference agent and head build it (fp64 on the host), uploaded once
+        self.z_values = np.linspace(v_min, v_max, self.N)
+        self.z = torch.from_numpy(self.z_values).to(device)
+        self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)      # per-row loss partials
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def distribution_logits(self, obs, B, use_target=False, tag="q"):
+        """the head's Dense output [B, A * atoms], before the softmax (a Tensor; .data is the buffer)."""
+        return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag)
+
+    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount, grad_scale=1.0,
+                         sync=None, states_pair=None, per_errors=None, m_out=None, target_actions_out=None,
+                         action_losses_out=None):
+        """CategoricalDQNAgent.learn_from_batch (agents/categorical_dqn_agent.py:104-167), all on device: target(s') and
+        online(s) logits, rlx_c51_head_loss (target action, projection, cross entropy, dlogits, the taken action's cross
+        entropy into per_errors), backward, Adam."""
+        ctx, AN = self.ctx, self.AN
+        if states_pair is not None:
+            # parallel_prediction (categorical_dqn_agent.py:109-112): online(s) and target(s') as two towers of the
+            # same launches
+            cols = int(np.prod(self.obs_shape))
+            x = G.Tensor(states_pair.view(2, B, cols), B, cols, 2, u8=self.image, div=255.0 if self.image else 1.0)
+            acts2 = self.torso.forward(ctx, x, tag="pair", pair=True)
+            q2 = self.q_head.forward(ctx, acts2[-1], tag="pair", pair=True)
+            q_next = q2.data[1].view(B, AN)
+            acts = [x.tower_view(0)] + [a.tower(0) for a in acts2[1:]]
+            q = q2.tower(0)
+        else:
+            q_next = self.distribution_logits(next_obs, B, use_target=True, tag="next_t").data.view(B, AN)
+            acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+            q = self.q_head.forward(ctx, acts[-1], tag="train")
+        dq = q.ensure_grad()
+        self.lib.c51_head_loss(q.data, AN, q_next, AN, self.z, actions, rewards, game_overs, float(discount), self.N,
+                               self.A, B, 1.0, dq, AN, per_errors, self.loss_ws, self.ticket, self.loss, self.status,
+                               m_out, target_actions_out, action_losses_out, ctx.stream)
+        self._backward_from_q(acts, q, None, B)
+        clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
+        if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
+            sync.all_reduce_sum(self.params.grads)
+        self.apply_gradients(grad_scale, with_norm=not clipped)
+        return self.loss

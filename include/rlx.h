@@ -866,6 +866,38 @@ int rlx_quantile_egreedy(const float *quantiles, long long ld, int n_atoms, cons
                          const int *random_actions, const double *tie_break_uniforms, double epsilon, int n_env,
                          int n_actions, double *q_out, int *actions, void *stream);
 
+/* ------------------------------------------------------------------ Categorical DQN (C51) -- */
+/* CategoricalDQNAgent.learn_from_batch + the CategoricalQHead loss (agents/categorical_dqn_agent.py:104-167,
+ * heads/categorical_q_head.py:42-58) in ONE launch, one workgroup per batch row.  logits / logits_next_target: the online
+ * head's Dense output on s / the target's on s', [batch][A*N] (column a*N + j = atom j of action a); z: the support,
+ * [N] fp64 (np.linspace(v_min, v_max, N) from the host).  Softmax over the atoms: mx = max, e_j = fp32(exp((double)(x_j -
+ * mx))), s = the e_j summed in atom order (fp32), p_j = e_j / s.  Per row: a* = argmax of the target's fp64 expectations
+ * sum_j p'_j z_j (atom order, first maximum); the projection for j = 0 .. N-1 in this order, fp64:
+ * tz = fmax(fmin(r + (1 - done) * discount * z_j, z_{N-1}), z_0), bj = (tz - z_0) / (z_1 - z_0), l = floor(bj),
+ * u = ceil(bj), m[l] += p'[a*, j] (u - bj), m[u] += p'[a*, j] (bj - l), m rounded to fp32 once (an integer bj drops
+ * that atom's mass, as the reference does; u == N, which rounding can produce at v_max on some supports and on which the
+ * reference raises, is left out).  Labels: m for the taken action, the online softmax itself for the others;
+ * loss = sum_b sum_a sum_j label_j (log s - (x_j - mx)) (a SUM over batch and actions);
+ * dlogits[b][a_b*N + j] = grad_scale * (p_j - m_j), zero elsewhere.  per_errors [batch] fp64 (optional): the taken action's
+ * cross entropy (0 for an invalid action).  row_partials: [batch] floats of workspace; ticket: one zero-initialised word
+ * (left at zero); the loss is summed in a fixed order (bit-identical run to run).  status |= 1 for an action outside
+ * [0, A).  m_out [batch][N], target_actions_out [batch] and action_losses_out [batch][A] are optional (null).
+ * 2 <= N <= 256, A <= 18, batch <= 256. */
+int rlx_c51_head_loss(const float *logits, long long ld_logits, const float *logits_next_target, long long ld_next,
+                      const double *z, const int *actions, const float *rewards, const unsigned char *game_overs,
+                      double discount, int n_atoms, int n_actions, int batch, float grad_scale, float *dlogits,
+                      long long ld_dlogits, double *per_errors, float *row_partials, unsigned int *ticket,
+                      float *loss_scalar, int *status, float *m_out, int *target_actions_out, float *action_losses_out,
+                      void *stream);
+/* distribution_prediction_to_q_values (categorical_dqn_agent.py:86-87: fp64 expectations of the softmax over z, summed
+ * in atom order) + rlx_egreedy's choice on them with the isclose tie test in fp64 (e_greedy.py:84-101).  logits:
+ * [n_env][ld], ld >= A*N; the draws as rlx_egreedy takes them; q_out [n_env][A] fp64 is optional (null).
+ * 2 <= N <= 256, A <= 18. */
+int rlx_categorical_egreedy(const float *logits, long long ld, const double *z, int n_atoms,
+                            const double *explore_uniforms, const int *random_actions,
+                            const double *tie_break_uniforms, double epsilon, int n_env, int n_actions, double *q_out,
+                            int *actions, void *stream);
+
 /* ------------------------------------------------ synthetic vector environment -- */
 /* Device-resident stand-in for Environment.step (environments/environment.py:276-327) on the
  * BASELINE workloads: fixed-length episodes, Philox4x32-10 observations/rewards keyed by
