@@ -110,7 +110,8 @@ class DQNAgent(VectorOffPolicyAgent):
             net.q_act(states, self.n_env, d["u"], d["ra"], d["tie"], eps, self._q_buf(), self.actions)
             return self.actions
         self._run(("q", self.n_env), lambda: self._q_forward(states))
-        self.exploration_policy.get_action(self._q_act, draws, self.actions)
+        eps, d = self.exploration_policy.stage(draws)
+        self._select_actions(d["u"], d["ra"], d["tie"], eps)
         return self.actions
 
     def _q_buf(self):
@@ -121,6 +122,11 @@ class DQNAgent(VectorOffPolicyAgent):
     def _q_forward(self, states):
         q = self.networks["main"].q_values(states, self.n_env, tag="act")
         self._q_act = q.data.view(self.n_env, self.A)
+
+    def _select_actions(self, u, ra, tie, eps):
+        """the acting reduction on staged draws: what _q_forward left -> self.actions (here: epsilon-greedy on Q)."""
+        self.lib.egreedy(self._q_act, self.A, u, ra, tie, float(eps), self.n_env, self.A, self.actions,
+                         _rlx.current_stream())
 
     # ------------------------------------------------------------------------------- training
     PER_UPDATE_RIDES = True
@@ -233,15 +239,14 @@ class DQNAgent(VectorOffPolicyAgent):
     def _step_body(self, k, start, with_act):
         """the device work of one step: [act, env, store] then updates start .. start+k-1 of the record."""
         v = self._step_record(self._rec_k)["views"]
-        mem, s, alg = self.memory, _rlx.current_stream(), self.ap.algorithm
+        mem = self.memory
         if with_act:
             net = self.networks["main"]
             if net.can_act_fused(self.n_env):
                 net.q_act(mem.current_states(), self.n_env, v["u"], v["ra"], v["tie"], 0.0, self._q_buf(), self.actions)
             else:
                 self._q_forward(mem.current_states())
-                self.lib.egreedy(self._q_act, self.A, v["u"], v["ra"], v["tie"], 0.0, self.n_env, self.A,
-                                 self.actions, s)
+                self._select_actions(v["u"], v["ra"], v["tie"], 0.0)
             self.env.launch_step()
             self._observe_device(v["dst"])
         B = self.batch_size

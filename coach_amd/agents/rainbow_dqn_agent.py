@@ -9,4 +9,5 @@ class RainbowDQNAgentParameters(object):
     def __init__(self):
         raise NotImplementedError("Rainbow DQN is not implemented by this engine (noisy nets and the n-step "
                                   "prioritized replay of its categorical head are out of its scope; the categorical "
-                                  "head itself is coach_amd.agents.categorical_dqn_agent)")
+                                  "head itself is coach_amd.agents.categorical_dqn_agent, and a further head "
+                                  "would sit on coach_amd.agents.distributional_dqn_agent as it does)")

@@ -14,14 +14,13 @@
 // (an fp64 exp rounded once is the correctly rounded fp32 exp but for double-rounding cases of probability ~2^-29).
 // The Q value of an action is fp64: q = sum_{j ascending} (double)p_j * z_j, z the host's np.linspace (numpy's dot may
 // associate differently: a few ulp).  Compiled with -ffp-contract=off so the fp64 arithmetic rounds like numpy.
-#include "egreedy_choice.hpp"
-#include "rlx_common.hpp"
+#include "distributional_head.hpp"
 
 namespace {
 
-constexpr int kC51Threads = 256;   // one thread per atom (N <= 256); four waves of 64
-constexpr int kC51MaxAtoms = 256;
-constexpr int kC51MaxActions = 18;
+constexpr int kC51Threads = rlx::kDistLossThreads;
+constexpr int kC51MaxAtoms = rlx::kDistLossThreads;   // one thread per atom
+constexpr int kC51MaxActions = rlx::kDistMaxActions;
 
 // Softmax of `rows` rows of N values held in LDS, in place.  mx[r] / sum[r] keep each row's maximum and fp32 sum of
 // exponentials.  The serial parts (maximum, sum in atom order) are one thread per row; the exponentials and the
@@ -93,8 +92,7 @@ __global__ void __launch_bounds__(kC51Threads) c51_head_loss_kernel(const C51Arg
     __shared__ bool last_s;
     const int b = blockIdx.x, t = threadIdx.x, N = a.n_atoms, A = a.n_actions, AN = A * N;
     const int act = a.actions[b];
-    const bool valid = act >= 0 && act < A;
-    if (t == 0 && !valid) atomicOr(a.status, 1);
+    const bool valid = rlx::taken_action_valid(act, A, t, a.status);
     const float *xn = a.logits_next + (size_t)b * a.ld_next;
     const float *xo = a.logits + (size_t)b * a.ld_logits;
     float *pn = p_s, *po = p_s + AN;
@@ -107,14 +105,11 @@ __global__ void __launch_bounds__(kC51Threads) c51_head_loss_kernel(const C51Arg
     __syncthreads();
     softmax_rows<kC51Threads>(p_s, mx_s, sum_s, 2 * A, N, t);
 
-    // a*_b = argmax_a of the TARGET network's fp64 expectations (np.argmax: the first maximum)
+    // a*_b = argmax_a of the TARGET network's fp64 expectations
     if (t < A) qn[t] = expectation(pn + t * N, z_s, N);
     __syncthreads();
     if (t == 0) {
-        int best = 0;
-        double bv = qn[0];
-        for (int k = 1; k < A; ++k)
-            if (qn[k] > bv) { bv = qn[k]; best = k; }
+        const int best = rlx::first_argmax_f64(qn, A);
         best_s = best;
         if (a.target_actions_out) a.target_actions_out[b] = best;
     }
@@ -173,29 +168,17 @@ __global__ void __launch_bounds__(kC51Threads) c51_head_loss_kernel(const C51Arg
     __syncthreads();
     // total_loss = reduce_sum over batch AND actions: the row's actions in order, then the row partials summed in a
     // fixed tree by the workgroup that draws the last ticket
+    float row = 0.f;
     if (t == 0) {
-        float row = 0.f;
         for (int k = 0; k < A; ++k) row += ce_s[k];
         if (a.per_errors) a.per_errors[b] = valid ? (double)ce_s[act] : 0.0;
-        __hip_atomic_store(&a.row_partials[b], row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned int old = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last_s = old == (unsigned int)(a.batch - 1);
-        if (last_s) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __syncthreads();
-    if (!last_s) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    red[t] = t < a.batch ? __hip_atomic_load(&a.row_partials[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    __syncthreads();
-    for (int d = kC51Threads >> 1; d > 0; d >>= 1) {
-        if (t < d) red[t] += red[t + d];
-        __syncthreads();
-    }
+    if (!rlx::ticketed_batch_sum<kC51Threads>(row, b, a.batch, a.row_partials, a.ticket, red, &last_s, t)) return;
     if (t == 0) a.loss[0] = red[0];
 }
 
 // One wave per env: the softmax of each action's logits in LDS, lanes a < A form the fp64 expectations, lane 0 makes
-// the epsilon-greedy choice on them (egreedy_choice.hpp).
+// the epsilon-greedy choice on them (distributional_head.hpp).
 __global__ void __launch_bounds__(64) categorical_egreedy_kernel(const float *__restrict__ logits, long long ld,
                                                                  const double *__restrict__ z, int n_atoms,
                                                                  const double *__restrict__ explore_u,
@@ -235,12 +218,9 @@ int rlx_c51_head_loss(const float *logits, long long ld_logits, const float *log
     RLX_REQUIRE(logits && logits_next_target && z && actions && rewards && game_overs && dlogits && row_partials &&
                     ticket && loss_scalar && status,
                 "rlx_c51_head_loss: null pointer");
-    RLX_REQUIRE(n_atoms >= 2 && n_atoms <= kC51MaxAtoms && n_actions >= 1 && n_actions <= kC51MaxActions && batch >= 1 &&
-                    batch <= kC51Threads,
-                "rlx_c51_head_loss: unsupported sizes (2 <= atoms=%d <= 256, actions=%d <= 18, batch=%d <= 256)", n_atoms,
-                n_actions, batch);
-    const long long row = (long long)n_atoms * n_actions;
-    RLX_REQUIRE(ld_logits >= row && ld_next >= row && ld_dlogits >= row, "rlx_c51_head_loss: leading dimension < A*N");
+    if (const int rc = rlx::check_head_loss_shape("rlx_c51_head_loss", 2, n_atoms, n_actions, batch, ld_logits, ld_next,
+                                                  ld_dlogits))
+        return rc;
     C51Args a;
     a.logits = logits; a.ld_logits = ld_logits; a.logits_next = logits_next_target; a.ld_next = ld_next; a.z = z;
     a.actions = actions; a.rewards = rewards; a.game_overs = game_overs; a.discount = discount;

@@ -12,13 +12,12 @@
 //   q = sum_{j = 0 .. N-1, in this order} (double)theta[a*N + j] * (1.0 / N)
 // (numpy's BLAS dot may associate differently: the means agree to a few ulp, the decisions on them exactly unless two
 // actions are within that distance).  Compiled with -ffp-contract=off so the fp64 arithmetic rounds like numpy.
-#include "egreedy_choice.hpp"
-#include "rlx_common.hpp"
+#include "distributional_head.hpp"
 
 namespace {
 
-constexpr int kQrThreads = 256;   // one thread per atom (N <= 256); four waves of 64
-constexpr int kQrMaxActions = 18;
+constexpr int kQrThreads = rlx::kDistLossThreads;
+constexpr int kQrMaxActions = rlx::kDistMaxActions;
 
 __device__ __forceinline__ double atom_mean(const float *row, int n_atoms, double w) {
     double s = 0.0;
@@ -64,20 +63,16 @@ __global__ void __launch_bounds__(kQrThreads) qr_dqn_head_loss_kernel(const QrAr
     const double w = 1.0 / (double)N;
     const float *tn = a.theta_next + (size_t)b * a.ld_next;
     const int act = a.actions[b];
-    const bool valid = act >= 0 && act < A;
-    if (t == 0 && !valid) atomicOr(a.status, 1);
+    const bool valid = rlx::taken_action_valid(act, A, t, a.status);
 
-    // (2) a*_b = argmax_a of the TARGET network's fp64 means (np.argmax: the first maximum)
+    // (2) a*_b = argmax_a of the TARGET network's fp64 means
     for (int c = t; c < A * N; c += kQrThreads) tn_s[c] = tn[c];
     __syncthreads();
     if (t < A) qn[t] = atom_mean(tn_s + t * N, N, w);
     if (t < N) th[t] = valid ? a.theta[(size_t)b * a.ld_theta + (size_t)act * N + t] : 0.f;
     __syncthreads();
     if (t == 0) {
-        int best = 0;
-        double bv = qn[0];
-        for (int k = 1; k < A; ++k)
-            if (qn[k] > bv) { bv = qn[k]; best = k; }
+        const int best = rlx::first_argmax_f64(qn, A);
         best_s = best;
         if (a.target_actions_out) a.target_actions_out[b] = best;
     }
@@ -135,26 +130,12 @@ __global__ void __launch_bounds__(kQrThreads) qr_dqn_head_loss_kernel(const QrAr
         __syncthreads();
     }
     // the batch sum: the row partials, summed in a fixed tree by the workgroup that draws the last ticket
-    if (t == 0) {
-        __hip_atomic_store(&a.row_partials[b], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned int old = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last_s = old == (unsigned int)(a.batch - 1);
-        if (last_s) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!last_s) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    red[t] = t < a.batch ? __hip_atomic_load(&a.row_partials[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    __syncthreads();
-    for (int d = kQrThreads >> 1; d > 0; d >>= 1) {
-        if (t < d) red[t] += red[t + d];
-        __syncthreads();
-    }
+    if (!rlx::ticketed_batch_sum<kQrThreads>(red[0], b, a.batch, a.row_partials, a.ticket, red, &last_s, t)) return;
     if (t == 0) a.loss[0] = red[0] / (float)N;
 }
 
 // One wave per env: lanes a < A form the fp64 means (order above), lane 0 makes the epsilon-greedy choice on them
-// (egreedy_choice.hpp: numpy's isclose in fp64, e_greedy.py:93-94).
+// (distributional_head.hpp: numpy's isclose in fp64, e_greedy.py:93-94).
 __global__ void __launch_bounds__(64) quantile_egreedy_kernel(const float *__restrict__ quant, long long ld, int n_atoms,
                                                               const double *__restrict__ explore_u,
                                                               const int *__restrict__ random_act,
@@ -186,12 +167,9 @@ int rlx_qr_dqn_head_loss(const float *theta, long long ld_theta, const float *th
     RLX_REQUIRE(theta && theta_next_target && actions && rewards && game_overs && dtheta && row_partials && ticket &&
                     loss_scalar && status,
                 "rlx_qr_dqn_head_loss: null pointer");
-    RLX_REQUIRE(n_atoms >= 1 && n_atoms <= kQrThreads && n_actions >= 1 && n_actions <= kQrMaxActions && batch >= 1 &&
-                    batch <= kQrThreads,
-                "rlx_qr_dqn_head_loss: unsupported sizes (atoms=%d <= 256, actions=%d <= 18, batch=%d <= 256)", n_atoms,
-                n_actions, batch);
-    const long long row = (long long)n_atoms * n_actions;
-    RLX_REQUIRE(ld_theta >= row && ld_next >= row && ld_dtheta >= row, "rlx_qr_dqn_head_loss: leading dimension < A*N");
+    if (const int rc = rlx::check_head_loss_shape("rlx_qr_dqn_head_loss", 1, n_atoms, n_actions, batch, ld_theta,
+                                                  ld_next, ld_dtheta))
+        return rc;
     QrArgs a;
     a.theta = theta; a.ld_theta = ld_theta; a.theta_next = theta_next_target; a.ld_next = ld_next;
     a.actions = actions; a.rewards = rewards; a.game_overs = game_overs; a.discount = discount; a.kappa = kappa;

@@ -4,13 +4,12 @@
 Every env keeps its own ``current_random_value`` exactly like one reference policy instance; the
 host makes each env's draws from the global legacy np.random stream in env order
 (explore: ``action_space.sample()`` = np.random.choice(n); greedy: np.random.random(n) for the
-tie-break; then np.random.rand() for the next step), the device applies them to the Q values
-(rlx_egreedy).
+tie-break; then np.random.rand() for the next step) and stages them; the agent's acting kernel applies them to its
+action values (rlx_egreedy for DQN).
 """
 import numpy as np
 import torch
 
-from .. import _rlx
 from ..core_types import RunPhase
 from ..schedules import LinearSchedule
 
@@ -31,7 +30,6 @@ class EGreedy(object):
         self.epsilon_schedule = params.epsilon_schedule
         self.evaluation_epsilon = params.evaluation_epsilon
         self.phase = RunPhase.HEATUP
-        self.lib = _rlx.lib()
         self.current_random_value = np.array([np.random.rand() for _ in range(n_env)])   # :82
         from ..staging import Stager
         self._st = dict(u=Stager((n_env,), torch.float64, device), ra=Stager((n_env,), torch.int32, device),
@@ -69,9 +67,3 @@ class EGreedy(object):
         st = self._st
         coded = np.where(u < eps, -1.0, 2.0)
         return 0.0, dict(u=st["u"].push(coded), ra=st["ra"].push(ra), tie=st["tie"].push(tie))
-
-    def get_action(self, q_values, draws, out_actions):
-        eps, d = self.stage(draws)
-        self.lib.egreedy(q_values, self.A, d["u"], d["ra"], d["tie"], float(eps), self.n_env, self.A,
-                         out_actions, _rlx.current_stream())
-        return out_actions

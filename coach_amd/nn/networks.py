@@ -556,18 +556,10 @@ class DQNNet(_NetBase):
             self.grad_norm()
         return self.loss
 
-    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount,
-                         importance_weights=None, td_errors=None, double_dqn=False, grad_scale=1.0,
-                         sync=None, states_pair=None):
-        """DQNAgent.learn_from_batch (agents/dqn_agent.py:81-113), all on device."""
-        ctx = self.ctx
-        if self._fused is not None and sync is None and B <= 32 and obs.is_contiguous() and next_obs.is_contiguous():
-            w = importance_weights
-            if w is not None and w.dtype != torch.float64:
-                w = w.double()
-            return self._fused_learn(obs, next_obs, B, actions, rewards, game_overs, discount, w, td_errors,
-                                     double_dqn, grad_scale)
-        sel = self.q_values(next_obs, B, tag="next_o").data.view(B, self.A) if double_dqn else None
+    def _online_and_target_forward(self, obs, next_obs, B, states_pair):
+        """the target network on s' and the online network on s -> (acts, q, saved, q_next): the online pass as the
+        backward pass needs it (saved: the dueling head's tensors, else None) and the target's head output [B, width]."""
+        ctx, saved = self.ctx, None
         if states_pair is not None and not self.dueling:
             # parallel_prediction (dqn_agent.py:86-89): online(s) and target(s') as two towers of the
             # same launches — the replay collates states / next_states into one [2, B, ...] buffer
@@ -581,16 +573,38 @@ class DQNNet(_NetBase):
             else:
                 acts2 = self.torso.forward(ctx, x, tag="pair", pair=True)
                 q2 = self.q_head.forward(ctx, acts2[-1], tag="pair", pair=True)
-            q_next = q2.data[1].view(B, self.A)
+            q_next = q2.data[1].view(B, -1)
             acts = [x.tower_view(0)] + [a.tower(0) for a in acts2[1:]]
             q = q2.tower(0)
         else:
-            q_next = self.q_values(next_obs, B, use_target=True, tag="next_t").data.view(B, self.A)
+            q_next = self.q_values(next_obs, B, use_target=True, tag="next_t").data.view(B, -1)
             acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
             if self.dueling:
                 q, saved = self._dueling_forward(acts[-1], B, "train", train=True)
             else:
                 q = self.q_head.forward(ctx, acts[-1], tag="train")
+        return acts, q, saved, q_next
+
+    def _apply_update(self, grad_scale, sync):
+        """the gradients in params.grads -> the weights: clip, share between the workers, Adam."""
+        clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
+        if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
+            sync.all_reduce_sum(self.params.grads)
+        self.apply_gradients(grad_scale, with_norm=not clipped)
+
+    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount,
+                         importance_weights=None, td_errors=None, double_dqn=False, grad_scale=1.0,
+                         sync=None, states_pair=None):
+        """DQNAgent.learn_from_batch (agents/dqn_agent.py:81-113), all on device."""
+        ctx = self.ctx
+        if self._fused is not None and sync is None and B <= 32 and obs.is_contiguous() and next_obs.is_contiguous():
+            w = importance_weights
+            if w is not None and w.dtype != torch.float64:
+                w = w.double()
+            return self._fused_learn(obs, next_obs, B, actions, rewards, game_overs, discount, w, td_errors,
+                                     double_dqn, grad_scale)
+        sel = self.q_values(next_obs, B, tag="next_o").data.view(B, self.A) if double_dqn else None
+        acts, q, saved, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
         dq = q.ensure_grad()
         # TD targets, |TD errors|, QHead loss and its gradient in one launch (importance weights are
         # the fp64 weights of the prioritized replay, or fp32 -> converted, or None)
@@ -614,122 +628,86 @@ class DQNNet(_NetBase):
             self.lib.dqn_head_loss(q.data, self.A, q_next, sel, self.A, actions, rewards, game_overs, w,
                                    float(discount), B, self.A, int(self.huber), 1.0, dq, self.A, td_errors,
                                    None, self.A, self.loss, self.status, ctx.stream)
-            self._backward_from_q(acts, q, saved if self.dueling else None, B)
-        clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
-        if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
-            sync.all_reduce_sum(self.params.grads)
-        self.apply_gradients(grad_scale, with_norm=not clipped)
+            self._backward_from_q(acts, q, saved, B)
+        self._apply_update(grad_scale, sync)
         return self.loss
 
 
-class QRDQNNet(DQNNet):
-    """QuantileRegressionDQNNetworkParameters (agents/qr_dqn_agent.py:28-33): the DQN torso (vector or image) under a
-    QuantileRegressionQHead — ONE Dense(feat, A * atoms) whose output column a * atoms + j is atom j of action a
-    (heads/quantile_regression_q_head.py:45-50).  Forward and backward go through the torso's and the Dense layer's
-    generic launches; the quantile Huber loss and its gradient come from rlx_qr_dqn_head_loss (csrc/qr_dqn.hip).
-    The fused small-MLP update / acting kernels are DQN's alone: _fused and _act stay None."""
+class DistributionalDQNNet(DQNNet):
+    """The DQN torso (vector or image) under a head that outputs N atoms per action: ONE Dense(feat, A * atoms) whose
+    output column a * atoms + j is atom j of action a.  Forward and backward go through the torso's and the Dense
+    layer's generic launches; what the atoms mean, and so the loss and its gradient, is the subclass's `_head_loss`
+    (one launch, csrc/qr_dqn.hip or csrc/c51.hip; their shared parts: csrc/distributional_head.hpp).  The fused
+    small-MLP update / acting kernels and the Q head inside the torso's last launch are DQN's alone: with these flags
+    _fused and _act stay None and the head's forward is a launch of its own."""
     FUSED_MLP = False
     FUSED_ACT = False
-    HEAD_LOSS_BACKWARD_ONE_LAUNCH = False
+    HEAD_FORWARD_WITH_TORSO = False
 
-    def __init__(self, device, obs_shape, n_actions, atoms, huber_loss_interval=1.0, **kw):
+    def __init__(self, device, obs_shape, n_actions, atoms, **kw):
         kw.pop("replace_mse_with_huber_loss", None)
         kw.pop("dueling", None)
         super().__init__(device, obs_shape, n_actions * atoms, dueling=False, **kw)
         self.A, self.N, self.AN = n_actions, int(atoms), n_actions * int(atoms)
-        self.kappa = float(huber_loss_interval)
-        self._fused, self._act = None, None
         self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)      # per-row loss partials
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def quantiles(self, obs, B, use_target=False, tag="q"):
-        """the head output [B, A * atoms] (a Tensor; .data is the buffer)."""
+    def head_output(self, obs, B, use_target=False, tag="q"):
+        """the head's Dense output [B, A * atoms] (a Tensor; .data is the buffer)."""
         return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag)
 
     def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount, grad_scale=1.0,
-                         sync=None, states_pair=None, targets_out=None, tau_out=None, target_actions_out=None):
-        """QuantileRegressionDQNAgent.learn_from_batch (agents/qr_dqn_agent.py:99-137), all on device: target(s') and
-        online(s) quantiles, rlx_qr_dqn_head_loss (target action, TD targets, midpoints, loss, dtheta), backward, Adam."""
-        ctx, AN = self.ctx, self.AN
-        if states_pair is not None:
-            # parallel_prediction (qr_dqn_agent.py:103-106): online(s) and target(s') as two towers of the same launches
-            cols = int(np.prod(self.obs_shape))
-            x = G.Tensor(states_pair.view(2, B, cols), B, cols, 2, u8=self.image, div=255.0 if self.image else 1.0)
-            acts2 = self.torso.forward(ctx, x, tag="pair", pair=True)
-            q2 = self.q_head.forward(ctx, acts2[-1], tag="pair", pair=True)
-            q_next = q2.data[1].view(B, AN)
-            acts = [x.tower_view(0)] + [a.tower(0) for a in acts2[1:]]
-            q = q2.tower(0)
-        else:
-            q_next = self.quantiles(next_obs, B, use_target=True, tag="next_t").data.view(B, AN)
-            acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
-            q = self.q_head.forward(ctx, acts[-1], tag="train")
+                         sync=None, states_pair=None, **head_outs):
+        """the agents' learn_from_batch, all on device: the target's head output on s' and the online one on s (two
+        towers of the same launches where the replay collated states_pair), _head_loss, backward, Adam.
+        head_outs: the optional outputs of the subclass's _head_loss, by keyword."""
+        acts, q, _, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
         dq = q.ensure_grad()
-        self.lib.qr_dqn_head_loss(q.data, AN, q_next, AN, actions, rewards, game_overs, float(discount), self.kappa,
-                                  self.N, self.A, B, 1.0, dq, AN, self.loss_ws, self.ticket, self.loss, self.status,
-                                  targets_out, tau_out, target_actions_out, ctx.stream)
+        self._head_loss(q.data, q_next, dq, actions, rewards, game_overs, float(discount), B, **head_outs)
         self._backward_from_q(acts, q, None, B)
-        clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
-        if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
-            sync.all_reduce_sum(self.params.grads)
-        self.apply_gradients(grad_scale, with_norm=not clipped)
+        self._apply_update(grad_scale, sync)
         return self.loss
 
 
-class C51Net(DQNNet):
-    """CategoricalDQNNetworkParameters (agents/categorical_dqn_agent.py:29-32): the DQN torso (vector or image) under a
-    CategoricalQHead — ONE Dense(feat, A * atoms) whose output column a * atoms + j is the logit of atom j of action a
-    (heads/categorical_q_head.py:42-47).  Forward and backward go through the torso's and the Dense layer's generic
-    launches; the softmaxes, the projection, the cross entropy and its gradient come from rlx_c51_head_loss
-    (csrc/c51.hip).  The fused small-MLP update / acting kernels are DQN's alone: _fused and _act stay None."""
-    FUSED_MLP = False
-    FUSED_ACT = False
-    HEAD_LOSS_BACKWARD_ONE_LAUNCH = False
+class QRDQNNet(DistributionalDQNNet):
+    """QuantileRegressionDQNNetworkParameters (agents/qr_dqn_agent.py:28-33): a QuantileRegressionQHead
+    (heads/quantile_regression_q_head.py:45-50); the quantile Huber loss and its gradient come from
+    rlx_qr_dqn_head_loss (csrc/qr_dqn.hip)."""
+
+    def __init__(self, device, obs_shape, n_actions, atoms, huber_loss_interval=1.0, **kw):
+        super().__init__(device, obs_shape, n_actions, atoms, **kw)
+        self.kappa = float(huber_loss_interval)
+
+    quantiles = DistributionalDQNNet.head_output
+
+    def _head_loss(self, q, q_next, dq, actions, rewards, game_overs, discount, B, targets_out=None, tau_out=None,
+                   target_actions_out=None):
+        """QuantileRegressionDQNAgent.learn_from_batch (agents/qr_dqn_agent.py:99-137): target action, TD targets,
+        midpoints, loss, dtheta."""
+        AN = self.AN
+        self.lib.qr_dqn_head_loss(q, AN, q_next, AN, actions, rewards, game_overs, discount, self.kappa, self.N, self.A,
+                                  B, 1.0, dq, AN, self.loss_ws, self.ticket, self.loss, self.status, targets_out,
+                                  tau_out, target_actions_out, self.ctx.stream)
+
+
+class C51Net(DistributionalDQNNet):
+    """CategoricalDQNNetworkParameters (agents/categorical_dqn_agent.py:29-32): a CategoricalQHead
+    (heads/categorical_q_head.py:42-47) whose outputs are logits; the softmaxes, the projection, the cross entropy and
+    its gradient come from rlx_c51_head_loss (csrc/c51.hip)."""
 
     def __init__(self, device, obs_shape, n_actions, atoms, v_min=-10.0, v_max=10.0, **kw):
-        kw.pop("replace_mse_with_huber_loss", None)
-        kw.pop("dueling", None)
-        super().__init__(device, obs_shape, n_actions * atoms, dueling=False, **kw)
-        self.A, self.N, self.AN = n_actions, int(atoms), n_actions * int(atoms)
-        self._fused, self._act = None, None
+        super().__init__(device, obs_shape, n_actions, atoms, **kw)
         # the support, as the reference agent and head build it (fp64 on the host), uploaded once
         self.z_values = np.linspace(v_min, v_max, self.N)
         self.z = torch.from_numpy(self.z_values).to(device)
-        self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)      # per-row loss partials
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def distribution_logits(self, obs, B, use_target=False, tag="q"):
-        """the head's Dense output [B, A * atoms], before the softmax (a Tensor; .data is the buffer)."""
-        return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag)
+    distribution_logits = DistributionalDQNNet.head_output       # before the softmax
 
-    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount, grad_scale=1.0,
-                         sync=None, states_pair=None, per_errors=None, m_out=None, target_actions_out=None,
-                         action_losses_out=None):
-        """CategoricalDQNAgent.learn_from_batch (agents/categorical_dqn_agent.py:104-167), all on device: target(s') and
-        online(s) logits, rlx_c51_head_loss (target action, projection, cross entropy, dlogits, the taken action's cross
-        entropy into per_errors), backward, Adam."""
-        ctx, AN = self.ctx, self.AN
-        if states_pair is not None:
-            # parallel_prediction (categorical_dqn_agent.py:109-112): online(s) and target(s') as two towers of the
-            # same launches
-            cols = int(np.prod(self.obs_shape))
-            x = G.Tensor(states_pair.view(2, B, cols), B, cols, 2, u8=self.image, div=255.0 if self.image else 1.0)
-            acts2 = self.torso.forward(ctx, x, tag="pair", pair=True)
-            q2 = self.q_head.forward(ctx, acts2[-1], tag="pair", pair=True)
-            q_next = q2.data[1].view(B, AN)
-            acts = [x.tower_view(0)] + [a.tower(0) for a in acts2[1:]]
-            q = q2.tower(0)
-        else:
-            q_next = self.distribution_logits(next_obs, B, use_target=True, tag="next_t").data.view(B, AN)
-            acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
-            q = self.q_head.forward(ctx, acts[-1], tag="train")
-        dq = q.ensure_grad()
-        self.lib.c51_head_loss(q.data, AN, q_next, AN, self.z, actions, rewards, game_overs, float(discount), self.N,
-                               self.A, B, 1.0, dq, AN, per_errors, self.loss_ws, self.ticket, self.loss, self.status,
-                               m_out, target_actions_out, action_losses_out, ctx.stream)
-        self._backward_from_q(acts, q, None, B)
-        clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
-        if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
-            sync.all_reduce_sum(self.params.grads)
-        self.apply_gradients(grad_scale, with_norm=not clipped)
-        return self.loss
+    def _head_loss(self, q, q_next, dq, actions, rewards, game_overs, discount, B, per_errors=None, m_out=None,
+                   target_actions_out=None, action_losses_out=None):
+        """CategoricalDQNAgent.learn_from_batch (agents/categorical_dqn_agent.py:104-167): target action, projection,
+        cross entropy, dlogits, the taken action's cross entropy into per_errors."""
+        AN = self.AN
+        self.lib.c51_head_loss(q, AN, q_next, AN, self.z, actions, rewards, game_overs, discount, self.N, self.A, B, 1.0,
+                               dq, AN, per_errors, self.loss_ws, self.ticket, self.loss, self.status, m_out,
+                               target_actions_out, action_losses_out, self.ctx.stream)
