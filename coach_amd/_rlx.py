@@ -266,6 +266,15 @@ class SplitkJob(ctypes.Structure):
         return (self.M * self.N + self.N) * self.batch * self.splits if self.splits > 1 else 0
 
 
+class NoisyLayer(ctypes.Structure):
+    """rlx_noisy_layer (include/rlx.h) — field order must match the header."""
+    _fields_ = [("f", ctypes.c_void_p), ("f64", ctypes.c_void_p), ("K", ctypes.c_int), ("N", ctypes.c_int),
+                ("layer", ctypes.c_int)]
+
+
+NOISY_PASSES = 4                # rlx.h RLX_NOISY_PASSES
+NOISY_MAX_LAYERS = 8            # rlx.h RLX_NOISY_MAX_LAYERS: layers of one rlx_noisy_sample launch
+NOISY_PASS = {"act": 0, "online": 1, "target": 2, "online_next": 3}
 ADAM_TICKET_WORDS = 1056        # rlx.h RLX_ADAM_TICKET_WORDS
 ABI_VERSION = 11                # rlx_abi_version() of the library this module's structures and buffer sizes match
 MAX_SPLITK_JOBS = 8

@@ -72,3 +72,8 @@ class CategoricalDQNAgent(DistributionalDQNAgent):
         self.lib.categorical_egreedy(self._head_act, self.A * self.N, self.networks["main"].z, self.N, u, ra, tie,
                                      float(eps), self.n_env, self.A, self._q_buf(), self.actions,
                                      _rlx.current_stream())
+
+    def _argmax_actions(self):
+        """ParameterNoise: np.argmax of the same fp64 expectations (the first maximum, no draws)."""
+        self.lib.categorical_argmax(self._head_act, self.A * self.N, self.networks["main"].z, self.N, self.n_env,
+                                    self.A, self._q_buf(), self.actions, _rlx.current_stream())

@@ -13,7 +13,6 @@ policy: either the loss kernel leaves an error per batch row in self.td_errors, 
 """
 import torch
 
-from ..exploration_policies.e_greedy import EGreedy
 from ..memories.non_episodic.prioritized_experience_replay import PrioritizedExperienceReplay
 from .dqn_agent import DQNAgent
 from .vector_agent import VectorOffPolicyAgent
@@ -37,11 +36,12 @@ class DistributionalDQNAgent(DQNAgent):
             adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon, seed=self.ap.seed or 0,
             head_activation=net.heads_parameters[0].activation_function,
             head_gradient_rescale=net.heads_parameters[0].rescale_gradient_from_head_by_factor,
-            clip_gradients=net.clip_gradients)}
+            clip_gradients=net.clip_gradients, noisy=self._parameter_noise())}
+        self._key_network_noise()
         self.memory = self._make_memory(action_dim=None)
         if self.PER_REFUSAL and isinstance(self.memory, PrioritizedExperienceReplay):
             raise ValueError(self.PER_REFUSAL)
-        self.exploration_policy = EGreedy(self.A, self.n_env, self.device, self.ap.exploration)
+        self.exploration_policy = self._make_exploration_policy()
         self.actions = torch.zeros(self.n_env, dtype=torch.int32, device=self.device)
         # the loss kernel's error per batch row: what update_priorities receives
         self.td_errors = None if self.PER_REFUSAL else \

@@ -17,6 +17,7 @@ from ..architectures.head_parameters import DuelingQHeadParameters, QHeadParamet
 from ..architectures.scheme_views import SchemeViews
 from ..core_types import DeviceBatch, EnvironmentSteps, RunPhase
 from ..exploration_policies.e_greedy import EGreedy, EGreedyParameters
+from ..exploration_policies.parameter_noise import ParameterNoise, ParameterNoiseParameters, network_is_noisy
 from ..memories.non_episodic.experience_replay import ExperienceReplayParameters
 from ..memories.non_episodic.prioritized_experience_replay import PrioritizedExperienceReplay
 from ..nn.networks import DQNNet
@@ -85,13 +86,39 @@ class DQNAgent(VectorOffPolicyAgent):
             dueling=isinstance(net.heads_parameters[0], DuelingQHeadParameters),
             head_activation=net.heads_parameters[0].activation_function,
             head_gradient_rescale=net.heads_parameters[0].rescale_gradient_from_head_by_factor,
-            clip_gradients=net.clip_gradients)}
+            clip_gradients=net.clip_gradients, noisy=self._parameter_noise())}
+        self._key_network_noise()
         self.memory = self._make_memory(action_dim=None)
-        self.exploration_policy = EGreedy(self.A, self.n_env, self.device, self.ap.exploration)
+        self.exploration_policy = self._make_exploration_policy()
         self.actions = torch.zeros(self.n_env, dtype=torch.int32, device=self.device)
         self.td_errors = torch.zeros(self.batch_size, dtype=torch.float64, device=self.device)
         self.loss_acc = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._finish_init()
+
+    # ------------------------------------------------------------------------- ParameterNoise
+    def _parameter_noise(self):
+        """is the exploration policy ParameterNoise?  Then the network is built from noisy dense layers (the policy's
+        parameters marked the network wrappers, parameter_noise.py:79-90) and acting is a plain argmax."""
+        noisy = network_is_noisy(self.ap.network_wrappers["main"])
+        if isinstance(self.ap.exploration, ParameterNoiseParameters) != noisy:
+            raise ValueError("noisy dense layers and the ParameterNoise exploration policy come together")
+        self.parameter_noise = noisy
+        return noisy
+
+    def _key_network_noise(self):
+        """the key of the noisy layers' generator, as for noise_source = "device": (noise seed, rank)"""
+        if self.parameter_noise:
+            self._key_noise_generator()
+            self.rekey_networks()
+
+    def rekey_networks(self):
+        if getattr(self, "parameter_noise", False):
+            net = self.networks["main"]
+            net.noise_seed, net.noise_rank = self._noise_seed, self._noise_rank
+
+    def _make_exploration_policy(self):
+        cls = ParameterNoise if self.parameter_noise else EGreedy
+        return cls(self.A, self.n_env, self.device, self.ap.exploration)
 
     # --------------------------------------------------------------------------------- acting
     def random_actions(self):
@@ -103,6 +130,10 @@ class DQNAgent(VectorOffPolicyAgent):
     def choose_action(self, states):
         net = self.networks["main"]
         self.exploration_policy.phase = self.phase
+        if self.parameter_noise:
+            # noisy forward pass (fresh noise, read from the device counters) + np.argmax: no host draw at all
+            self._run(("q_argmax", self.n_env), lambda: (self._q_forward(states), self._argmax_actions()))
+            return self.actions
         draws = self.exploration_policy.draw()                       # host RNG, per env, in order
         if net.can_act_fused(self.n_env):
             # small MLP, a few envs: Q(s) and the epsilon-greedy choice are ONE launch
@@ -122,6 +153,10 @@ class DQNAgent(VectorOffPolicyAgent):
     def _q_forward(self, states):
         q = self.networks["main"].q_values(states, self.n_env, tag="act")
         self._q_act = q.data.view(self.n_env, self.A)
+
+    def _argmax_actions(self):
+        """ParameterNoise.get_action (parameter_noise.py:62-68): np.argmax of what _q_forward left — the first maximum."""
+        self.lib.argmax_rows(self._q_act, self.A, self.n_env, self.A, self.actions, _rlx.current_stream())
 
     def _select_actions(self, u, ra, tie, eps):
         """the acting reduction on staged draws: what _q_forward left -> self.actions (here: epsilon-greedy on Q)."""
@@ -180,8 +215,9 @@ class DQNAgent(VectorOffPolicyAgent):
     # every kernel are those of act() + train(): the results are bit-identical (tests/test_dqn_agent.py).
     def _step_graph_ok(self):
         from ..memories.non_episodic.experience_replay import ExperienceReplay
+        # (ParameterNoise: the record's epsilon-greedy draws do not exist; act() + train() run as they are)
         return (self.use_graphs and self.dist is None and self.phase == RunPhase.TRAIN and not self.image
-                and type(self.memory) is ExperienceReplay and self.signal_stats is None
+                and not self.parameter_noise and type(self.memory) is ExperienceReplay and self.signal_stats is None
                 and self.debug_draws is None and self.debug_losses is None
                 and hasattr(self.env, "launch_step") and hasattr(self.env, "host_tick"))
 

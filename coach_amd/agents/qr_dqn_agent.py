@@ -58,3 +58,8 @@ class QuantileRegressionDQNAgent(DistributionalDQNAgent):
         """get_q_values (qr_dqn_agent.py:75-76) + the epsilon-greedy choice on the fp64 atom means."""
         self.lib.quantile_egreedy(self._head_act, self.A * self.N, self.N, u, ra, tie, float(eps), self.n_env, self.A,
                                   self._q_buf(), self.actions, _rlx.current_stream())
+
+    def _argmax_actions(self):
+        """ParameterNoise: np.argmax of the same fp64 atom means (the first maximum, no draws)."""
+        self.lib.quantile_argmax(self._head_act, self.A * self.N, self.N, self.n_env, self.A, self._q_buf(),
+                                 self.actions, _rlx.current_stream())

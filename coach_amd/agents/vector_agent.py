@@ -290,11 +290,18 @@ class VectorOffPolicyAgent(GraphRunner):
         self.debug_draws = None          # tests set these to lists to record every replay draw /
         self.debug_losses = None         # every update's loss (forces a sync per update)
         if self.noise_source == "device":
-            # key of the agent's noise generator: (noise seed, rank); the acting draws count their own events
-            self._noise_seed = int(self.ap.seed) & 0xFFFFFFFF if self.ap.seed is not None else \
-                int.from_bytes(os.urandom(4), "little")
-            self._noise_rank = int(self.dist.rank) if self.dist is not None else 0
-            self._act_event = 0
+            self._key_noise_generator()
+            self._act_event = 0             # the acting draws count their own events
+
+    def _key_noise_generator(self):
+        """key of the agent's device noise generator: (noise seed, rank)"""
+        self._noise_seed = int(self.ap.seed) & 0xFFFFFFFF if self.ap.seed is not None else \
+            int.from_bytes(os.urandom(4), "little")
+        self._noise_rank = int(self.dist.rank) if self.dist is not None else 0
+
+    def rekey_networks(self):
+        """hand the generator's key to the networks that sample with it (noisy layers); called again after a checkpoint
+        restored the key.  Nothing to do for an agent without such networks."""
 
     # ------------------------------------------------------------------ helpers for subclasses
     def _finish_init(self):

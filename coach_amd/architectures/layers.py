@@ -14,6 +14,14 @@ class Dense(object):
         return isinstance(other, Dense) and other.units == self.units
 
 
+class NoisyNetDense(Dense):
+    """rl_coach/architectures/layers.py:69-76: the factorised NoisyNet dense layer (sigma0 = 0.5).  As a component's
+    `dense_layer` it is ParameterNoise's mark: the device network then builds nn.graph.NoisyDense layers."""
+    def __init__(self, units, sigma0=0.5):
+        super().__init__(units)
+        self.sigma0 = sigma0
+
+
 class Conv2d(object):
     def __init__(self, num_filters, kernel_size, strides):
         self.num_filters, self.kernel_size, self.strides = int(num_filters), int(kernel_size), int(strides)

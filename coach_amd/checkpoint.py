@@ -39,6 +39,9 @@ def agent_state(agent):
         st["networks"][name] = {
             "weights": net.params.weights.cpu(), "target": None if net.target is None else net.target.cpu(),
             "adam_m": net.adam.m.cpu(), "adam_v": net.adam.v.cpu(), "adam_state": net.adam.state.cpu()}
+        if getattr(net, "noise_counters", None) is not None:
+            # ParameterNoise: the noisy layers' pass counters (device int64) — a restored agent continues the sequence
+            st["networks"][name]["noise_counters"] = net.noise_counters.cpu()
     mem = agent.memory
     st["memory"]["tensors"] = _tensors_of(mem, _MEMORY_TENSORS)
     import copy
@@ -72,6 +75,10 @@ def load_agent_state(agent, st):
         if net.target is not None:
             net.target.copy_(s["target"])
         net.adam.m.copy_(s["adam_m"]); net.adam.v.copy_(s["adam_v"]); net.adam.state.copy_(s["adam_state"])
+        if getattr(net, "noise_counters", None) is not None:
+            if "noise_counters" not in s:
+                raise ValueError("checkpoint of a network without noisy layers restored into one with them")
+            net.noise_counters.copy_(s["noise_counters"])
     mem = agent.memory
     for k, t in st["memory"]["tensors"].items():
         if k in ("act_value", "act_probs") and not hasattr(mem, k):
@@ -84,6 +91,8 @@ def load_agent_state(agent, st):
         mem.beta = pickle.loads(st["memory"]["beta"])
     for k, v in st["agent"]["scalars"].items():
         setattr(agent, k, copy.deepcopy(v))
+    if hasattr(agent, "rekey_networks"):
+        agent.rekey_networks()               # the restored noise key reaches the networks that sample with it
     if hasattr(mem, "act_value") and "act_value" not in st["memory"]["tensors"]:
         # a checkpoint written without the recorded V(s) / probability columns (an agent that did not record, an older
         # writer): the rows of the restored rollout carry none — its training phase runs the dataset passes

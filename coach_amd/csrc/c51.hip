@@ -205,6 +205,29 @@ __global__ void __launch_bounds__(64) categorical_egreedy_kernel(const float *__
         actions[e] = rlx::egreedy_choice_f64(q, A, explore_u[e], random_act[e], tie_rand + (size_t)e * A, epsilon);
 }
 
+// ParameterNoise acting (exploration_policies/parameter_noise.py:62-68): np.argmax of the same fp64 expectations — the
+// first maximum, no draws.
+__global__ void __launch_bounds__(64) categorical_argmax_kernel(const float *__restrict__ logits, long long ld,
+                                                                const double *__restrict__ z, int n_atoms, int n_actions,
+                                                                double *__restrict__ q_out, int *__restrict__ actions) {
+    __shared__ float p_s[kC51MaxActions * kC51MaxAtoms];
+    __shared__ double z_s[kC51MaxAtoms];
+    __shared__ float mx_s[kC51MaxActions], sum_s[kC51MaxActions];
+    __shared__ double q[kC51MaxActions];
+    const int e = blockIdx.x, t = threadIdx.x, N = n_atoms, A = n_actions;
+    const float *x = logits + (size_t)e * ld;
+    for (int c = t; c < A * N; c += 64) p_s[c] = x[c];
+    for (int j = t; j < N; j += 64) z_s[j] = z[j];
+    __syncthreads();
+    softmax_rows<64>(p_s, mx_s, sum_s, A, N, t);
+    if (t < A) {
+        q[t] = expectation(p_s + t * N, z_s, N);
+        if (q_out) q_out[(size_t)e * A + t] = q[t];
+    }
+    __syncthreads();
+    if (t == 0) actions[e] = rlx::first_argmax_f64(q, A);
+}
+
 }  // namespace
 
 extern "C" {
@@ -244,6 +267,18 @@ int rlx_categorical_egreedy(const float *logits, long long ld, const double *z, 
                 "rlx_categorical_egreedy: bad shape (2 <= atoms <= 256, actions <= 18, ld >= A*N)");
     RLX_LAUNCH((categorical_egreedy_kernel), n_env, 64, 0, rlx::as_stream(stream), logits, ld, z, n_atoms,
                explore_uniforms, random_actions, tie_break_uniforms, epsilon, n_actions, q_out, actions);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_categorical_argmax(const float *logits, long long ld, const double *z, int n_atoms, int n_env, int n_actions,
+                           double *q_out, int *actions, void *stream) {
+    RLX_REQUIRE(logits && z && actions, "rlx_categorical_argmax: null pointer");
+    RLX_REQUIRE(n_env > 0 && n_atoms >= 2 && n_atoms <= kC51MaxAtoms && n_actions > 0 && n_actions <= kC51MaxActions &&
+                    ld >= (long long)n_atoms * n_actions,
+                "rlx_categorical_argmax: bad shape (2 <= atoms <= 256, actions <= 18, ld >= A*N)");
+    RLX_LAUNCH((categorical_argmax_kernel), n_env, 64, 0, rlx::as_stream(stream), logits, ld, z, n_atoms, n_actions,
+               q_out, actions);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

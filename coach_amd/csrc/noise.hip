@@ -21,7 +21,8 @@
 namespace {
 
 constexpr uint32_t kNoiseTag = 0x4E4F4953u;          // "NOIS"
-constexpr int kNoiseStreams = 5;                     // 0 TD3 smoothing, 1-3 SAC draws 0-2, 4 acting
+constexpr int kNoiseStreams = 5;                     // of rlx_normal_fill: 0 TD3 smoothing, 1-3 SAC draws 0-2, 4 acting;
+                                                     // 5 and up: the NoisyNet layers (noisy_sample_kernel)
 
 constexpr double kTwoM53 = 1.1102230246251565e-16;   // 2^-53
 constexpr double kTwoM51 = 4.440892098500626e-16;    // 2^-51
@@ -125,9 +126,76 @@ __global__ void normal_fill_kernel(double *__restrict__ out, const long long *__
     }
 }
 
+// The factorised NoisyNet layers' noise (csrc/noisy_dense.hip): f(e) = sign(e) sqrt(|e|) of standard normals e, in fp64
+// (sqrt is correctly rounded), then rounded once to fp32.  One workgroup per layer; layer L's vectors of pass P are
+// streams kNoiseStreams + 3 (RLX_NOISY_PASSES L + P) + {0: f_in, 1: f_out, 2: f_b} at the event index held in
+// counters[RLX_NOISY_PASSES L + P], which the workgroup reads from device memory and then advances by one: a
+// replayed graph draws fresh values.
+constexpr int kMaxNoisyLayers = RLX_NOISY_MAX_LAYERS;
+struct NoisySample {
+    rlx_noisy_layer l[kMaxNoisyLayers];
+};
+
+__device__ __forceinline__ double signed_sqrt(double v) {
+    const double s = __builtin_sqrt(__builtin_fabs(v));
+    return v < 0.0 ? -s : s;
+}
+
+__global__ void __launch_bounds__(256) noisy_sample_kernel(const NoisySample s, long long *__restrict__ counters,
+                                                           int pass, uint32_t seed, uint32_t rank) {
+    const rlx_noisy_layer &L = s.l[blockIdx.x];
+    long long *cnt = counters + (size_t)L.layer * RLX_NOISY_PASSES + pass;
+    const unsigned long long ev = (unsigned long long)*cnt;
+    const uint32_t stream0 = (uint32_t)kNoiseStreams + 3u * (uint32_t)(RLX_NOISY_PASSES * L.layer + pass);
+    const unsigned pin = ((unsigned)L.K + 1u) >> 1, pn = ((unsigned)L.N + 1u) >> 1;
+    for (unsigned i = threadIdx.x; i < pin + 2u * pn; i += blockDim.x) {
+        const unsigned which = i < pin ? 0u : (i < pin + pn ? 1u : 2u);
+        const unsigned p = which == 0u ? i : (which == 1u ? i - pin : i - pin - pn);
+        const unsigned n = which == 0u ? (unsigned)L.K : (unsigned)L.N;
+        const size_t base = which == 0u ? 0 : (which == 1u ? (size_t)L.K : (size_t)L.K + (size_t)L.N);
+        const rlx::U4 w = rlx::philox4x32_10(p, stream0 + which, (uint32_t)ev, (uint32_t)(ev >> 32) ^ kNoiseTag, seed,
+                                             rank);
+        double z0, z1;
+        box_muller(w, z0, z1);
+        const double f0 = signed_sqrt(z0), f1 = signed_sqrt(z1);
+        const size_t o = base + 2 * (size_t)p;
+        L.f[o] = (float)f0;
+        if (L.f64) L.f64[o] = f0;
+        if (2 * p + 1 < n) {
+            L.f[o + 1] = (float)f1;
+            if (L.f64) L.f64[o + 1] = f1;
+        }
+    }
+    __syncthreads();                      // every thread has read the counter
+    if (threadIdx.x == 0) *cnt = (long long)(ev + 1ull);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rlx_noisy_sample(const rlx_noisy_layer *layers_host, int n_layers, long long *counters, int pass,
+                     unsigned int seed, unsigned int rank, void *stream) {
+    RLX_REQUIRE(layers_host && counters, "rlx_noisy_sample: null pointer");
+    RLX_REQUIRE(n_layers >= 1 && n_layers <= kMaxNoisyLayers, "rlx_noisy_sample: need 1..%d layers (got %d)",
+                kMaxNoisyLayers, n_layers);
+    RLX_REQUIRE(pass >= 0 && pass < RLX_NOISY_PASSES, "rlx_noisy_sample: bad pass %d (0..%d)", pass,
+                RLX_NOISY_PASSES - 1);
+    NoisySample s;
+    for (int i = 0; i < n_layers; ++i) {
+        const rlx_noisy_layer &l = layers_host[i];
+        RLX_REQUIRE(l.f, "rlx_noisy_sample: null pointer in layer %d", i);
+        RLX_REQUIRE(l.K > 0 && l.N > 0 && l.layer >= 0 && l.layer < (1 << 20),
+                    "rlx_noisy_sample: bad shape in layer %d (K=%d N=%d index=%d)", i, l.K, l.N, l.layer);
+        for (int j = 0; j < i; ++j)
+            RLX_REQUIRE(layers_host[j].layer != l.layer, "rlx_noisy_sample: layer index %d given twice", l.layer);
+        s.l[i] = l;
+    }
+    RLX_LAUNCH((noisy_sample_kernel), n_layers, 256, 0, rlx::as_stream(stream), s, counters, pass, (uint32_t)seed,
+               (uint32_t)rank);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
 
 int rlx_normal_fill(double *out, const long long *events, int n_events, int stream0, int n_streams, int n,
                     unsigned int seed, unsigned int rank, double scale, void *stream) {

@@ -155,6 +155,22 @@ __global__ void __launch_bounds__(64) quantile_egreedy_kernel(const float *__res
                                          epsilon);
 }
 
+// ParameterNoise acting (exploration_policies/parameter_noise.py:62-68): np.argmax of the same fp64 means — the first
+// maximum, no draws.
+__global__ void __launch_bounds__(64) quantile_argmax_kernel(const float *__restrict__ quant, long long ld, int n_atoms,
+                                                             int n_actions, double *__restrict__ q_out,
+                                                             int *__restrict__ actions) {
+    __shared__ double q[64];
+    const int e = blockIdx.x, t = threadIdx.x;
+    const double w = 1.0 / (double)n_atoms;
+    if (t < n_actions) {
+        q[t] = atom_mean(quant + (size_t)e * ld + (size_t)t * n_atoms, n_atoms, w);
+        if (q_out) q_out[(size_t)e * n_actions + t] = q[t];
+    }
+    __syncthreads();
+    if (t == 0) actions[e] = rlx::first_argmax_f64(q, n_actions);
+}
+
 }  // namespace
 
 extern "C" {
@@ -191,6 +207,17 @@ int rlx_quantile_egreedy(const float *quantiles, long long ld, int n_atoms, cons
                 "rlx_quantile_egreedy: bad shape");
     RLX_LAUNCH((quantile_egreedy_kernel), n_env, 64, 0, rlx::as_stream(stream), quantiles, ld, n_atoms,
                explore_uniforms, random_actions, tie_break_uniforms, epsilon, n_env, n_actions, q_out, actions);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_quantile_argmax(const float *quantiles, long long ld, int n_atoms, int n_env, int n_actions, double *q_out,
+                        int *actions, void *stream) {
+    RLX_REQUIRE(quantiles && actions, "rlx_quantile_argmax: null pointer");
+    RLX_REQUIRE(n_env > 0 && n_atoms > 0 && n_actions > 0 && n_actions <= 64 && ld >= (long long)n_atoms * n_actions,
+                "rlx_quantile_argmax: bad shape");
+    RLX_LAUNCH((quantile_argmax_kernel), n_env, 64, 0, rlx::as_stream(stream), quantiles, ld, n_atoms, n_actions, q_out,
+               actions);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -544,6 +544,72 @@ class Dense(Layer):
             ctx.commit_deferred(job)
 
 
+class NoisyDense(Layer):
+    """Factorised NoisyNet dense layer (NoisyNetDense, tensorflow_components/layers.py:196-257; Fortunato et al. 2017):
+    y = act(x (Wm + Ws * (f_in outer f_out)) + bm + bs * f_b), f = sign(e) sqrt(|e|) of standard normals drawn anew for
+    every forward pass.  csrc/noisy_dense.hip: the noisy matrix is never formed (two MFMA accumulators per tile), the
+    backward pass uses the factorisation instead of more products.
+
+    The four tensors live in the network's flat parameter buffer under the reference's variable names, so the target
+    copy, Adam, the gradient norm / clipping, the all-reduce and the checkpoints cover them like any weight.  The noise
+    of a pass is one vector [f_in | f_out | f_b] per (layer, tag) in the context, filled by the network's
+    sample_noise(tag, pass) in front of the pass (rlx_noisy_sample: all noisy layers of the network in one launch);
+    backward() uses the vector of the pass that produced y.  One tower only."""
+    SIGMA0 = 0.5                 # architectures/layers.py:75
+
+    def __init__(self, params, name, in_features, units, activation=None, towers=1, init=None):
+        if towers != 1 or init is not None:
+            raise NotImplementedError("NoisyDense: one tower, the layer's own initialiser")
+        self.name, self.K, self.N, self.act, self.T, self.params = name, in_features, units, activation, 1, params
+        self.wmname, self.bmname = name + "/weight_mean", name + "/bias_mean"
+        self.wsname, self.bsname = name + "/weight_stddev", name + "/bias_stddev"
+        self.kname, self.bname = self.wmname, self.bmname        # (the layer's first tensors: gradient split offsets)
+        self.index = None                                        # position among the network's noisy layers
+        params.add_group([(self.wmname, (in_features, units)), (self.bmname, (units,)),
+                          (self.wsname, (in_features, units)), (self.bsname, (units,))], 1)
+
+    def initialize(self, rng):
+        """layers.py:233-242, default branch: weight_mean ~ U(+-1/sqrt K), the stddevs ~ U(+-sigma0/sqrt K), bias_mean 0."""
+        lim = 1.0 / math.sqrt(self.K)
+        put = lambda name, a: self.params.w(name).copy_(torch.from_numpy(np.ascontiguousarray(a.astype(np.float32))))
+        put(self.wmname, rng.uniform(-lim, lim, size=(self.K, self.N)))
+        put(self.wsname, rng.uniform(-self.SIGMA0 * lim, self.SIGMA0 * lim, size=(self.K, self.N)))
+        put(self.bsname, rng.uniform(-self.SIGMA0 * lim, self.SIGMA0 * lim, size=(self.N,)))
+
+    def noise(self, ctx, tag):
+        return ctx.buffer(self.name + "/noise", (self.K + 2 * self.N,), tag=tag)
+
+    def forward(self, ctx, x, tag="", weights=None, t0=0, nt=None, pair=False, launch=True, row_heads=None):
+        if pair or row_heads or not launch:
+            raise NotImplementedError("NoisyDense runs as a launch of its own (no paired / row-head / deferred form)")
+        self._range(t0, nt)
+        assert x.towers in (0, 1) and x.cols == self.K and not x.u8, (self.name, x.towers, x.cols, self.K)
+        p, M = self.params, x.rows
+        y = ctx.buffer(self.name, (1, M, self.N), tag=tag)
+        ctx.lib.noisy_dense_forward(x.data, self.K, p.w(self.wmname, 0, weights), p.w(self.wsname, 0, weights),
+                                    p.w(self.bmname, 0, weights), p.w(self.bsname, 0, weights), self.noise(ctx, tag),
+                                    y, self.N, M, self.K, self.N, _rlx.ACT[self.act], ctx.ws.splitk,
+                                    ctx.ws.splitk.numel(), ctx.stream)
+        return Tensor(y, M, self.N, 1, grad_key=(ctx, self.name, tag), act=self.act)
+
+    def backward(self, ctx, x, y, need_dx=True, weights=None, t0=0, nt=None, need_dw=True, overlap=False):
+        """y.grad holds dL/dy; writes the four parameter gradients and (optionally) x.grad, which carries the lower
+        layer's activation derivative (it IS that layer's dz), as Dense.backward does."""
+        p, M = self.params, x.rows
+        dz = y.grad
+        if self.act is not None and not y.grad_is_dz:
+            ctx.lib.act_backward(dz, y.data, M * self.N, _rlx.ACT[self.act], ctx.stream)
+        lower = x.act if need_dx else None
+        g = (lambda n: p.g(n)) if need_dw else (lambda n: None)
+        ctx.lib.noisy_dense_backward(x.data, self.K, p.w(self.wmname, 0, weights), p.w(self.wsname, 0, weights), dz,
+                                     self.N, self.noise(ctx, y.grad_key[2]), g(self.wmname), g(self.wsname),
+                                     g(self.bmname), g(self.bsname), x.ensure_grad() if need_dx else None, self.K, M,
+                                     self.K, self.N, _rlx.ACT[lower], ctx.ws.splitk, ctx.ws.splitk.numel(),
+                                     ctx.stream)
+        if need_dx:
+            x.grad_is_dz = lower is not None
+
+
 class BatchNorm(Layer):
     """tf.layers.batch_normalization(x, training=is_training) + the activation, after a Dense layer built without one
     (BatchnormActivationDropout, tensorflow_components/layers.py:26-55, 138-152): momentum 0.99, epsilon 1e-3, gamma / beta

@@ -18,10 +18,12 @@ VECTOR_EMBEDDER = {"Medium": [256], "Shallow": [128], "Empty": []}
 FC_MIDDLEWARE = {"Medium": [512], "Shallow": [64], "Empty": []}
 
 
-def build_torso(params, prefix, obs_shape, activation, towers, embedder="Medium", middleware="Medium"):
+def build_torso(params, prefix, obs_shape, activation, towers, embedder="Medium", middleware="Medium", noisy=False):
     """input embedder + FC middleware.  obs_shape (H, W, C) -> image embedder on uint8 frames
-    (input / 255, embedder_parameters.py:33-36), (D,) -> vector embedder."""
+    (input / 255, embedder_parameters.py:33-36), (D,) -> vector embedder.
+    noisy: every dense layer is a factorised NoisyNet layer (G.NoisyDense; the convolutions stay)."""
     layers = []
+    Dense = G.NoisyDense if noisy else G.Dense
     if len(obs_shape) == 3:
         hwc = tuple(obs_shape)
         convs = IMAGE_EMBEDDER[embedder] if isinstance(embedder, str) else embedder
@@ -34,11 +36,11 @@ def build_torso(params, prefix, obs_shape, activation, towers, embedder="Medium"
         feat = int(obs_shape[0])
         dense = VECTOR_EMBEDDER[embedder] if isinstance(embedder, str) else embedder
         for i, u in enumerate(dense):
-            layers.append(G.Dense(params, "%s/embedder/dense%d" % (prefix, i), feat, u, activation, towers))
+            layers.append(Dense(params, "%s/embedder/dense%d" % (prefix, i), feat, u, activation, towers))
             feat = u
     mids = FC_MIDDLEWARE[middleware] if isinstance(middleware, str) else middleware
     for i, u in enumerate(mids):
-        layers.append(G.Dense(params, "%s/middleware/dense%d" % (prefix, i), feat, u, activation, towers))
+        layers.append(Dense(params, "%s/middleware/dense%d" % (prefix, i), feat, u, activation, towers))
         feat = u
     return G.Sequential(layers), feat
 
@@ -392,15 +394,27 @@ class DQNNet(_NetBase):
     def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium",
                  middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99,
                  optimizer_epsilon=1e-4, replace_mse_with_huber_loss=True, seed=0, dueling=False,
-                 head_activation="relu", head_gradient_rescale=1.0, clip_gradients=None):
+                 head_activation="relu", head_gradient_rescale=1.0, clip_gradients=None, noisy=False):
+        """noisy: ParameterNoise's network — every dense layer (embedder, middleware, head) is a G.NoisyDense."""
         self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, n_actions
         self.huber = replace_mse_with_huber_loss
         self.dueling = dueling
+        self.noisy = bool(noisy)
         self.head_gradient_rescale = float(head_gradient_rescale)
         self.clip_gradients = clip_gradients
         self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
-        if dueling:
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware,
+                                       noisy=self.noisy)
+        if dueling and self.noisy:
+            # the same head from noisy layers: the two fc1 streams are layers of their own (a NoisyDense has one tower:
+            # each stream draws its own noise), so the towers-of-one-launch and multi-problem shortcuts are declined
+            hn = "main/dueling_q_values_head"
+            self.v_fc = G.NoisyDense(self.params, hn + "/state_value/fc1", feat, 512, head_activation)
+            self.a_fc = G.NoisyDense(self.params, hn + "/action_advantage/fc1", feat, 512, head_activation)
+            self.v_out = G.NoisyDense(self.params, hn + "/state_value/fc2", 512, 1, None)
+            self.a_out = G.NoisyDense(self.params, hn + "/action_advantage/fc2", 512, n_actions, None)
+            self.modules = [self.torso, self.v_fc, self.a_fc, self.v_out, self.a_out]
+        elif dueling:
             # DuelingQHead (heads/dueling_q_head.py:33-48): state-value and action-advantage streams,
             # each Dense(512, act) -> Dense(1 | A); the two fc1 layers are towers of one launch
             hn = "main/dueling_q_values_head"
@@ -409,12 +423,45 @@ class DQNNet(_NetBase):
             self.a_out = G.Dense(self.params, hn + "/action_advantage/fc2", 512, n_actions, None, 1)
             self.modules = [self.torso, self.stream_fc, self.v_out, self.a_out]
         else:
-            self.q_head = G.Dense(self.params, "main/q_head/dense", feat, n_actions, None, 1)
+            self.q_head = (G.NoisyDense if self.noisy else G.Dense)(self.params, "main/q_head/dense", feat, n_actions,
+                                                                    None, 1)
             self.modules = [self.torso, self.q_head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
         self.loss = torch.zeros(1, dtype=torch.float32, device=device)
+        self._noisy_setup()
         self._fused = self._fused_mlp_setup()
         self._act = self._act_setup()
+
+    # ---------------------------------------------------------------- noisy layers (ParameterNoise)
+    def _noisy_setup(self):
+        """the network's noisy layers in forward order, their device counters [layer][pass] (int64, advanced by
+        rlx_noisy_sample itself — part of a checkpoint) and the generator's key (the agent sets seed and rank)."""
+        self.noisy_layers = [l for m in self.modules for l in (m.layers if isinstance(m, G.Sequential) else [m])
+                             if isinstance(l, G.NoisyDense)]
+        for i, l in enumerate(self.noisy_layers):
+            l.index = i
+        if len(self.noisy_layers) > _rlx.NOISY_MAX_LAYERS:      # (one sampling launch serves them all)
+            raise ValueError("a noisy network may have at most %d dense layers (this one has %d)"
+                             % (_rlx.NOISY_MAX_LAYERS, len(self.noisy_layers)))
+        self.noise_seed, self.noise_rank = 0, 0
+        self.noise_counters = torch.zeros(max(1, len(self.noisy_layers)) * _rlx.NOISY_PASSES, dtype=torch.int64,
+                                          device=self.device) if self.noisy else None
+
+    def sample_noise(self, tag, noise_pass):
+        """fresh noise for the forward pass `tag` of every noisy layer: one launch; noise_pass (_rlx.NOISY_PASS) names
+        the pass's own streams and counters.  No-op for a plain network."""
+        if not self.noisy:
+            return
+        key = ("noisy_layers", tag)
+        arr = self.ctx.cache.get(key)
+        if arr is None:
+            arr = (_rlx.NoisyLayer * len(self.noisy_layers))()
+            for q, l in zip(arr, self.noisy_layers):
+                q.f, q.f64, q.K, q.N, q.layer = l.noise(self.ctx, tag).data_ptr(), None, l.K, l.N, l.index
+            self.ctx.cache[key] = arr
+        import ctypes
+        self.lib.noisy_sample(ctypes.byref(arr), len(arr), self.noise_counters, _rlx.NOISY_PASS[noise_pass],
+                              self.noise_seed, self.noise_rank, self.ctx.stream)
 
     # ---------------------------------------------------------------- fused small-MLP update (one launch)
     def _fused_mlp_setup(self):
@@ -492,6 +539,15 @@ class DQNNet(_NetBase):
     def _dueling_forward(self, feat, B, tag, weights=None, train=False):
         """-> (q Tensor [1, B, A], saved) ; saved = tensors the backward pass needs."""
         ctx = self.ctx
+        if self.noisy:
+            hv = self.v_fc.forward(ctx, feat, tag=tag, weights=weights)
+            ha = self.a_fc.forward(ctx, feat, tag=tag, weights=weights)
+            v = self.v_out.forward(ctx, hv, tag=tag, weights=weights)
+            adv = self.a_out.forward(ctx, ha, tag=tag, weights=weights)
+            qbuf = ctx.buffer("main/dueling_q_values_head/output", (1, B, self.A), tag=tag)
+            self.lib.dueling_combine(v.data, adv.data, B, self.A, qbuf, ctx.stream)
+            q = G.Tensor(qbuf, B, self.A, 1, grad_key=(ctx, "main/dueling_q_values_head/output", tag))
+            return q, (None, None, hv, ha, v, adv)
         shared = G.Tensor(feat.data, feat.rows, feat.cols, 0, act=feat.act)      # one input, two streams
         h = self.stream_fc.forward(ctx, shared, tag=tag, weights=weights)
         hv, ha = (h.tower(0), h.tower(1)) if train else (h.tower_view(0), h.tower_view(1))
@@ -510,6 +566,17 @@ class DQNNet(_NetBase):
         ctx = self.ctx
         shared, h, hv, ha, v, adv = saved
         self.lib.dueling_combine_backward(q.grad, B, self.A, v.ensure_grad(), adv.ensure_grad(), ctx.stream)
+        if self.noisy:
+            self.v_out.backward(ctx, hv, v)
+            self.a_out.backward(ctx, ha, adv)
+            # the two streams' input gradients (each already times act'(feat)) add up in feat.grad
+            side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
+            side.grad = ctx.buffer("main/dueling_q_values_head/side:grad", tuple(feat.data.shape))
+            self.v_fc.backward(ctx, feat, hv)
+            self.a_fc.backward(ctx, side, ha)
+            g = feat.grad
+            self.lib.axpby(g, 1.0, g, 1.0, side.grad, g.numel(), ctx.stream)
+            return
         if self.A <= G.SMALL_N and B * self.A <= 1024:
             G.small_dense_backward_multi(ctx, [(self.v_out, hv, v), (self.a_out, ha, adv)])
         else:
@@ -520,8 +587,10 @@ class DQNNet(_NetBase):
         self.stream_fc.backward(ctx, shared, h)
         feat.grad_is_dz = shared.grad_is_dz
 
-    def q_values(self, obs, B, use_target=False, tag="q"):
+    def q_values(self, obs, B, use_target=False, tag="q", noise_pass="act"):
+        """noise_pass: which pass's noise a noisy network samples for this forward pass (every pass samples its own)."""
         w = self.target if use_target else None
+        self.sample_noise(tag, noise_pass)
         acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
         if self.dueling:
             return self._dueling_forward(acts[-1], B, tag, w)[0]
@@ -543,6 +612,7 @@ class DQNNet(_NetBase):
         against explicit [B, A] targets, backward; leaves the gradients in params.grads (clipped when
         clip_gradients is set), the loss in self.loss and tf.global_norm of the raw gradients in self.norm."""
         ctx = self.ctx
+        self.sample_noise("train", "online")
         acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
         saved = None
         if self.dueling:
@@ -560,7 +630,7 @@ class DQNNet(_NetBase):
         """the target network on s' and the online network on s -> (acts, q, saved, q_next): the online pass as the
         backward pass needs it (saved: the dueling head's tensors, else None) and the target's head output [B, width]."""
         ctx, saved = self.ctx, None
-        if states_pair is not None and not self.dueling:
+        if states_pair is not None and not self.dueling and not self.noisy:
             # parallel_prediction (dqn_agent.py:86-89): online(s) and target(s') as two towers of the
             # same launches — the replay collates states / next_states into one [2, B, ...] buffer
             cols = int(np.prod(self.obs_shape))
@@ -577,7 +647,10 @@ class DQNNet(_NetBase):
             acts = [x.tower_view(0)] + [a.tower(0) for a in acts2[1:]]
             q = q2.tower(0)
         else:
-            q_next = self.q_values(next_obs, B, use_target=True, tag="next_t").data.view(B, -1)
+            # (a noisy network takes this branch: the paired launches have no noisy form, and every pass samples its own
+            # noise — target on s', online on s)
+            q_next = self.q_values(next_obs, B, use_target=True, tag="next_t", noise_pass="target").data.view(B, -1)
+            self.sample_noise("train", "online")
             acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
             if self.dueling:
                 q, saved = self._dueling_forward(acts[-1], B, "train", train=True)
@@ -603,7 +676,8 @@ class DQNNet(_NetBase):
                 w = w.double()
             return self._fused_learn(obs, next_obs, B, actions, rewards, game_overs, discount, w, td_errors,
                                      double_dqn, grad_scale)
-        sel = self.q_values(next_obs, B, tag="next_o").data.view(B, self.A) if double_dqn else None
+        sel = self.q_values(next_obs, B, tag="next_o", noise_pass="online_next").data.view(B, self.A) \
+            if double_dqn else None
         acts, q, saved, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
         dq = q.ensure_grad()
         # TD targets, |TD errors|, QHead loss and its gradient in one launch (importance weights are
@@ -614,7 +688,7 @@ class DQNNet(_NetBase):
         feat = acts[-1]
         if self.HEAD_LOSS_BACKWARD_ONE_LAUNCH and not self.dueling and self.head_gradient_rescale == 1.0 and \
                 self.q_head.T == 1 and self.A <= G.SMALL_N and B * self.A <= 1024 and B <= 256 and not feat.u8 and \
-                feat.towers == 1:
+                feat.towers == 1 and not self.noisy:
             # TD targets, |TD errors|, loss, dQ AND the Q head's backward pass (dW, db, dz of the last dense layer) in one
             # launch (rlx_dqn_head_loss_backward): what the two calls of the else branch compute, bit for bit
             import ctypes
@@ -652,9 +726,9 @@ class DistributionalDQNNet(DQNNet):
         self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)      # per-row loss partials
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def head_output(self, obs, B, use_target=False, tag="q"):
+    def head_output(self, obs, B, use_target=False, tag="q", noise_pass="act"):
         """the head's Dense output [B, A * atoms] (a Tensor; .data is the buffer)."""
-        return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag)
+        return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag, noise_pass=noise_pass)
 
     def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount, grad_scale=1.0,
                          sync=None, states_pair=None, **head_outs):

@@ -928,6 +928,62 @@ int rlx_synth_env_step_lengths(int kind, void *next_obs, void *reset_obs, float 
 int rlx_normal_fill(double *out, const long long *events, int n_events, int stream0, int n_streams, int n,
                     unsigned int seed, unsigned int rank, double scale, void *stream);
 
+/* ------------------------------------------------- factorised NoisyNet dense layers -- */
+/* ParameterNoise (exploration_policies/parameter_noise.py) swaps a network's dense layers for the factorised noisy
+ * layer of architectures/tensorflow_components/layers.py:196-257:
+ *   f(v) = sign(v) sqrt(|v|);  W = weight_mean + weight_stddev * (f(e_in) outer f(e_out));
+ *   b = bias_mean + bias_stddev * f(e_b);  y = act(x W + b), e_* standard normals drawn anew for every forward pass.
+ * A layer's noise of one pass is ONE vector `noise` of K + 2 N floats: [f(e_in) (K) | f(e_out) (N) | f(e_b) (N)].
+ *
+ * rlx_noisy_sample fills it for up to RLX_NOISY_MAX_LAYERS layers in one launch (one workgroup per layer) from rlx_normal_fill's generator
+ * (csrc/noise.hip), f applied in fp64 and the result rounded once to fp32 (f64, optional: the fp64 values).  Stream
+ * assignment of that generator: 0..4 belong to rlx_normal_fill (above); layer L's vectors of pass P are the streams
+ *   5 + 3 * (RLX_NOISY_PASSES * L + P) + {0: e_in, 1: e_out, 2: e_b},
+ * value i of a vector being value i of its stream, at the event index held in counters[RLX_NOISY_PASSES * L + P]
+ * (device int64), under the key (seed, rank).  The launch READS the counter from device memory and then advances it
+ * by one, so every pass — also every replay of a captured graph — draws new values, and a draw is a function of
+ * (seed, rank, layer, pass, counter) alone.  Passes: 0 acting, 1 the online network on s (the pass the loss is taken
+ * on), 2 the target network on s', 3 the online network on s' (Double DQN's selection).
+ * These entry points (and rlx_quantile_argmax / rlx_categorical_argmax below) were ADDED under ABI version 11: no
+ * existing signature or structure changed, which is what rlx_abi_version counts, and the loader refuses a library that
+ * does not export a symbol this header declares. */
+#define RLX_NOISY_PASSES 4
+#define RLX_NOISY_MAX_LAYERS 8
+typedef struct rlx_noisy_layer {
+    float *f;      /* [K + 2 N] */
+    double *f64;   /* [K + 2 N] or NULL */
+    int K, N;
+    int layer;     /* the layer's index in its network (selects streams and counters) */
+} rlx_noisy_layer;
+int rlx_noisy_sample(const rlx_noisy_layer *layers_host, int n_layers, long long *counters, int pass,
+                     unsigned int seed, unsigned int rank, void *stream);
+/* y [M][ldy] = act(x Wm + ((x * f_in) Ws) * f_out + bias_mean + bias_stddev * f_b): two fp32 MFMA accumulators per
+ * output tile, each weight matrix ([K][N] row-major) read once per 32 rows, the noisy matrix never formed (csrc/noisy_dense.hip).
+ * K is split over workgroups by the shape alone; workspace: rlx_noisy_dense_workspace_floats(M, K, N) floats (the larger
+ * of the forward and the input-gradient need).  Sums are bit-identical run to run. */
+int rlx_noisy_dense_workspace_floats(int M, int K, int N, long long *floats_host);
+int rlx_noisy_dense_forward(const float *x, long long ldx, const float *weight_mean, const float *weight_stddev,
+                            const float *bias_mean, const float *bias_stddev, const float *noise, float *y,
+                            long long ldy, int M, int K, int N, int activation, float *workspace,
+                            long long workspace_floats, void *stream);
+/* From dz [M][lddz] = dL/d(pre-activation) and the noise of the forward pass whose output the loss was taken on:
+ * d_weight_mean = x^T dz, d_weight_stddev[k][n] = d_weight_mean[k][n] f_in[k] f_out[n], d_bias_mean = column sums of dz,
+ * d_bias_stddev = d_bias_mean * f_b (one launch; all four or, with d_weight_mean NULL, none), and (dx not NULL)
+ * dx [M][lddx] = (dz Wm^T + ((dz * f_out) Ws^T) * f_in) * act'(x) with the LOWER layer's activation lower_activation
+ * (x is that layer's output). */
+int rlx_noisy_dense_backward(const float *x, long long ldx, const float *weight_mean, const float *weight_stddev,
+                             const float *dz, long long lddz, const float *noise, float *d_weight_mean,
+                             float *d_weight_stddev, float *d_bias_mean, float *d_bias_stddev, float *dx,
+                             long long lddx, int M, int K, int N, int lower_activation, float *workspace,
+                             long long workspace_floats, void *stream);
+/* ParameterNoise acting on the distributional heads (parameter_noise.py:62-68: np.argmax, the FIRST maximum, no draws)
+ * over the fp64 action values of rlx_quantile_egreedy / rlx_categorical_egreedy; q_out [n_env][A] fp64 is optional.
+ * (fp32 Q values: rlx_argmax_rows.) */
+int rlx_quantile_argmax(const float *quantiles, long long ld, int n_atoms, int n_env, int n_actions, double *q_out,
+                        int *actions, void *stream);
+int rlx_categorical_argmax(const float *logits, long long ld, const double *z, int n_atoms, int n_env, int n_actions,
+                           double *q_out, int *actions, void *stream);
+
 /* ------------------------------------------------------------ CartPole-v0 / -v1 -- */
 /* N CartPole environments per GPU: gym 0.12.5's physics (gym/envs/classic_control/cartpole.py `step`, fp64, Euler)
  * behind gym's TimeLimit (max_episode_steps), i.e. what `GymVectorEnvironment(level='CartPole-v0')` steps through
