@@ -330,6 +330,8 @@ class VectorOffPolicyAgent(GraphRunner):
             return EpisodicExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling,
                                             n_step=getattr(mp, "n_step", -1), discount=self.ap.algorithm.discount,
                                             max_episode_length=self.L, **kw)
+        if getattr(self, "MASK_COLUMN", False):
+            kw["mask_column"] = True
         return ExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling, **kw)
 
     def _to_device(self, key, array, dtype):
@@ -421,6 +423,7 @@ class VectorOffPolicyAgent(GraphRunner):
         record = self.phase != RunPhase.TEST
         if record:
             self.memory.commit_pending()
+        self._observe_previous_host(record)
         states = self.memory.current_states()
         if self.phase == RunPhase.HEATUP and not alg.heatup_using_network_decisions:
             actions = self.random_actions()                                    # agent.py:838-840
@@ -440,8 +443,18 @@ class VectorOffPolicyAgent(GraphRunner):
         # the rows of a step become visible together, at once only when EVERY env's episode ended on it.
         self.memory.store(actions, self.filtered_reward, stored, next_obs, reset_obs, record=record,
                           dones=None if stored is game_over else game_over,
-                          defer=not all_ended, episode_end=any_ended, dones_host=dones_host)
+                          defer=not all_ended, episode_end=any_ended, dones_host=dones_host,
+                          **self._store_extra_host(dones_host, record))
         return self._after_step_host(dones_host, ended, any_ended, all_ended, record)
+
+    def _observe_previous_host(self, record):
+        """host draws an agent's observe() makes when the previous step's response is observed (Bootstrapped DQN's
+        masks); nothing for the others."""
+
+    def _store_extra_host(self, dones_host, record):
+        """-> extra keyword arguments of memory.store for this step's rows, after whatever host draws the observe() of a
+        terminal response makes."""
+        return {}
 
     def _episode_ends_host(self):
         """which envs finished on the step just taken: a host fact (the env front end's `dones_host`; lockstep envs

@@ -6,6 +6,9 @@ rl_coach/architectures/head_parameters.py the hot-path presets put into
 
 class HeadParameters(object):
     head_type = None
+    # copies of this head on the same middleware output, each with its own weights (head_parameters.py:22-34); a class
+    # default, so that only a network that sets it (Bootstrapped DQN: 10) carries the field
+    num_output_head_copies = 1
 
     def __init__(self, activation_function='relu', name='head', rescale_gradient_from_head_by_factor=1.0,
                  loss_weight=1.0):

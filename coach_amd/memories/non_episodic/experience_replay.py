@@ -52,7 +52,7 @@ class ExperienceReplay(Memory):
     GATHER_ONE_LAUNCH = True     # image replay: the batch's small columns ride on the frame gather's launch
 
     def __init__(self, max_size, allow_duplicates_in_batch_sampling=True, device=None, n_env=1,
-                 observation_shape=None, stack=None, action_dim=None, min_episode_length=1):
+                 observation_shape=None, stack=None, action_dim=None, min_episode_length=1, mask_column=False):
         """
         :param max_size: (MemoryGranularity.Transitions, n)                    (reference signature)
         :param allow_duplicates_in_batch_sampling: sample with replacement      (reference signature)
@@ -61,6 +61,8 @@ class ExperienceReplay(Memory):
         :param stack: frames per stacked image state (ObservationStackingFilter), None for vectors
         :param action_dim: None = discrete (int32), else continuous fp32[action_dim]
         :param min_episode_length: bounds the frames an env adds per stored step (1 + 1/L)
+        :param mask_column: keep a 32-bit word per transition (Bootstrapped DQN's head mask, bit h = head h; the uint32
+                            bit pattern in an int32 tensor); absent (None) unless asked for
         """
         super().__init__(max_size)
         if max_size[0] != MemoryGranularity.Transitions:                        # :48-49
@@ -108,6 +110,7 @@ class ExperienceReplay(Memory):
             torch.zeros(rows, action_dim, dtype=torch.float32, device=dev)
         self.reward = torch.zeros(rows, dtype=torch.float32, device=dev)
         self.game_over = torch.zeros(rows, dtype=torch.uint8, device=dev)
+        self.mask = torch.zeros(rows, dtype=torch.int32, device=dev) if mask_column else None
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.cursor = 0          # physical row the next vector step is written to
         self.count = 0           # len(self.transitions) of the reference (the VISIBLE transitions)
@@ -129,8 +132,9 @@ class ExperienceReplay(Memory):
         return cap + n_env
 
     def _extra_gather_columns(self):
-        """[(stored column, batch-buffer key)] a subclass wants collated with the Batch (same launch)."""
-        return []
+        """[(stored column, batch-buffer key)] collated with the Batch (same launch): the mask column where the memory
+        keeps one; a subclass adds its own."""
+        return [(self.mask, "mask")] if self.mask is not None else []
 
     # ---------------------------------------------------------------- Memory interface (:56-69)
     def length(self):
@@ -248,7 +252,7 @@ class ExperienceReplay(Memory):
         return self.cur_state
 
     def store(self, actions, rewards, game_overs, next_obs, reset_obs, record=True, dones=None,
-              defer=False, episode_end=False, dones_host=None):
+              defer=False, episode_end=False, dones_host=None, masks=None):
         """n_env transitions (state = current state of every env), then advance the env states.
         Reference: ExperienceReplay.store + _enforce_max_length (:117-150) called n_env times.
         record=False only advances the observation state (evaluation episodes are not stored).
@@ -257,7 +261,8 @@ class ExperienceReplay(Memory):
         defer=True: the rows are written now but become visible at the next commit_pending() (the
         reference observes a non-terminal response at the start of the NEXT step).
         episode_end: host copy of "the episodes ended on this step" (lockstep envs), used only for
-        the frame-ring accounting of image observations."""
+        the frame-ring accounting of image observations.
+        masks: the rows' words of the mask column (device int32[n_env]); required where the memory keeps one."""
         s = _rlx.current_stream()
         if record:
             self.commit_pending()
@@ -271,6 +276,7 @@ class ExperienceReplay(Memory):
             self._account_frames(row0, episode_end)
         if record:
             pairs = [(actions, self.action), (rewards, self.reward), (stored_go, self.game_over)]
+            pairs += self._mask_pair(masks)
             if not self.image:
                 pairs += [(self.cur_state, self.obs), (next_obs, self.next_obs)]
             self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, None, 0, row0,
@@ -292,6 +298,18 @@ class ExperienceReplay(Memory):
             else:
                 self._became_visible(self.n_env)
 
+    def _mask_pair(self, masks):
+        if (masks is None) != (self.mask is None):
+            raise ValueError("a memory with a mask column is stored with masks, one without it without them")
+        return [] if masks is None else [(masks, self.mask)]
+
+    def set_masks(self, rows, masks, n):
+        """the mask words of n rows already written (device int32 physical rows / words): the reference draws a
+        transition's mask when it OBSERVES the response — for a non-terminal one at the start of the next step, after the
+        row was written here (see the module text on visibility)."""
+        self.lib.copy_columns(_rlx.make_columns([(masks, self.mask)]), 1, None, rows, 0, 0, n, self.rows, n, self.status,
+                              _rlx.current_stream())
+
     def reserve_step(self, defer):
         """The HOST half of store(): where the rows of this vector step go (-> row0) and how the sampled window
         moves.  The device half may then run from a captured graph whose destination rows arrive as data."""
@@ -305,12 +323,12 @@ class ExperienceReplay(Memory):
             self._became_visible(self.n_env)
         return row0
 
-    def store_device(self, actions, rewards, game_overs, next_obs, reset_obs, dst_rows):
+    def store_device(self, actions, rewards, game_overs, next_obs, reset_obs, dst_rows, masks=None):
         """The DEVICE half of store() for vector observations with the destination rows as a device int32[n_env]
         (staged with the step's other host draws): pure launches on static buffers."""
         s = _rlx.current_stream()
         pairs = [(actions, self.action), (rewards, self.reward), (game_overs, self.game_over),
-                 (self.cur_state, self.obs), (next_obs, self.next_obs)]
+                 (self.cur_state, self.obs), (next_obs, self.next_obs)] + self._mask_pair(masks)
         self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, dst_rows, 0, 0, self.n_env, self.rows,
                               self.n_env, self.status, s)
         self.lib.select_rows(game_overs, reset_obs, next_obs, self.cur_state, self.n_env, self.obs_dim * 4, s)
@@ -342,6 +360,8 @@ class ExperienceReplay(Memory):
                                    dtype=self.action.dtype, device=dev),
                 reward=torch.empty(size, dtype=torch.float32, device=dev),
                 game_over=torch.empty(size, dtype=torch.uint8, device=dev))
+            if self.mask is not None:
+                b["mask"] = torch.empty(size, dtype=torch.int32, device=dev)
             from ...staging import Stager
             st = Stager((size,), torch.int32, dev)
             b["rows"] = st.dst
@@ -393,9 +413,11 @@ class ExperienceReplay(Memory):
     def collate(self, drawn, size, rows_dev=None):
         """The device half of sample(): gather the Batch of a draw."""
         b = self._gather_rows(drawn, size, rows_dev)
+        info = {"logical_idx": drawn, "states_pair": b["states_pair"]}
+        if self.mask is not None:
+            info["mask"] = b["mask"]
         return DeviceBatch(size, {"observation": b["state"]}, {"observation": b["next_state"]},
-                           b["action"], b["reward"], b["game_over"],
-                           info={"logical_idx": drawn, "states_pair": b["states_pair"]})
+                           b["action"], b["reward"], b["game_over"], info=info)
 
     def sample(self, size):
         """ExperienceReplay.sample (:71-90) -> DeviceBatch (the Batch the agent would build)."""

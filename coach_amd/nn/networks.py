@@ -423,14 +423,17 @@ class DQNNet(_NetBase):
             self.a_out = G.Dense(self.params, hn + "/action_advantage/fc2", 512, n_actions, None, 1)
             self.modules = [self.torso, self.stream_fc, self.v_out, self.a_out]
         else:
-            self.q_head = (G.NoisyDense if self.noisy else G.Dense)(self.params, "main/q_head/dense", feat, n_actions,
-                                                                    None, 1)
+            self.q_head = self._q_head_layer(feat, n_actions)
             self.modules = [self.torso, self.q_head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
         self.loss = torch.zeros(1, dtype=torch.float32, device=device)
         self._noisy_setup()
         self._fused = self._fused_mlp_setup()
         self._act = self._act_setup()
+
+    def _q_head_layer(self, feat, units):
+        """the plain head's output layer (a subclass with its own initialisation builds its own)"""
+        return (G.NoisyDense if self.noisy else G.Dense)(self.params, "main/q_head/dense", feat, units, None, 1)
 
     # ---------------------------------------------------------------- noisy layers (ParameterNoise)
     def _noisy_setup(self):
@@ -785,3 +788,70 @@ class C51Net(DistributionalDQNNet):
         self.lib.c51_head_loss(q, AN, q_next, AN, self.z, actions, rewards, game_overs, discount, self.N, self.A, B, 1.0,
                                dq, AN, per_errors, self.loss_ws, self.ticket, self.loss, self.status, m_out,
                                target_actions_out, action_losses_out, self.ctx.stream)
+
+
+class _HeadCopiesDense(G.Dense):
+    """Dense(feat, copies * units) whose column block h is copy h of a head's Dense(feat, units): every block is
+    initialised as that layer of its own would be — glorot uniform with fan-out `units`, one draw per copy, in copy
+    order (general_network.py builds num_output_head_copies heads, each with its own variables)."""
+
+    def __init__(self, params, name, in_features, units, copies):
+        super().__init__(params, name, in_features, units * copies, None, 1)
+        self.units, self.copies = units, copies
+
+    def initialize(self, rng):
+        w = np.concatenate([G.xavier_uniform(rng, self.K, self.units, (self.K, self.units)) for _ in range(self.copies)],
+                           axis=1)
+        self.params.w(self.kname, 0).copy_(torch.from_numpy(np.ascontiguousarray(w)))
+
+
+class BootstrappedDQNNet(DQNNet):
+    """BootstrappedDQNNetworkParameters (agents/bootstrapped_dqn_agent.py:26-30): the DQN torso under K copies of the
+    QHead (num_output_head_copies), held as ONE Dense(feat, K * A) whose output column h * A + a is action a of head h;
+    rescale_gradient_from_head_by_factor = 1 / K acts on what flows from the heads into the torso (the head's own
+    weights get the full gradient).  Forward and backward go through the generic launches; the K masked losses and
+    their gradient are one launch (rlx_bootstrapped_dqn_head_loss, csrc/bootstrapped_dqn.hip).  The fused small-MLP
+    kernels and the head inside the torso's last launch are DQN's alone."""
+    FUSED_MLP = False
+    FUSED_ACT = False
+    HEAD_FORWARD_WITH_TORSO = False
+    MAX_HEADS = 32
+
+    def __init__(self, device, obs_shape, n_actions, heads, dueling=False, noisy=False, **kw):
+        if dueling or noisy:
+            raise ValueError("Bootstrapped DQN has plain Q heads: the reference has neither a dueling nor a noisy form")
+        heads = int(heads)
+        if not 1 <= heads <= self.MAX_HEADS:
+            raise ValueError("1 <= num_output_head_copies <= %d (a transition's mask is one 32-bit word), got %d"
+                             % (self.MAX_HEADS, heads))
+        self._heads, self._head_actions = heads, int(n_actions)
+        super().__init__(device, obs_shape, n_actions * heads, dueling=False, noisy=False, **kw)
+        self.A, self.K, self.KA = int(n_actions), heads, heads * int(n_actions)
+        self.partials = torch.zeros(self.K * 256, dtype=torch.float32, device=device)    # per (head, row) loss terms
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+        self.head_losses = torch.zeros(self.K, dtype=torch.float32, device=device)
+
+    def _q_head_layer(self, feat, units):
+        return _HeadCopiesDense(self.params, "main/q_head/dense", feat, self._head_actions, self._heads)
+
+    def head_output(self, obs, B, use_target=False, tag="q"):
+        """every head's Q values [B, K * A] (a Tensor; .data is the buffer)."""
+        return DQNNet.q_values(self, obs, B, use_target=use_target, tag=tag)
+
+    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, masks, discount, grad_scale=1.0,
+                         sync=None, states_pair=None, td_targets_out=None, target_actions_out=None):
+        """BootstrappedDQNAgent.learn_from_batch (agents/bootstrapped_dqn_agent.py:57-86), all on device: online on
+        s' (the selector), target on s' and online on s, the K masked head losses, backward, Adam.
+        masks: int32 [B], bit h = the transition trains head h."""
+        sel = self.head_output(next_obs, B, tag="next_o").data.view(B, self.KA)
+        acts, q, _, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
+        dq = q.ensure_grad()
+        self.last_q, self.last_q_next, self.last_q_sel = q.data, q_next, sel     # (views of the pass's buffers)
+        KA = self.KA
+        self.lib.bootstrapped_dqn_head_loss(q.data, KA, q_next, sel, KA, actions, rewards, game_overs, masks,
+                                            float(discount), B, self.K, self.A, int(self.huber), 1.0, dq, KA,
+                                            self.partials, self.ticket, self.loss, self.status, self.head_losses,
+                                            td_targets_out, target_actions_out, self.ctx.stream)
+        self._backward_from_q(acts, q, None, B)
+        self._apply_update(grad_scale, sync)
+        return self.loss

@@ -984,6 +984,38 @@ int rlx_quantile_argmax(const float *quantiles, long long ld, int n_atoms, int n
 int rlx_categorical_argmax(const float *logits, long long ld, const double *z, int n_atoms, int n_env, int n_actions,
                            double *q_out, int *actions, void *stream);
 
+/* -------------------------------------------------------------------- Bootstrapped DQN -- */
+/* BootstrappedDQNAgent.learn_from_batch + the K QHead losses and their sum (agents/bootstrapped_dqn_agent.py:57-86,
+ * heads/q_head.py, head.py:172-181) in ONE launch, one workgroup per batch row.  q_online / q_next_target /
+ * q_next_online: the head layer's outputs on s (online), s' (target) and s' (online) [batch][K*A], column h*A + a =
+ * action a of head h.  masks [batch]: bit h set = the transition trains head h.  Per (row, head) with its bit set: the
+ * arithmetic of rlx_dqn_head_loss for that head alone with a selector and no importance weights (a* = first maximum of
+ * the online s' values, fp64 TD target rounded to fp32 once, MSE or Huber, dq = grad_scale * l' / batch at the taken
+ * action); with every bit set head h's slice of dq and head_losses[h] equal that call's outputs on columns
+ * [h*A, (h+1)*A) bit for bit.  A cleared bit: dq = 0 and a zero loss term, the mean's denominator stays batch.
+ * loss_scalar = the K head losses added in head order; every batch sum is taken in a fixed tree (bit-identical run to
+ * run, no float atomics).  partials: [K*batch] floats of workspace; ticket: one zero-initialised word (left at zero).
+ * status |= 1 for an action outside [0, A) (the row then has a zero gradient).  Optional outputs (null):
+ * head_losses [K]; td_targets [batch][K] (the fp32 target at the taken action; the online prediction where the bit is
+ * cleared); target_actions [batch][K] (a*, whatever the bit).  K <= 32, A <= 18, batch <= 256.
+ * Added under ABI version 11, like the entry points above. */
+int rlx_bootstrapped_dqn_head_loss(const float *q_online, long long ld_q, const float *q_next_target,
+                                   const float *q_next_online, long long ld_next, const int *actions,
+                                   const float *rewards, const unsigned char *game_overs, const uint32_t *masks,
+                                   double discount, int batch, int n_heads, int n_actions, int huber, float grad_scale,
+                                   float *dq, long long ld_dq, float *partials, unsigned int *ticket, float *loss_scalar,
+                                   int *status, float *head_losses, float *td_targets, int *target_actions,
+                                   void *stream);
+/* Bootstrapped.get_action (exploration_policies/bootstrapped.py:72-85) + rlx_egreedy's choice, one wave per env.
+ * q_values [n_env][ld], ld >= K*A.  vote == 0 (TRAIN): the action values are head selected_head[e]'s.  vote != 0: every
+ * head votes for its first maximum, the most voted action wins (the lowest index on a tie) and the action values are
+ * its one-hot vector; selected_head may then be null.  The draws as rlx_egreedy takes them, with its fp32 isclose tie
+ * test.  values_out [n_env][A] (optional): the action values the choice was made on (last_action_values). */
+int rlx_bootstrapped_egreedy(const float *q_values, long long ld, int n_heads, const int *selected_head, int vote,
+                             const double *explore_uniforms, const int *random_actions,
+                             const double *tie_break_uniforms, double epsilon, int n_env, int n_actions,
+                             float *values_out, int *actions, void *stream);
+
 /* ------------------------------------------------------------ CartPole-v0 / -v1 -- */
 /* N CartPole environments per GPU: gym 0.12.5's physics (gym/envs/classic_control/cartpole.py `step`, fp64, Euler)
  * behind gym's TimeLimit (max_episode_steps), i.e. what `GymVectorEnvironment(level='CartPole-v0')` steps through
