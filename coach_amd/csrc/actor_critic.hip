@@ -36,8 +36,9 @@ __global__ void copy_2d_kernel(const float *__restrict__ src, long long src_ld,
     }
 }
 
-__global__ void axpby_kernel(float *__restrict__ out, float a, const float *__restrict__ x, float b,
-                             const float *__restrict__ y, long long n) {
+// out may be x or y themselves (the callers add and scale in place): element i is read before it is written and no
+// other element is touched, so neither out nor the inputs are declared __restrict__.
+__global__ void axpby_kernel(float *out, float a, const float *x, float b, const float *y, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
         out[i] = a * x[i] + (y ? b * y[i] : 0.f);

@@ -388,7 +388,10 @@ __global__ void sumsq_final_kernel(const float *__restrict__ part, int nparts, f
 
 __global__ void clip_by_global_norm_kernel(float *__restrict__ g, long long n, const float *__restrict__ norm,
                                            float clip) {
-    const float scale = clip * fminf(1.0f / *norm, 1.0f / clip);
+    // tf.minimum is (y < x) ? y : x: a NaN norm makes every gradient NaN, as TensorFlow's clip and oracle/agents.py do
+    // (fminf would drop the NaN and pass the buffer through unscaled)
+    const float inv_norm = 1.0f / *norm, inv_clip = 1.0f / clip;
+    const float scale = clip * (inv_clip < inv_norm ? inv_clip : inv_norm);
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) g[i] *= scale;
 }

@@ -789,7 +789,10 @@ int rlx_global_norm(const float *x, long long n, float *norm_out, float *workspa
 
 /* tf.clip_by_global_norm (architectures/tensorflow_components/architecture.py:196-200, clip method
  * ClipByGlobalNorm): grads *= clip_norm * min(1 / global_norm, 1 / clip_norm), in place; global_norm is
- * the device scalar rlx_global_norm wrote. */
+ * the device scalar rlx_global_norm wrote.  min is TF's (y < x) ? y : x.  Pinned (tests/test_glue_kernels.py):
+ * global_norm < clip_norm: the scale is clip_norm * (1 / clip_norm), which is 1 up to two roundings (exactly 1 for 40, 10,
+ * 0.5 and every power of two); global_norm == 0: 1 / 0 = inf loses the min, the scale is the same; global_norm NaN: every
+ * gradient becomes NaN (the reference's behaviour, and oracle/agents.py:205-210's); global_norm inf: the scale is 0. */
 int rlx_clip_by_global_norm(float *grads, long long n, const float *global_norm, float clip_norm,
                             void *stream);
 
@@ -801,7 +804,8 @@ int rlx_copy_2d(const float *src, long long src_ld, float *dst, long long dst_ld
 int rlx_exp_rows(const float *log_std, float *out, int batch, int action_dim,
                  void *stream);                /* policy_std = tile(exp(policy_logstd)), heads/ppo_head.py:139 */
 int rlx_axpby(float *out, float a, const float *x, float b, const float *y, long long n,
-              void *stream);                   /* out = a*x + b*y (y may be NULL); heads/sac_q_head.py:63-67 */
+              void *stream);                   /* out = a*x + b*y (y may be NULL: then out = a*x whatever b is; out may be
+                                                * x or y: in place); heads/sac_q_head.py:63-67 */
 /* out_min = min(q1,q2); grad_i = grad_scale * d sum(min)/d q_i (tf.minimum: ties go to q1).
  * heads/sac_q_head.py:84-88, heads/td3_v_head.py:54-58 */
 int rlx_min_pair(const float *q1, const float *q2, float *out_min, float *grad1, float *grad2,

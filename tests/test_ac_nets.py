@@ -316,18 +316,29 @@ def test_td3_update_matches_oracle(dev, paired, fused, monkeypatch):
 @pytest.mark.parametrize("resample,paired,dims", [(True, False, (23, 5, 64)), (False, False, (23, 5, 64)),
                                                   (True, True, (23, 5, 64)),
                                                   (True, False, (11, 3, 37)),         # ragged last row block
-                                                  (True, True, (376, 17, 256))])      # BASELINE C5: Humanoid SAC
+                                                  (True, True, (376, 17, 256)),       # BASELINE C5: Humanoid SAC
+                                                  (True, False, (23, 5, 64, "clip"))])
 def test_sac_update_matches_oracle(dev, resample, paired, dims, fused, monkeypatch):
     """fused: the six-launch update of csrc/ac_fused.hip (the default wherever the topology allows it); otherwise the
-    layer-by-layer launch chain."""
+    layer-by-layer launch chain.
+    "clip": the bias of policy_mu_logsig is shifted so that one log-std column in five sits above 2 and one in five
+    below -20 (checked on the oracle before the device runs) -- the clip of SACPolicyHead and its zero gradient, which
+    freshly initialised weights never reach; the normal draws are scaled down so that |raw action| stays <= 3 and
+    saturation does not enter the tolerances."""
     from coach_amd.agents.soft_actor_critic_agent import SoftActorCriticAgent, SoftActorCriticAgentParameters
     monkeypatch.setattr(SoftActorCriticAgent, "FUSED_UPDATE", fused)
-    D, A, B = dims
+    D, A, B = dims[:3]
+    clip = len(dims) > 3
     p = SoftActorCriticAgentParameters()
     p.algorithm.resample_noise_per_pass = resample
     ag = _agent(dev, SoftActorCriticAgent, p, D, A, B)
     assert (ag._fused() is not None) == fused
     pol, qn, vn = ag.networks["policy"], ag.networks["q"], ag.networks["v"]
+    if clip:
+        shift = np.zeros(2 * A, dtype=F32)
+        shift[A], shift[A + 1] = 30.0, -50.0
+        bias = pol.params.w("policy/sac_policy_head/policy_mu_logsig/bias")
+        bias.copy_(bias + _t(shift, dev))
     op = O.SACPolicyOracle(pol.params.named_arrays())
     oq = O.SACQOracle(qn.params.named_arrays())
     ov = O.SACValueOracle(vn.params.named_arrays())
@@ -340,6 +351,13 @@ def test_sac_update_matches_oracle(dev, resample, paired, dims, fused, monkeypat
             # observations (what the reference's Humanoid preset feeds, ObservationNormalizationFilter) keep it sane.
             batch = (batch[0] * np.float32(0.05),) + tuple(batch[1:4]) + (batch[4] * np.float32(0.05),)
         z = rng.standard_normal((3, B, A))
+        if clip:
+            z = z * 0.05
+            for k in range(3):
+                o = op.forward(batch[0], z[k])
+                ls_raw = op.cache[1]
+                assert 0.1 <= (ls_raw > 2).mean() <= 0.5 and 0.1 <= (ls_raw < -20).mean() <= 0.5
+                assert np.abs(o["raw_actions"]).max() <= 3
         r = O.sac_update(op, oq, ov, batch, z, resample=resample)
         ag.normals.copy_(_t(z, dev))
         ag._learn_device(_B(dev, batch, paired))
