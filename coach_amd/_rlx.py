@@ -1,7 +1,13 @@
 """ctypes binding of librlx.so — the only way the Python adapters reach the HIP kernels.
 
-The prototypes are read from ``include/rlx.h`` (the single source of truth for the C ABI),
-so a symbol that is declared but not exported — or the other way round — fails at load time.
+``include/rlx.h`` is the single definition of the C ABI, and everything that crosses the boundary is read from it when
+this module is imported: the prototypes (``parse_header``), the descriptor structures (``parse_structs`` -> the
+``ctypes.Structure`` classes named in ``STRUCT_NAMES``), the ``#define`` / enum constants (``parse_constants``) and the
+ABI version.  Nothing here repeats a field list or a number of the header; a new structure, constant or entry point is
+added in rlx.h alone (within the grammar its opening comment states) and a structure gets its class name in
+``STRUCT_NAMES``.  tests/test_abi_layout.py pins the generated layouts to what a C compiler makes of the same header.
+A symbol that is declared but not exported — or the other way round — fails at load time, and so does a library built
+from another RLX_ABI_VERSION.
 There is deliberately NO fallback: if the library cannot be loaded the product path raises
 (``RlxUnavailable``); nothing under ``oracle/`` is ever imported from here.
 """
@@ -30,6 +36,7 @@ _CTYPE = {
     "int": ctypes.c_int,
     "unsigned": ctypes.c_uint,
     "unsigned int": ctypes.c_uint,
+    "unsigned char": ctypes.c_ubyte,
     "float": ctypes.c_float,
     "double": ctypes.c_double,
     "long long": ctypes.c_longlong,
@@ -39,17 +46,28 @@ _CTYPE = {
     "size_t": ctypes.c_size_t,
 }
 
-_VALUE_RETURNING = {"rlx_abi_version", "rlx_ppo_fc_heads_supported", "rlx_ppo_fc_rows_supported", "rlx_td3_fused_supported", "rlx_sac_fused_supported", "rlx_mlp_dqn_supported", "rlx_mlp_q_act_supported", "rlx_conv23_forward_supported",
-                    "rlx_conv123_forward_supported", "rlx_conv32_input_grad_supported", "rlx_conv_dw_u8_supported", "rlx_conv_dw_f32_supported"}  # return a value, not an rlx_status
-
 _DECL = re.compile(r"^\s*(int|const char \*)\s*(rlx_\w+)\s*\(([^;{]*?)\)\s*;", re.M | re.S)
+_STRUCT = re.compile(r"typedef\s+struct\s+(rlx_\w+)\s*\{(.*?)\}\s*\1\s*;", re.S)
+_MEMBER = re.compile(r"^([\w ]+?) ?((?:\*+ ?)?\w+(?: ?, ?(?:\*+ ?)?\w+)*)$")    # <type> <declarator>, <declarator> ...
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(RLX_\w+)[ \t]+(-?\d+)[ \t]*$", re.M)
+_ENUM = re.compile(r"\benum\b[^{;]*\{([^}]*)\}")
+
+
+def returns_value(name):
+    """rlx.h's naming rule: rlx_abi_version and every rlx_*_supported return a value, not an rlx_status."""
+    return name == "rlx_abi_version" or name.endswith("_supported")
+
+
+def header_text(path=HEADER):
+    """rlx.h without its comments."""
+    text = open(path).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return re.sub(r"//[^\n]*", "", text)
 
 
 def parse_header(path=HEADER):
     """Return {name: (restype, [(ctype, param_name), ...])} for every declaration in rlx.h."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
+    text = header_text(path)
     protos = {}
     for ret, name, args in _DECL.findall(text):
         params = []
@@ -68,6 +86,55 @@ def parse_header(path=HEADER):
                     params.append((_CTYPE[key], pname))
         protos[name] = (ctypes.c_char_p if "char" in ret else ctypes.c_int, params)
     return protos
+
+
+def parse_structs(text, names):
+    """{rlx_NAME: ctypes.Structure subclass called names[rlx_NAME]} for every `typedef struct rlx_NAME { ... } rlx_NAME;`
+    of `text` (a header without comments), in declaration order.  Accepts the grammar rlx.h states and nothing else:
+    scalar members of the types in _CTYPE, pointers (all c_void_p), earlier structures by value; anything else — an
+    array, a bit-field, a union, a function pointer, an unknown type — is a ValueError naming structure and statement."""
+    structs = {}
+    found = _STRUCT.findall(text)
+    if len(found) != len(re.findall(r"\btypedef\s+struct\b", text)):
+        raise ValueError("rlx.h: a structure that is not written `typedef struct rlx_NAME { ... } rlx_NAME;` (after %s)"
+                         % ", ".join(n for n, _ in found))
+    for name, body in found:
+        if name not in names:
+            raise ValueError("rlx.h: struct %s has no class name in the table of coach_amd/_rlx.py" % name)
+        fields = []
+        for stmt in body.split(";"):
+            stmt = " ".join(stmt.split())
+            if not stmt:
+                continue
+            m = _MEMBER.match(stmt)
+            if not m:
+                raise ValueError("rlx.h: struct %s: %r is outside the accepted grammar (scalars, pointers and earlier "
+                                 "structures by value; no arrays, bit-fields, unions or function pointers)" % (name, stmt))
+            base = re.sub(r"^const ", "", m.group(1))
+            for decl in m.group(2).split(","):
+                if "*" in decl:         # every pointer is a c_void_p; what it points to must still be a known type
+                    known = base == "void" or base in _CTYPE or base in structs or re.fullmatch(r"struct rlx_\w+", base)
+                    ctype = ctypes.c_void_p if known else None
+                else:
+                    ctype = _CTYPE.get(base) or structs.get(base)
+                if ctype is None:
+                    raise ValueError("rlx.h: struct %s: unknown type %r in %r" % (name, base, stmt))
+                fields.append((decl.strip("* "), ctype))
+        structs[name] = type(names[name], (ctypes.Structure,),
+                             {"_fields_": fields, "__doc__": "%s (include/rlx.h)." % name, "__module__": __name__})
+    return structs
+
+
+def parse_constants(text):
+    """{RLX_NAME: int} of every `#define RLX_NAME <integer>` and every enumerator of `text` (a header without comments)."""
+    consts = {k: int(v) for k, v in _DEFINE.findall(text)}
+    for body in _ENUM.findall(text):
+        for item in filter(None, (" ".join(i.split()) for i in body.split(","))):
+            m = re.fullmatch(r"(RLX_\w+) ?= ?(-?\d+)", item)
+            if not m:
+                raise ValueError("rlx.h: enumerator %r needs an explicit integer value" % item)
+            consts[m.group(1)] = int(m.group(2))
+    return consts
 
 
 def build_library(verbose=False):
@@ -147,7 +214,7 @@ class _Lib:
             def call_str(*args):
                 return fn(*args).decode()
             return call_str
-        if full in _VALUE_RETURNING:
+        if returns_value(full):
             return fn
 
         def call(*args):
@@ -211,10 +278,46 @@ class KernelTimer(object):
         return False
 
 
-# --------------------------------------------------------------------------- ABI structures
-class Column(ctypes.Structure):
-    """rlx_column (include/rlx.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_bytes", ctypes.c_longlong)]
+# ------------------------------------------------- ABI structures and constants, read from rlx.h
+STRUCT_NAMES = {          # rlx.h structure -> its class in this module (bound below, so that the names are static)
+    "rlx_column": "Column", "rlx_gemm_desc": "GemmDesc", "rlx_splitk_job": "SplitkJob", "rlx_noisy_layer": "NoisyLayer",
+    "rlx_per_update_desc": "PerUpdateDesc", "rlx_conv_dw_item": "ConvDwItem",
+    "rlx_small_dense_problem": "SmallDenseProblem", "rlx_mlp_dqn_desc": "MlpDqnDesc", "rlx_mlp3": "Mlp3",
+    "rlx_fused_net": "FusedNet", "rlx_td3_fused_desc": "Td3FusedDesc", "rlx_sac_fused_desc": "SacFusedDesc",
+    "rlx_ppo_fc_heads_desc": "PpoFcHeadsDesc", "rlx_ppo_rows_desc": "PpoRowsDesc", "rlx_observe_desc": "ObserveDesc",
+    "rlx_signal_source": "SignalSource",
+}
+_TEXT = header_text()
+STRUCTS = parse_structs(_TEXT, STRUCT_NAMES)
+CONSTANTS = parse_constants(_TEXT)
+
+Column, GemmDesc, NoisyLayer = STRUCTS["rlx_column"], STRUCTS["rlx_gemm_desc"], STRUCTS["rlx_noisy_layer"]
+PerUpdateDesc, ConvDwItem = STRUCTS["rlx_per_update_desc"], STRUCTS["rlx_conv_dw_item"]
+SmallDenseProblem, MlpDqnDesc = STRUCTS["rlx_small_dense_problem"], STRUCTS["rlx_mlp_dqn_desc"]
+Mlp3, FusedNet = STRUCTS["rlx_mlp3"], STRUCTS["rlx_fused_net"]
+Td3FusedDesc, SacFusedDesc = STRUCTS["rlx_td3_fused_desc"], STRUCTS["rlx_sac_fused_desc"]
+PpoFcHeadsDesc, PpoRowsDesc = STRUCTS["rlx_ppo_fc_heads_desc"], STRUCTS["rlx_ppo_rows_desc"]
+ObserveDesc, SignalSource = STRUCTS["rlx_observe_desc"], STRUCTS["rlx_signal_source"]
+
+
+class SplitkJob(STRUCTS["rlx_splitk_job"]):
+    __doc__ = STRUCTS["rlx_splitk_job"].__doc__
+
+    def workspace_floats(self):
+        """floats of the workspace the outstanding reduction still reads (0 when nothing is outstanding)."""
+        return (self.M * self.N + self.N) * self.batch * self.splits if self.splits > 1 else 0
+
+
+ABI_VERSION = CONSTANTS["RLX_ABI_VERSION"]      # rlx_abi_version() of a library built from the same header
+NOISY_PASSES = CONSTANTS["RLX_NOISY_PASSES"]
+NOISY_MAX_LAYERS = CONSTANTS["RLX_NOISY_MAX_LAYERS"]        # layers of one rlx_noisy_sample launch
+NOISY_PASS = {"act": 0, "online": 1, "target": 2, "online_next": 3}
+assert sorted(NOISY_PASS.values()) == list(range(NOISY_PASSES)), "NOISY_PASS names every pass of RLX_NOISY_PASSES"
+ADAM_TICKET_WORDS = CONSTANTS["RLX_ADAM_TICKET_WORDS"]
+MAX_SPLITK_JOBS = CONSTANTS["RLX_MAX_SPLITK_JOBS"]
+MAX_COLUMNS = CONSTANTS["RLX_MAX_COLUMNS"]
+ACT = {None: CONSTANTS["RLX_ACT_NONE"]}         # activation codes by name: {None: 0, "none": 0, "relu": 1, "tanh": 2}
+ACT.update((k[len("RLX_ACT_"):].lower(), v) for k, v in CONSTANTS.items() if k.startswith("RLX_ACT_"))
 
 
 def make_columns(pairs):
@@ -224,60 +327,6 @@ def make_columns(pairs):
         rb = (s[0].numel() if s.dim() > 1 else 1) * s.element_size()
         arr[i] = Column(s.data_ptr(), d.data_ptr(), rb)
     return arr
-
-
-class GemmDesc(ctypes.Structure):
-    """rlx_gemm_desc (include/rlx.h) — field order must match the header."""
-    _fields_ = [
-        ("A", ctypes.c_void_p), ("a_row_tab", ctypes.c_void_p), ("a_k_tab", ctypes.c_void_p),
-        ("B", ctypes.c_void_p), ("C", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-        ("deriv_aux", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
-        ("colsum_out", ctypes.c_void_p),
-        ("a_row_stride", ctypes.c_longlong), ("a_k_stride", ctypes.c_longlong),
-        ("a_batch_stride", ctypes.c_longlong),
-        ("b_k_stride", ctypes.c_longlong), ("b_n_stride", ctypes.c_longlong),
-        ("b_batch_stride", ctypes.c_longlong),
-        ("ldc", ctypes.c_longlong), ("c_batch_stride", ctypes.c_longlong),
-        ("bias_batch_stride", ctypes.c_longlong),
-        ("aux_ld", ctypes.c_longlong), ("aux_batch_stride", ctypes.c_longlong),
-        ("workspace_floats", ctypes.c_longlong), ("colsum_batch_stride", ctypes.c_longlong),
-        ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("batch", ctypes.c_int),
-        ("a_is_u8", ctypes.c_int), ("a_vec_along_k", ctypes.c_int), ("a_tab_vec_ok", ctypes.c_int),
-        ("activation", ctypes.c_int), ("deriv_kind", ctypes.c_int), ("accumulate", ctypes.c_int),
-        ("a_div", ctypes.c_float),
-        ("batch_inner", ctypes.c_int),
-        ("a_batch_stride2", ctypes.c_longlong), ("b_batch_stride2", ctypes.c_longlong),
-        ("bias_batch_stride2", ctypes.c_longlong),
-        ("n_fold", ctypes.c_int),
-        ("row_heads", ctypes.c_void_p), ("n_row_heads", ctypes.c_int),
-        ("kw_min_tiles", ctypes.c_int),
-    ]
-
-
-class SplitkJob(ctypes.Structure):
-    """rlx_splitk_job (include/rlx.h) — field order must match the header."""
-    _fields_ = [("partials", ctypes.c_void_p), ("colsum_partials", ctypes.c_void_p), ("C", ctypes.c_void_p),
-                ("colsum_out", ctypes.c_void_p), ("ldc", ctypes.c_longlong), ("c_batch_stride", ctypes.c_longlong),
-                ("colsum_batch_stride", ctypes.c_longlong), ("M", ctypes.c_int), ("N", ctypes.c_int),
-                ("batch", ctypes.c_int), ("splits", ctypes.c_int), ("n_fold", ctypes.c_int)]
-
-    def workspace_floats(self):
-        """floats of the workspace the outstanding reduction still reads (0 when nothing is outstanding)."""
-        return (self.M * self.N + self.N) * self.batch * self.splits if self.splits > 1 else 0
-
-
-class NoisyLayer(ctypes.Structure):
-    """rlx_noisy_layer (include/rlx.h) — field order must match the header."""
-    _fields_ = [("f", ctypes.c_void_p), ("f64", ctypes.c_void_p), ("K", ctypes.c_int), ("N", ctypes.c_int),
-                ("layer", ctypes.c_int)]
-
-
-NOISY_PASSES = 4                # rlx.h RLX_NOISY_PASSES
-NOISY_MAX_LAYERS = 8            # rlx.h RLX_NOISY_MAX_LAYERS: layers of one rlx_noisy_sample launch
-NOISY_PASS = {"act": 0, "online": 1, "target": 2, "online_next": 3}
-ADAM_TICKET_WORDS = 1056        # rlx.h RLX_ADAM_TICKET_WORDS
-ABI_VERSION = 11                # rlx_abi_version() of the library this module's structures and buffer sizes match
-MAX_SPLITK_JOBS = 8
 
 
 def splitk_reduce_jobs(jobs, stream=None, ppo_tail=None, per_tail=None):
@@ -320,14 +369,6 @@ def conv_input_grad(dz, weights, dx, x_out, deriv, tables, B, H, W, C, KH, KW, S
     run()
 
 
-class PerUpdateDesc(ctypes.Structure):
-    """rlx_per_update_desc (include/rlx.h): the arguments of rlx_per_update for a rider launch."""
-    _fields_ = [("sum_tree", ctypes.c_void_p), ("min_tree", ctypes.c_void_p), ("max_tree", ctypes.c_void_p),
-                ("capacity", ctypes.c_int), ("idx", ctypes.c_void_p), ("td_errors", ctypes.c_void_p), ("n", ctypes.c_int),
-                ("alpha", ctypes.c_double), ("epsilon", ctypes.c_double), ("max_priority", ctypes.c_void_p),
-                ("status", ctypes.c_void_p)]
-
-
 def per_update_desc(args):
     """PrioritizedExperienceReplay.priority_update_args() -> PerUpdateDesc"""
     sum_t, min_t, max_t, cap, idx, err, n, alpha, eps, maxp, status = args
@@ -336,15 +377,6 @@ def per_update_desc(args):
     d.idx, d.td_errors, d.n, d.alpha, d.epsilon = idx.data_ptr(), err.data_ptr(), int(n), float(alpha), float(eps)
     d.max_priority, d.status = maxp.data_ptr(), status.data_ptr()
     return d
-
-
-class ConvDwItem(ctypes.Structure):
-    """rlx_conv_dw_item (include/rlx.h) — field order must match the header."""
-    _fields_ = [("x", ctypes.c_void_p), ("x_tower_stride", ctypes.c_longlong), ("x_is_u8", ctypes.c_int), ("a_div", ctypes.c_float),
-                ("dz", ctypes.c_void_p), ("dz_tower_stride", ctypes.c_longlong)] + \
-               [(n, ctypes.c_int) for n in ("B", "H", "W", "C", "KH", "KW", "S", "filters", "towers")] + \
-               [("dw", ctypes.c_void_p), ("dw_tower_stride", ctypes.c_longlong), ("db", ctypes.c_void_p),
-                ("db_tower_stride", ctypes.c_longlong), ("workspace", ctypes.c_void_p), ("workspace_floats", ctypes.c_longlong)]
 
 
 def conv_dw_item(x, x_tower_stride, x_is_u8, a_div, dz, dz_tower_stride, B, H, W, C, KH, KW, S, Co, towers, dw, dw_tower_stride, db,
@@ -382,107 +414,6 @@ def conv_dw_multi(items, jobs, stream=None):
         ctypes.memmove(ctypes.byref(out), ctypes.byref(j), ctypes.sizeof(SplitkJob))
 
 
-class SmallDenseProblem(ctypes.Structure):
-    """rlx_small_dense_problem (include/rlx.h) — field order must match the header."""
-    _fields_ = [
-        ("x", ctypes.c_void_p), ("x_tower_stride", ctypes.c_longlong),
-        ("w", ctypes.c_void_p), ("w_tower_stride", ctypes.c_longlong),
-        ("bias", ctypes.c_void_p), ("bias_tower_stride", ctypes.c_longlong),
-        ("y", ctypes.c_void_p), ("y_tower_stride", ctypes.c_longlong),
-        ("dy", ctypes.c_void_p), ("dy_tower_stride", ctypes.c_longlong),
-        ("dw", ctypes.c_void_p), ("dw_tower_stride", ctypes.c_longlong),
-        ("db", ctypes.c_void_p), ("db_tower_stride", ctypes.c_longlong),
-        ("dx", ctypes.c_void_p), ("dx_tower_stride", ctypes.c_longlong),
-        ("towers", ctypes.c_int), ("M", ctypes.c_int), ("K", ctypes.c_int), ("N", ctypes.c_int),
-        ("activation", ctypes.c_int), ("lower_activation", ctypes.c_int),
-    ]
-
-
-class MlpDqnDesc(ctypes.Structure):
-    """rlx_mlp_dqn_desc (include/rlx.h) — field order must match the header."""
-    _fields_ = [(n, ctypes.c_void_p) for n in (
-        "weights", "target_weights", "adam_m", "adam_v", "adam_state", "states", "next_states", "actions",
-        "rewards", "game_overs", "importance_weights", "workspace", "sync_words", "loss_out", "norm_out",
-        "td_errors", "status")] + [(n, ctypes.c_longlong) for n in (
-            "workspace_floats", "off_w1", "off_b1", "off_w2", "off_b2", "off_w3", "off_b3")] + [
-        ("discount", ctypes.c_double)] + [(n, ctypes.c_int) for n in (
-            "batch", "obs_dim", "h1", "h2", "n_actions", "huber", "double_dqn")] + [(n, ctypes.c_float) for n in (
-                "learning_rate", "beta1", "beta2", "epsilon", "grad_scale")]
-
-
-class Mlp3(ctypes.Structure):
-    """rlx_mlp3 (include/rlx.h) — field order must match the header."""
-    _fields_ = [(n, ctypes.c_longlong) for n in ("off_w1", "off_b1", "off_w2", "off_b2", "off_w3", "off_b3",
-                                                 "tower_stride1", "tower_stride2", "tower_stride3")] + \
-               [(n, ctypes.c_int) for n in ("d_in", "h1", "h2", "d_out")]
-
-
-class FusedNet(ctypes.Structure):
-    """rlx_fused_net (include/rlx.h) — field order must match the header."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("weights", "target_weights", "adam_m", "adam_v", "adam_state", "grads",
-                                               "norm_out", "ticket")] + \
-               [(n, ctypes.c_float) for n in ("learning_rate", "beta1", "beta2", "epsilon", "grad_scale", "mix_rate")]
-
-
-class Td3FusedDesc(ctypes.Structure):
-    """rlx_td3_fused_desc (include/rlx.h) — field order must match the header."""
-    _fields_ = [("actor", FusedNet), ("critic", FusedNet), ("actor_mlp", Mlp3), ("critic_mlp", Mlp3)] + \
-               [(n, ctypes.c_void_p) for n in ("obs", "next_obs", "actions", "rewards", "game_overs", "noise",
-                                               "action_low", "action_high")] + \
-               [(n, ctypes.c_double) for n in ("noise_clip", "discount", "clip_low", "clip_high")] + \
-               [("use_non_zero_discount_for_terminal_states", ctypes.c_int), ("has_clip", ctypes.c_int),
-                ("actor_scale", ctypes.c_float), ("batch", ctypes.c_int), ("obs_dim", ctypes.c_int),
-                ("act_dim", ctypes.c_int), ("workspace", ctypes.c_void_p), ("workspace_floats", ctypes.c_longlong)] + \
-               [(n, ctypes.c_void_p) for n in ("td_targets", "q_min", "loss", "neg_action_grad")]
-
-
-class SacFusedDesc(ctypes.Structure):
-    """rlx_sac_fused_desc (include/rlx.h) — field order must match the header."""
-    _fields_ = [("policy", FusedNet), ("q", FusedNet), ("v", FusedNet), ("policy_mlp", Mlp3), ("v_mlp", Mlp3)] + \
-               [(n, ctypes.c_longlong) for n in ("q_off_obs_w", "q_off_obs_b", "q_off_act_w", "q_off_act_b", "q_off_fc_w",
-                                                 "q_off_fc_b", "q_off_out_w", "q_off_out_b", "q_stride_obs", "q_stride_act",
-                                                 "q_stride_fc", "q_stride_out")] + \
-               [(n, ctypes.c_void_p) for n in ("obs", "next_obs", "actions", "rewards", "game_overs", "normals")] + \
-               [("discount", ctypes.c_double)] + \
-               [(n, ctypes.c_int) for n in ("resample_noise_per_pass", "batch", "obs_dim", "act_dim", "q_hidden", "reserved")] + \
-               [("workspace", ctypes.c_void_p), ("workspace_floats", ctypes.c_longlong)] + \
-               [(n, ctypes.c_void_p) for n in ("value_targets", "log_target", "td_targets", "dq_da", "q_loss", "v_loss")]
-
-
-class PpoFcHeadsDesc(ctypes.Structure):
-    """rlx_ppo_fc_heads_desc (include/rlx.h) — field order must match the header."""
-    P, LL, F, I = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_int
-    _fields_ = [("x", P), ("x_tower_stride", LL), ("weights", P), ("weight_tower_stride", LL), ("bias", P),
-                ("bias_tower_stride", LL), ("value_w", P), ("value_b", P), ("policy_w", P), ("policy_b", P),
-                ("value_targets", P), ("advantages", P), ("old_probs", P), ("ld_old", LL), ("actions", P), ("clip_scale", P),
-                ("clip_epsilon", F), ("beta_entropy", F), ("grad_scale", F), ("batch", I), ("in_features", I), ("units", I),
-                ("n_actions", I), ("activation", I), ("h", P), ("dz", P), ("values", P), ("logits", P), ("dvalues", P),
-                ("dlogits", P), ("d_value_w", P), ("d_value_b", P), ("d_policy_w", P), ("d_policy_b", P), ("scalars", P),
-                ("likelihood_ratio", P), ("clipped_likelihood_ratio", P), ("status", P), ("workspace", P),
-                ("workspace_floats", LL), ("tickets", P)]
-
-
-class PpoRowsDesc(ctypes.Structure):
-    """rlx_ppo_rows_desc (include/rlx.h) — field order must match the header."""
-    P, LL, F, I = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float, ctypes.c_int
-    _fields_ = [("value_head", SmallDenseProblem), ("policy_head", SmallDenseProblem), ("value_targets", P), ("actions", P),
-                ("advantages", P), ("old_probs", P), ("ld_old", LL), ("clip_scale", P), ("clip_epsilon", F),
-                ("beta_entropy", F), ("grad_scale", F), ("batch", I), ("row_terms", P), ("scalars", P),
-                ("likelihood_ratio", P), ("clipped_likelihood_ratio", P), ("status", P)]
-
-
-class ObserveDesc(ctypes.Structure):
-    """rlx_observe_desc (include/rlx.h) — field order must match the header."""
-    P, LL, D, I = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double, ctypes.c_int
-    _fields_ = [("reward", P), ("filtered_reward", P), ("reward_rescale", D), ("has_clip", I), ("clip_low", D),
-                ("clip_high", D), ("game_over", P), ("stored_game_over", P), ("ep_return", P), ("ep_len", P),
-                ("acc", P), ("last_return", P), ("last_len", P), ("actions", P), ("action_row_bytes", LL),
-                ("cur_state", P), ("next_obs", P), ("reset_obs", P), ("obs_row_bytes", LL), ("mem_action", P),
-                ("mem_reward", P), ("mem_game_over", P), ("mem_obs", P), ("mem_next_obs", P), ("dst_rows", P),
-                ("mem_rows", LL), ("status", P), ("n_env", I)]
-
-
-ACT = {None: 0, "none": 0, "relu": 1, "tanh": 2}
 GEMM_HOOK = None   # bench.py sets this to record the descriptors issued by one update
 CALL_COUNT = 0     # librlx entry points called so far (bench.py: launches of one eager update)
 

@@ -7,17 +7,12 @@ is logged.  The hot path cannot afford a host copy per update, so each signal is
 (rlx_signals_accumulate: every signal of the update in ONE launch); `flush()` reads all records with one copy when a
 row is logged and clears them.  mean = sum / n, stdev = sqrt(sumsq / n - mean^2) — np.std's population form — in fp64.
 """
-import ctypes
 import math
 
 import torch
 
 from . import _rlx
-
-
-class SignalSource(ctypes.Structure):
-    """rlx_signal_source (include/rlx.h)."""
-    _fields_ = [("values", ctypes.c_void_p), ("n", ctypes.c_int), ("is_f64", ctypes.c_int), ("signal", ctypes.c_int)]
+from ._rlx import SignalSource                                  # rlx_signal_source (include/rlx.h)
 
 
 class DeviceSignals(object):

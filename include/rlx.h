@@ -12,10 +12,21 @@
  *   - All pointers are DEVICE pointers unless the parameter name ends in _host.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *   - Every function returns RLX_OK (0) or a negative rlx_status; the human readable
- *     reason is available from rlx_last_error() (thread local).
+ *     reason is available from rlx_last_error() (thread local).  The exceptions return a
+ *     VALUE, and their names say so: rlx_abi_version and every rlx_*_supported (1 / 0)
+ *     return an int that is no status; the `const char *` functions return a string.
+ *     A binding tells the two apart by that naming rule alone.
  *   - No function allocates device memory or synchronises the device unless its
  *     name says so (rlx_*_sync / rlx_event_elapsed_ms): all are hipGraph-capturable.
  *   - Layouts are row-major, innermost dimension last (NHWC for images).
+ *   - This header is also READ BY THE BINDING (coach_amd/_rlx.py builds its prototypes, ctypes
+ *     structures and constants from it), so it keeps to a small grammar.  A structure is
+ *     `typedef struct rlx_NAME { ... } rlx_NAME;` whose members are scalars (int, unsigned,
+ *     unsigned char, float, double, long long, size_t, uint32_t, [u]int64_t), pointers to those, to
+ *     void or to a (`struct`) rlx_* structure, or earlier rlx_* structures by value; several
+ *     declarators per statement and several statements per line are fine.  No arrays,
+ *     bit-fields, unions, function pointers or anonymous members.  A constant the binding needs
+ *     is `#define RLX_NAME <integer>` or an enumerator with an explicit integer value.
  */
 #ifndef RLX_H
 #define RLX_H
@@ -35,7 +46,17 @@ typedef enum rlx_status {
 } rlx_status;
 
 /* ------------------------------------------------------------------ runtime -- */
-int rlx_abi_version(void);               /* bumps when a signature changes          */
+/* What rlx_abi_version() returns; the binding refuses a library built from another value.  It bumps when a signature or
+ * a structure changes (an added entry point does not count: the loader already refuses a library that lacks a declared
+ * symbol).  11: rlx_normal_fill; 10: rlx_gemm_desc.kw_min_tiles, rlx_dqn_head_loss_backward;
+ * 9: rlx_conv32_input_grad_per_update / rlx_splitk_reduce_jobs_per_update (rlx_per_update_desc),
+ * rlx_imgreplay_gather_columns, conv_dw_u8 for one tower of 32 filters (2 B splits); 8: rlx_ppo_fc_rows /
+ * rlx_ppo_heads_tail / rlx_splitk_reduce_jobs_ppo_tail, fused TD3 / SAC updates, rlx_conv_dw_*; 7: rlx_conv123_forward,
+ * rlx_gemm_describe; 6: rlx_conv23_forward, rlx_gemm_multi_defer, rlx_gemm_big_tiles; 5: rlx_adam_tf1_step ticket =
+ * RLX_ADAM_TICKET_WORDS words; 4: per_sample payload rows, libm pow; 3: gemm desc batch_inner, n_fold;
+ * 2: adam_tf1_norm / sac head accumulate. */
+#define RLX_ABI_VERSION 11
+int rlx_abi_version(void);               /* RLX_ABI_VERSION of the header the library was built from */
 const char *rlx_last_error(void);        /* message of the last failure (this thread) */
 const char *rlx_build_arch(void);        /* "gfx950"                                  */
 int rlx_device_count(int *count_host);   /* replaces coach.py:61-84 (cuDeviceGetCount) */

@@ -1,7 +1,7 @@
 """Small helpers shared by the parity tests."""
-import ctypes
-
 import numpy as np
+
+from coach_amd._rlx import Column
 
 
 def dev_tensor(x, dev, dtype=None):
@@ -13,10 +13,6 @@ def dev_tensor(x, dev, dtype=None):
 def status_tensor(dev):
     import torch
     return torch.zeros(1, dtype=torch.int32, device=dev)
-
-
-class Column(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_bytes", ctypes.c_longlong)]
 
 
 def columns(pairs):
