@@ -55,3 +55,14 @@ class CategoricalQHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='categorical_q_head_params',
                  rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class NAFHeadParameters(HeadParameters):
+    """NAFHeadParameters (head_parameters.py:152-159): three Dense layers on the middleware's output — V (1),
+    mu_unscaled (A, this activation, then times the action space's max_abs_range) and l_vector (A(A+1)/2), read as a
+    lower-triangular matrix with an exponentiated diagonal (heads/naf_head.py:45-86)."""
+    head_type = "NAFHead"
+
+    def __init__(self, activation_function='tanh', name='naf_head_params', rescale_gradient_from_head_by_factor=1.0,
+                 loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

@@ -44,6 +44,12 @@ class RunPhase(Enum):                                    # core_types.py:186-190
     UNDEFINED = "Undefined"
 
 
+class GradientClippingMethod(Enum):                      # core_types.py:690-693
+    ClipByGlobalNorm = 0
+    ClipByNorm = 1
+    ClipByValue = 2
+
+
 class Transition(object):
     """core_types.py:236-340 — the object agents written against the reference store and receive
     (coach_amd/memories/reference_api.py); the device agents move columns instead and never build one."""

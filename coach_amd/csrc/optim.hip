@@ -396,6 +396,16 @@ __global__ void clip_by_global_norm_kernel(float *__restrict__ g, long long n, c
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) g[i] *= scale;
 }
 
+__global__ void clip_by_value_kernel(float *__restrict__ g, long long n, float clip) {
+    // tf.clip_by_value = minimum(maximum(x, -clip), clip), written with comparisons so that a NaN stays a NaN
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        float x = g[i];
+        x = x < -clip ? -clip : x;
+        g[i] = x > clip ? clip : x;
+    }
+}
+
 int g_norm_in_kernel = 2;       // rlx_adam_norm_in_kernel
 }  // namespace
 
@@ -543,6 +553,14 @@ int rlx_clip_by_global_norm(float *grads, long long n, const float *global_norm,
     RLX_REQUIRE(grads && global_norm && n > 0, "rlx_clip_by_global_norm: bad arguments");
     RLX_REQUIRE(clip_norm > 0.f, "rlx_clip_by_global_norm: clip_norm must be positive (got %g)", (double)clip_norm);
     RLX_LAUNCH((clip_by_global_norm_kernel), rlx::grid_for(n, kBlock, 1024), kBlock, 0, rlx::as_stream(stream), grads, n, global_norm, clip_norm);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_clip_by_value(float *grads, long long n, float clip_value, void *stream) {
+    RLX_REQUIRE(grads && n > 0, "rlx_clip_by_value: bad arguments");
+    RLX_REQUIRE(clip_value > 0.f, "rlx_clip_by_value: clip_value must be positive (got %g)", (double)clip_value);
+    RLX_LAUNCH((clip_by_value_kernel), rlx::grid_for(n, kBlock, 1024), kBlock, 0, rlx::as_stream(stream), grads, n, clip_value);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -855,3 +855,140 @@ class BootstrappedDQNNet(DQNNet):
         self._backward_from_q(acts, q, None, B)
         self._apply_update(grad_scale, sync)
         return self.loss
+
+
+class NAFNet(_NetBase):
+    """NAFNetworkParameters (agents/naf_agent.py:34-43): vector embedder -> FC middleware -> NAFHead
+    (heads/naf_head.py:45-86): three Dense layers on the middleware's output — V (1), mu_unscaled (A, the head's
+    activation, then * output_scale) and l_vector (A(A+1)/2, a packed lower-triangular L with an exponentiated
+    diagonal) — and Q = V - 1/2 ||L^T (u - mu)||^2.  The layers go through the generic launches (the multi-problem
+    narrow-dense ones where their preconditions hold); the head's arithmetic, its loss and its gradient are one launch
+    (rlx_naf_head_loss, csrc/naf.hip), acting and the signals use rlx_naf_head_forward."""
+    MAX_ACTIONS = 32
+    MAX_BATCH = 256
+    HEAD = "main/naf_q_values_head"
+
+    def __init__(self, device, obs_shape, action_dim, output_scale, activation="relu", embedder="Medium",
+                 middleware="Medium", learning_rate=1e-3, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4,
+                 replace_mse_with_huber_loss=False, head_activation="tanh", clip_gradients=None,
+                 clip_by_value=False, seed=0):
+        """clip_gradients with clip_by_value: GradientClippingMethod.ClipByValue (architecture.py:241-245) — every
+        gradient clamped to [-clip_gradients, clip_gradients]; otherwise ClipByGlobalNorm as in the other networks."""
+        if len(obs_shape) != 1:
+            raise ValueError("NAF works only for continuous control problems (vector observations)")
+        A = int(action_dim)
+        if not 1 <= A <= self.MAX_ACTIONS:
+            raise ValueError("1 <= action dimension <= %d (rlx_naf_head_loss), got %d" % (self.MAX_ACTIONS, A))
+        self.obs_shape, self.image, self.A, self.NL = tuple(obs_shape), False, A, A * (A + 1) // 2
+        self.huber = bool(replace_mse_with_huber_loss)
+        self.clip_gradients, self.clip_value = clip_gradients, bool(clip_by_value)
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        self.v_layer = G.Dense(self.params, self.HEAD + "/V", feat, 1, None, 1)
+        self.mu_layer = G.Dense(self.params, self.HEAD + "/mu_unscaled", feat, A, head_activation, 1)
+        self.l_layer = G.Dense(self.params, self.HEAD + "/l_vector", feat, self.NL, None, 1)
+        self.heads = [self.v_layer, self.mu_layer, self.l_layer]
+        self.modules = [self.torso] + self.heads
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
+        self.scale = torch.as_tensor(np.broadcast_to(np.asarray(output_scale, dtype=np.float32), (A,)).copy(),
+                                     device=device)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=device)
+        self.partials = torch.zeros(self.MAX_BATCH, dtype=torch.float32, device=device)     # per-row loss terms
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+
+    # ---------------------------------------------------------------------------------- forward
+    def _heads_forward(self, feat, layers, tag, weights=None, inputs=None):
+        """the given head layers on the middleware's output -> {layer: output Tensor}; the narrow ones in one launch.
+        inputs: {layer: the Tensor it reads} (the training pass gives every layer its own gradient buffer)."""
+        ctx = self.ctx
+        x = lambda l: inputs[l] if inputs else feat
+        narrow = [l for l in layers if l.N <= G.SMALL_N]
+        out = {}
+        if len(narrow) > 1:
+            out.update(zip(narrow, G.small_dense_forward_multi(ctx, [(l, x(l)) for l in narrow], tag=tag,
+                                                                weights=weights)))
+        for l in layers:
+            if l not in out:
+                out[l] = l.forward(ctx, x(l), tag=tag, weights=weights)
+        return out
+
+    def state_values(self, obs, B, use_target=False, tag="v"):
+        """V(s) [B] (a view of the V layer's output)."""
+        w = self.target if use_target else None
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        return self.v_layer.forward(self.ctx, acts[-1], tag=tag, weights=w).data.view(B)
+
+    def head_forward(self, obs, B, actions=None, use_target=False, tag="act", mu_out=None, with_signals=False):
+        """-> dict(mu [B, A]) and, with_signals, Q [B], Advantage [B], L [B, A, A], V [B] of the head at `actions`
+        (None: at u = mu, where Advantage = 0 and Q = V) — naf_agent.py:101-131."""
+        ctx, A = self.ctx, self.A
+        w = self.target if use_target else None
+        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        o = self._heads_forward(acts[-1], self.heads, tag, w)
+        v, m, l = (o[k].data for k in self.heads)
+        mu = mu_out if mu_out is not None else ctx.buffer("naf/mu", (B, A), tag=tag)
+        res = dict(mu=mu, V=v.view(B))
+        q = adv = L = None
+        if with_signals:
+            q, adv = ctx.buffer("naf/q", (B,), tag=tag), ctx.buffer("naf/adv", (B,), tag=tag)
+            L = ctx.buffer("naf/L", (B, A, A), tag=tag)
+            res.update(Q=q, Advantage=adv, L=L)
+        self.lib.naf_head_forward(v, 1, m, A, l, self.NL, self.scale, actions, A, B, A, mu, q, adv, L, ctx.stream)
+        return res
+
+    # --------------------------------------------------------------------------------- training
+    def clip_by_value(self):
+        """clip_gradients (ClipByValue, architecture.py:241-245): the flat gradient buffer clamped in place."""
+        self.lib.clip_by_value(self.params.grads, self.params.size, float(self.clip_gradients), self.ctx.stream)
+
+    def _apply_update(self, grad_scale, sync, mix_rate=None):
+        """the gradients in params.grads -> the weights: clip, share between the workers, Adam (self.norm = the global
+        norm of the unclipped gradients either way).  mix_rate: a soft target update is due right after this update —
+        the Adam pass mixes the target where it can."""
+        if self.clip_gradients and self.clip_value:
+            self.grad_norm()
+            self.clip_by_value()
+            clipped = True
+        else:
+            clipped = self.clip_by_global_norm()
+        if sync is not None:
+            sync.all_reduce_sum(self.params.grads)
+        self.apply_gradients(grad_scale, with_norm=not clipped, mix_rate=mix_rate)
+
+    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount, grad_scale=1.0, sync=None,
+                         td_targets_out=None, q_out=None, adv_out=None, mix_rate=None):
+        """NAFAgent.learn_from_batch (agents/naf_agent.py:80-99), all on device: the target network's V(s'), the
+        online head on s, rlx_naf_head_loss (TD targets, Q, loss, dV / dmu_unscaled / dl_vector), the three layers'
+        backward pass with their input gradients summed, the torso's backward pass, clip, Adam."""
+        if not 1 <= B <= self.MAX_BATCH:
+            raise ValueError("1 <= batch <= %d (rlx_naf_head_loss), got %d" % (self.MAX_BATCH, B))
+        ctx, A, NL = self.ctx, self.A, self.NL
+        v_next = self.state_values(next_obs, B, use_target=True, tag="next_t")
+        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+        feat = acts[-1]
+        feat.ensure_grad()
+        # every head layer writes its input gradient into a buffer of its own; they are added into feat.grad below
+        ins = {self.v_layer: feat}
+        for l in self.heads[1:]:
+            side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
+            side.grad = ctx.buffer(l.name + "/input:grad", tuple(feat.data.shape), tag="train")
+            ins[l] = side
+        o = self._heads_forward(feat, self.heads, "train", inputs=ins)
+        v, m, l = (o[k] for k in self.heads)
+        self.lib.naf_head_loss(v.data, 1, m.data, A, l.data, NL, self.scale, actions, A, v_next, 1, rewards, game_overs,
+                               float(discount), B, A, int(self.huber), 1.0, v.ensure_grad(), 1, m.ensure_grad(), A,
+                               l.ensure_grad(), NL, self.partials, self.ticket, self.loss, td_targets_out, q_out,
+                               adv_out, ctx.stream)
+        narrow = [k for k in self.heads if k.N <= G.SMALL_N and B * k.N <= 1024]
+        if len(narrow) > 1:
+            G.small_dense_backward_multi(ctx, [(k, ins[k], o[k]) for k in narrow])
+        for k in self.heads:
+            if len(narrow) <= 1 or k not in narrow:
+                k.backward(ctx, ins[k], o[k])
+        g = feat.grad
+        for k in self.heads[1:]:
+            self.lib.axpby(g, 1.0, g, 1.0, ins[k].grad, g.numel(), ctx.stream)
+        feat.grad_is_dz = all(ins[k].grad_is_dz for k in self.heads)
+        self.torso.backward(ctx, acts)
+        self._apply_update(grad_scale, sync, mix_rate)
+        return self.loss

@@ -816,6 +816,9 @@ int rlx_global_norm(const float *x, long long n, float *norm_out, float *workspa
  * gradient becomes NaN (the reference's behaviour, and oracle/agents.py:205-210's); global_norm inf: the scale is 0. */
 int rlx_clip_by_global_norm(float *grads, long long n, const float *global_norm, float clip_norm,
                             void *stream);
+/* tf.clip_by_value(grad, -clip_value, clip_value) on every gradient (architecture.py:241-245, clip method
+ * ClipByValue): an element-wise clamp of the flat gradient buffer, in place; a NaN stays a NaN. */
+int rlx_clip_by_value(float *grads, long long n, float clip_value, void *stream);
 
 /* ------------------------------------ continuous-control agents (DDPG / TD3 / SAC) -- */
 /* dst[r][c] = scale * src[r][c]: concat / slice / negate / DDPGActorHead output_scale
@@ -1040,6 +1043,38 @@ int rlx_bootstrapped_egreedy(const float *q_values, long long ld, int n_heads, c
                              const double *explore_uniforms, const int *random_actions,
                              const double *tie_break_uniforms, double epsilon, int n_env, int n_actions,
                              float *values_out, int *actions, void *stream);
+
+/* ------------------------------------------------- Normalized Advantage Functions (NAF) -- */
+/* The NAFHead (architectures/tensorflow_components/heads/naf_head.py:45-86), NAFAgent's TD targets
+ * (agents/naf_agent.py:83-90), the head's loss (head.py:143-186: mean squared error, or Huber with delta 1) and its
+ * gradient in ONE launch: one wave per batch row, four rows per workgroup.
+ * Inputs, each [batch] rows with its own leading dimension: v (the V layer's output), mu_unscaled [A] (the mu_unscaled
+ * layer's ACTIVATED output), l_vector [A(A+1)/2] (column c of the lower-triangular L at i_c = sum_{k<c} (A - k):
+ * L[c][c] = exp(l[i_c]), L[r][c] = l[i_c + r - c] for r > c), actions [A], v_next (the target network's V(s'));
+ * output_scale [A]; rewards, game_overs [batch].
+ * Arithmetic (fp32, every sum in ascending index order, no contraction; tests/naf_ref.py states it operation for
+ * operation): mu = mu_unscaled * output_scale, d = u - mu, y_c = sum_{r>=c} L[r][c] d_r, Q = V - 0.5 sum_c y_c^2; the
+ * TD target r + (1 - game_over) * discount * v_next in fp64, rounded to fp32 once (as rlx_dqn_head_loss does);
+ * g = grad_scale * l'(Q - target) / batch; dv = g, dmu_unscaled_c = g (L y)_c output_scale_c (the gradient w.r.t. the
+ * layer's activated output), dl_vector: dL[r][c] = -g y_c d_r, times L[c][c] on the diagonal.
+ * loss_scalar = mean of the row terms, summed in a fixed tree by the workgroup that draws the last ticket (bit-identical
+ * run to run, no float atomics).  partials: [batch] floats of workspace; ticket: one zero-initialised word (left at
+ * zero).  Optional outputs (null): td_targets_out, q_out, adv_out [batch].  1 <= A <= 32, 1 <= batch <= 256.
+ * Added under ABI version 11, like the entry points above. */
+int rlx_naf_head_loss(const float *v, long long ld_v, const float *mu_unscaled, long long ld_mu, const float *l_vector,
+                      long long ld_l, const float *output_scale, const float *actions, long long ld_act,
+                      const float *v_next, long long ld_vnext, const float *rewards, const unsigned char *game_overs,
+                      double discount, int batch, int action_dim, int huber, float grad_scale, float *dv,
+                      long long ld_dv, float *dmu_unscaled, long long ld_dmu, float *dl_vector, long long ld_dl,
+                      float *partials, unsigned int *ticket, float *loss_scalar, float *td_targets_out, float *q_out,
+                      float *adv_out, void *stream);
+/* The head's forward pass alone, for acting and for the Q / L / Advantage / Action / V signals
+ * (agents/naf_agent.py:101-131).  actions null: u = mu, so Adv = 0 and Q = V.  Outputs (each optional, at least one):
+ * mu_out [batch][A], q_out [batch], adv_out [batch], l_out [batch][A][A] (zeros above the diagonal).  1 <= A <= 32. */
+int rlx_naf_head_forward(const float *v, long long ld_v, const float *mu_unscaled, long long ld_mu,
+                         const float *l_vector, long long ld_l, const float *output_scale, const float *actions,
+                         long long ld_act, int batch, int action_dim, float *mu_out, float *q_out, float *adv_out,
+                         float *l_out, void *stream);
 
 /* ------------------------------------------------------------ CartPole-v0 / -v1 -- */
 /* N CartPole environments per GPU: gym 0.12.5's physics (gym/envs/classic_control/cartpole.py `step`, fp64, Euler)
