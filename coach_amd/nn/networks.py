@@ -857,6 +857,47 @@ class BootstrappedDQNNet(DQNNet):
         return self.loss
 
 
+class MixedTargetDQNNet(DQNNet):
+    """The DQN network (plain or dueling head) of the agents whose TD target mixes the Double-DQN target with other
+    estimates: PALAgent (agents/pal_agent.py:70-111, the advantage-learning correction from the target network on s
+    and the Monte Carlo return) and MixedMonteCarloAgent (agents/mmc_agent.py:57-83, the Monte Carlo return).  The
+    passes are DQN's; the targets, the head's loss and its gradient are one launch (rlx_mixed_target_head_loss,
+    csrc/pal.hip).  The fused small-MLP update computes DQN targets, so the fused kernels and the head inside the
+    torso's last launch stay DQN's alone."""
+    FUSED_MLP = False
+    FUSED_ACT = False
+    HEAD_FORWARD_WITH_TORSO = False
+    MODES = ("pal", "mmc")
+
+    def __init__(self, device, obs_shape, n_actions, noisy=False, **kw):
+        if noisy:
+            raise ValueError("noisy dense layers are not implemented for the PAL / Mixed Monte Carlo network")
+        super().__init__(device, obs_shape, n_actions, noisy=False, **kw)
+
+    def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, total_returns, discount, pal_alpha=0.9,
+                         persistent=False, mixing_rate=0.1, mode="pal", grad_scale=1.0, sync=None, states_pair=None,
+                         td_targets_out=None):
+        """PALAgent / MixedMonteCarloAgent.learn_from_batch, all on device: online on s' (the selector), for PAL the
+        target on s, target on s' and online on s, the mixed targets with loss and dQ, backward, Adam.
+        total_returns: fp64 [B], the rows' n_step_discounted_rewards; td_targets_out: optional fp32 [B, A]."""
+        if mode not in self.MODES:
+            raise ValueError("mode is one of %s, got %r" % (self.MODES, mode))
+        A = self.A
+        sel = self.q_values(next_obs, B, tag="next_o", noise_pass="online_next").data.view(B, A)
+        cur = self.q_values(obs, B, use_target=True, tag="cur_t", noise_pass="target").data.view(B, A) \
+            if mode == "pal" else None
+        acts, q, saved, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
+        dq = q.ensure_grad()
+        self.last_q, self.last_q_cur, self.last_q_next, self.last_q_sel = q.data, cur, q_next, sel    # (views)
+        self.lib.mixed_target_head_loss(q.data, A, cur, q_next, sel, A, actions, rewards, game_overs, total_returns,
+                                        float(discount), float(pal_alpha), int(bool(persistent)), float(mixing_rate),
+                                        B, A, int(self.huber), 1.0, dq, A, td_targets_out, A, self.loss, self.status,
+                                        self.ctx.stream)
+        self._backward_from_q(acts, q, saved, B)
+        self._apply_update(grad_scale, sync)
+        return self.loss
+
+
 class NAFNet(_NetBase):
     """NAFNetworkParameters (agents/naf_agent.py:34-43): vector embedder -> FC middleware -> NAFHead
     (heads/naf_head.py:45-86): three Dense layers on the middleware's output — V (1), mu_unscaled (A, the head's

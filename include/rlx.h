@@ -1076,6 +1076,32 @@ int rlx_naf_head_forward(const float *v, long long ld_v, const float *mu_unscale
                          long long ld_act, int batch, int action_dim, float *mu_out, float *q_out, float *adv_out,
                          float *l_out, void *stream);
 
+/* ------------------------------------ Persistent Advantage Learning / Mixed Monte Carlo -- */
+/* PALAgent.learn_from_batch (agents/pal_agent.py:70-111) or MixedMonteCarloAgent.learn_from_batch
+ * (agents/mmc_agent.py:57-83), the QHead loss (MSE / Huber) on their targets and its gradient w.r.t. Q_online in ONE
+ * launch, modelled on rlx_dqn_head_loss: one workgroup, one row per thread, batch <= 1024, the batch mean in the same
+ * fixed-order tree (no float atomics).  q_online and q_target_cur (the target network on s) [batch][ld_q];
+ * q_next_target and q_next_selector (the target and the online network on s') [batch][ld_next]; total_returns [batch]
+ * fp64: the rows' n_step_discounted_rewards.  Per row with taken action a: sel = first maximum of q_next_selector,
+ * y = r + (1 - game_over) * discount * q_next_target[sel] in fp64 (the Double-DQN target), then
+ *   q_target_cur given (PAL): T = fp32(y) - fp32(pal_alpha) * adv in fp32, adv = max q_target_cur - q_target_cur[a], or
+ *       with persistent != 0 the smaller of it and max q_next_target - q_next_target[sel];
+ *       T = fp32( fp64(fp32(1 - mixing_rate) * T) + mixing_rate * total_return );
+ *   q_target_cur NULL (MMC): T = fp32( (1 - mixing_rate) * y + mixing_rate * total_return ), all fp64; pal_alpha and
+ *       persistent are ignored.
+ * (tests/pal_ref.py states every rounding; they are the reference's under numpy >= 2.)  With pal_alpha = 0 and
+ * mixing_rate = 0 dq, td_targets and loss_scalar equal rlx_dqn_head_loss's with that selector and no importance weights,
+ * bit for bit.  dq[b][a_b] = grad_scale * l'(Q - T) / batch, zero elsewhere.  status |= 1 for an action outside
+ * [0, n_actions) (the row then contributes nothing and its dq row is left unwritten, as in rlx_dqn_head_loss).
+ * td_targets (Q_online with T at the taken action) and loss_scalar are optional outputs. */
+int rlx_mixed_target_head_loss(const float *q_online, long long ld_q, const float *q_target_cur,
+                               const float *q_next_target, const float *q_next_selector, long long ld_next,
+                               const int *actions, const float *rewards, const unsigned char *game_overs,
+                               const double *total_returns, double discount, double pal_alpha, int persistent,
+                               double mixing_rate, int batch, int n_actions, int huber, float grad_scale, float *dq,
+                               long long ld_dq, float *td_targets, long long ld_targets, float *loss_scalar, int *status,
+                               void *stream);
+
 /* ------------------------------------------------------------ CartPole-v0 / -v1 -- */
 /* N CartPole environments per GPU: gym 0.12.5's physics (gym/envs/classic_control/cartpole.py `step`, fp64, Euler)
  * behind gym's TimeLimit (max_episode_steps), i.e. what `GymVectorEnvironment(level='CartPole-v0')` steps through
