@@ -187,12 +187,14 @@ __global__ void __launch_bounds__(64) bootstrapped_egreedy_kernel(const float *_
         return;
     }
     float mx = v_s[0];
-    for (int k = 1; k < A; ++k) mx = fmaxf(mx, v_s[k]);
+    for (int k = 1; k < A; ++k) mx = (v_s[k] > mx || v_s[k] != v_s[k]) ? v_s[k] : mx;   // egreedy_kernel's np.max
     const float tol = 1e-8f + 1e-5f * fabsf(mx);                 // egreedy_kernel's isclose (explore.hip)
+    const bool mx_finite = fabsf(mx) <= 3.402823466e+38f;
     int best = 0;
     double bv = -1.0;
     for (int k = 0; k < A; ++k) {
-        const double v = fabsf(v_s[k] - mx) <= tol ? tie_rand[(size_t)e * A + k] : 0.0;
+        const bool close = (mx_finite && fabsf(v_s[k] - mx) <= tol) || v_s[k] == mx;
+        const double v = close ? tie_rand[(size_t)e * A + k] : 0.0;
         if (v > bv) { bv = v; best = k; }
     }
     actions[e] = best;

@@ -88,14 +88,16 @@ __global__ void egreedy_kernel(const float *__restrict__ q, long long ld,
     }
     const float *qe = q + (size_t)e * ld;
     float mx = qe[0];
-    for (int a = 1; a < n_actions; ++a) mx = fmaxf(mx, qe[a]);
+    for (int a = 1; a < n_actions; ++a) mx = (qe[a] > mx || qe[a] != qe[a]) ? qe[a] : mx;   // np.max: a NaN comes through
     // np.argmax(np.random.random(shape) * np.isclose(action_values, action_values.max()))  (:93-94)
-    // isclose on fp32 inputs (numpy 2 keeps fp32): |a - b| <= atol + rtol * |b|
+    // isclose on fp32 inputs (numpy 2 keeps fp32): (|a - b| <= atol + rtol * |b| and b finite) or a == b -- an infinite
+    // maximum is close only to its equals, a NaN maximum to nothing (the mask is empty and argmax returns 0)
     const float tol = 1e-8f + 1e-5f * fabsf(mx);
+    const bool mx_finite = fabsf(mx) <= 3.402823466e+38f;
     int best = 0;
     double bv = -1.0;
     for (int a = 0; a < n_actions; ++a) {
-        const bool close = fabsf(qe[a] - mx) <= tol;
+        const bool close = (mx_finite && fabsf(qe[a] - mx) <= tol) || qe[a] == mx;
         const double v = close ? tie_rand[(size_t)e * n_actions + a] : 0.0;
         if (v > bv) {
             bv = v;
@@ -121,7 +123,8 @@ __global__ void gaussian_action_kernel(const float *__restrict__ mean, const flo
     out[t] = (float)v;
 }
 
-// np.argmax per row: the FIRST maximal entry (Categorical.get_action outside TRAIN, categorical.py:50-52)
+// np.argmax per row: the FIRST maximal entry (Categorical.get_action outside TRAIN, categorical.py:50-52); a NaN counts
+// as the maximum, so the first NaN of a row wins
 __global__ void argmax_rows_kernel(const float *__restrict__ v, long long ld, int n_rows, int n_cols, int *out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_rows) return;
@@ -129,7 +132,7 @@ __global__ void argmax_rows_kernel(const float *__restrict__ v, long long ld, in
     int best = 0;
     float bv = r[0];
     for (int a = 1; a < n_cols; ++a)
-        if (r[a] > bv) {
+        if (bv == bv && (r[a] > bv || r[a] != r[a])) {
             bv = r[a];
             best = a;
         }

@@ -590,12 +590,13 @@ __global__ void __launch_bounds__(1024) mlp_q_act_kernel(const MlpActDev p) {
         } else {
             const float *qe = qs + e * p.A;
             float mx = qe[0];
-            for (int a = 1; a < p.A; ++a) mx = fmaxf(mx, qe[a]);
+            for (int a = 1; a < p.A; ++a) mx = (qe[a] > mx || qe[a] != qe[a]) ? qe[a] : mx;   // egreedy_kernel's np.max
             const float tol = 1e-8f + 1e-5f * fabsf(mx);
+            const bool mx_finite = fabsf(mx) <= 3.402823466e+38f;                               // ... and its np.isclose
             int best = 0;
             double bv = -1.0;
             for (int a = 0; a < p.A; ++a) {
-                const bool close = fabsf(qe[a] - mx) <= tol;
+                const bool close = (mx_finite && fabsf(qe[a] - mx) <= tol) || qe[a] == mx;
                 const double v = close ? p.tie_rand[(size_t)e * p.A + a] : 0.0;
                 if (v > bv) {
                     bv = v;
