@@ -56,6 +56,10 @@ class MixedTargetDQNAgent(DQNAgent):
             raise ValueError("%s mixes the Monte Carlo return into its targets, and only the episodic replay computes "
                              "one (n_step_discounted_rewards): use EpisodicExperienceReplayParameters, not %s"
                              % (name, type(self.ap.memory).__name__))
+        from ..memories.episodic.episodic_hindsight_experience_replay import EpisodicHindsightExperienceReplayParameters
+        if isinstance(self.ap.memory, EpisodicHindsightExperienceReplayParameters):
+            raise ValueError("%s reads the transitions' Monte Carlo returns (n_step_discounted_rewards), which the "
+                             "hindsight replay does not provide: use EpisodicExperienceReplayParameters" % name)
         self.parameter_noise = False
         self.A = ep.num_actions
         self.batch_size = net.batch_size

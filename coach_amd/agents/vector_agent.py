@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from .. import _rlx
-from ..core_types import EnvironmentSteps, RunPhase, TrainingSteps
+from ..core_types import EnvironmentEpisodes, EnvironmentSteps, RunPhase, TrainingSteps
 
 
 class no_gc_while_capturing(object):
@@ -267,10 +267,13 @@ class VectorOffPolicyAgent(GraphRunner):
         if self.ap.seed is not None:                     # agents/agent.py:49-55
             random.seed(self.ap.seed)
             np.random.seed(self.ap.seed)
+        self._check_input_embedder_names(ep)
         self.phase = RunPhase.HEATUP
         self.total_steps_counter = 0
         self.training_iteration = 0
         self.last_training_phase_step = 0
+        self._train_episodes_finished = 0                       # TRAIN-phase episodes finished so far (every env's counts)
+        self._last_training_phase_episode = 0                   # ... at the last training phase opened by episodes
         self.last_target_network_update_step = 0
         self.current_episode_steps_counter = 0                  # steps of env 0's running episode
         self._episode_steps = np.zeros(self.n_env, dtype=np.int64)     # ... of every env's
@@ -292,6 +295,19 @@ class VectorOffPolicyAgent(GraphRunner):
         if self.noise_source == "device":
             self._key_noise_generator()
             self._act_event = 0             # the acting draws count their own events
+
+    def _check_input_embedder_names(self, ep):
+        """several named (Empty) input embedders stand for ONE concatenated observation vector: their sorted names must
+        be the environment's slices, laid out in that order (SchemeViews.input_embedders_parameters)."""
+        for wrapper in self.ap.network_wrappers.values():
+            names = getattr(wrapper, "input_embedder_names", None)
+            if names is None:
+                continue
+            slices = getattr(ep, "observation_slices", None) or {}
+            order = tuple(sorted(slices, key=lambda k: slices[k][0]))
+            if tuple(sorted(slices)) != tuple(names) or order != tuple(names):
+                raise ValueError("the input embedders {} do not match the environment's observation slices {}"
+                                 .format(list(names), sorted(slices) or "(none: the observation is one vector)"))
 
     def _key_noise_generator(self):
         """key of the agent's device noise generator: (noise seed, rank)"""
@@ -326,6 +342,15 @@ class VectorOffPolicyAgent(GraphRunner):
             return PrioritizedExperienceReplay(mp.max_size, mp.alpha, mp.beta, mp.epsilon,
                                                mp.allow_duplicates_in_batch_sampling,
                                                exact_pow=getattr(mp, "exact_pow", "device"), **kw)
+        from ..memories.episodic.episodic_hindsight_experience_replay import (
+            EpisodicHindsightExperienceReplay, EpisodicHindsightExperienceReplayParameters)
+        if isinstance(mp, EpisodicHindsightExperienceReplayParameters):
+            # the goal and achieved-goal slices come from the environment's table, by goals_space.goal_name
+            return EpisodicHindsightExperienceReplay(
+                mp.max_size, mp.hindsight_transitions_per_regular_transition, mp.hindsight_goal_selection_method,
+                mp.goals_space, observation_slices=getattr(ep, "observation_slices", None),
+                allow_duplicates_in_batch_sampling=mp.allow_duplicates_in_batch_sampling,
+                discount=self.ap.algorithm.discount, max_episode_length=self.L, **kw)
         if isinstance(mp, EpisodicExperienceReplayParameters):
             return EpisodicExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling,
                                             n_step=getattr(mp, "n_step", -1), discount=self.ap.algorithm.discount,
@@ -476,6 +501,7 @@ class VectorOffPolicyAgent(GraphRunner):
             self._episode_steps[ended] = 0
             if self.phase == RunPhase.TRAIN:       # heat-up episode ends open no training phase later
                 self._unconsumed_episode_lengths.extend(int(x) for x in self.ended_episode_lengths)
+                self._train_episodes_finished += int(ended.size)
             if record and self.signal_stats is not None:
                 self._note_finished_episodes(ended)
             self.handle_episode_ended()
@@ -543,7 +569,10 @@ class VectorOffPolicyAgent(GraphRunner):
 
     def _training_phases_due(self):
         """agent.py:662-699 for a step counter that advances n_env at a time."""
-        steps = self.ap.algorithm.num_consecutive_playing_steps.num_steps
+        playing = self.ap.algorithm.num_consecutive_playing_steps
+        if isinstance(playing, EnvironmentEpisodes):
+            return self._training_phase_due_by_episodes(playing.num_steps)
+        steps = playing.num_steps
         # what the reference's memory holds at this point: an episodic memory receives an episode only
         # when it ends (agent.py:576-584), so its num_transitions() counts complete episodes
         mem = self.memory
@@ -568,6 +597,21 @@ class VectorOffPolicyAgent(GraphRunner):
         due = min(gap // steps, max(1, self.n_env // steps))
         self.last_training_phase_step = self.total_steps_counter
         return due
+
+    def _training_phase_due_by_episodes(self, episodes):
+        """num_consecutive_playing_steps = EnvironmentEpisodes(n) (agent.py:662-699): a phase is due when at least n
+        episodes finished since the last phase — every env's finished TRAIN-phase episode is one — and the memory holds
+        an episode; the marker moves to the current count; at most one phase per check."""
+        if self._train_episodes_finished - self._last_training_phase_episode < episodes:
+            return 0
+        mem = self.memory
+        if hasattr(mem, "num_complete_episodes"):
+            if mem.num_complete_episodes() < 1:
+                return 0
+        elif mem.num_transitions() <= 0:
+            return 0
+        self._last_training_phase_episode = self._train_episodes_finished
+        return 1
 
     _staged = None            # device views of the current update's record (see _update_record), or None
     # the host-RNG side of a train() call on a producer thread (_HostDrawsAhead): same values, measured SLOWER — C5 953 - 1087

@@ -58,8 +58,37 @@ class SchemeViews(object):
 
     @property
     def input_embedders_parameters(self):
+        names = self.__dict__.get("input_embedder_names")
+        if names is not None:            # several Empty vector embedders over one concatenated observation (see the setter)
+            field = self._EMBEDDER_FIELDS["observation"]
+            return {k: _SchemeView(self, field, self._TUPLE_SCHEMES) for k in names}
         return {k: _SchemeView(self, f, self._TUPLE_SCHEMES) for k, f in self._EMBEDDER_FIELDS.items()
                 if hasattr(self, f)}
+
+    @input_embedders_parameters.setter
+    def input_embedders_parameters(self, value):
+        """`input_embedders_parameters = {...}` of a preset text.  Accepted: (a) the class's own entries ('observation'
+        [, 'action']) — each record's `scheme` goes to its flat field; (b) several named vector embedders that are ALL
+        `Empty`: the reference concatenates its embedders' outputs in sorted() name order (general_network.py:252,277),
+        so with nothing but Empty embedders the middleware sees the concatenation of the named observations — which is
+        the ONE observation vector an environment with a slice table emits.  The names are kept in
+        `input_embedder_names` (sorted) and checked against the environment's slices when the agent is built.
+        Anything else has no device network and raises."""
+        if not isinstance(value, dict) or not value:
+            raise ValueError("input_embedders_parameters takes a non-empty dict of embedder parameter records")
+        fields = {k: f for k, f in self._EMBEDDER_FIELDS.items() if hasattr(self, f)}
+        if set(value) == set(fields):
+            for k, rec in value.items():
+                setattr(self, fields[k], scheme_to_native(rec.scheme, self._TUPLE_SCHEMES))
+            self.__dict__.pop("input_embedder_names", None)
+            return
+        empty = all(getattr(getattr(rec, "scheme", None), "name", getattr(rec, "scheme", None)) == "Empty"
+                    for rec in value.values())
+        if list(fields) != ["observation"] or len(value) < 2 or not empty:
+            raise ValueError("supported input embedders: {} or several named vector embedders whose scheme is Empty "
+                             "(got {})".format(sorted(fields), {k: getattr(v, "scheme", v) for k, v in value.items()}))
+        setattr(self, fields["observation"], scheme_to_native(next(iter(value.values())).scheme, self._TUPLE_SCHEMES))
+        self.__dict__["input_embedder_names"] = tuple(sorted(value))
 
     @property
     def middleware_parameters(self):

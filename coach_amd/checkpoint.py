@@ -29,6 +29,7 @@ _MEMORY_SCALARS = ["cursor", "count", "pending", "committed_total", "steps", "_o
 _AGENT_SCALARS = ["total_steps_counter", "training_iteration", "last_training_phase_step",
                   "last_target_network_update_step", "current_episode_steps_counter", "last_episode_steps",
                   "_episode_just_ended", "_episode_steps", "_unconsumed_episode_lengths",
+                  "_train_episodes_finished", "_last_training_phase_episode",      # num_consecutive_playing_steps in episodes
                   "_draw_pool", "_draw_pos", "_draw_table_from", "_rec_missing",      # PPO: host draws made for steps that have not run yet
                   "_noise_seed", "_act_event",     # device noise (TD3 / SAC noise_source = "device"): key and acting counter
                   "_needs_head", "_open_rows"]     # Bootstrapped DQN: envs that start an episode, rows whose masks are not drawn yet

@@ -118,10 +118,27 @@ def vector_parameters(env_params):
              episode_length=env_params.episode_length or limit, seed=env_params.seed)
 
 
+BIT_FLIP_LEVEL = 'rl_coach.environments.toy_problems.bit_flip:BitFlip'     # a 'module:Class' level (gym_environment.py:253-262)
+
+
+def bit_flip_parameters(env_params):
+    """env_params -> BitFlipVectorEnvironmentParameters from `additional_simulator_parameters` (the constructor
+    arguments of the reference's BitFlip class: bit_length, max_steps, mean_zero)."""
+    from .bit_flip_vector_environment import BitFlipVectorEnvironmentParameters
+    sim = dict(env_params.additional_simulator_parameters or {})
+    unknown = set(sim) - {"bit_length", "max_steps", "mean_zero"}
+    if unknown:
+        raise ValueError("BitFlip takes bit_length, max_steps and mean_zero, not {}".format(sorted(unknown)))
+    if env_params.episode_length is not None:
+        sim["max_steps"] = env_params.episode_length
+    return BitFlipVectorEnvironmentParameters(env_params.num_envs, sim.get("bit_length", 16), sim.get("max_steps"),
+                                              sim.get("mean_zero", False), seed=env_params.seed)
+
+
 def create(env_params, device, rank=0):
-    """The `path` target of the parameter classes above: build the environment of a preset on `device`.  CartPole is
-    the one level whose simulator exists on the device (csrc/cartpole.hip); every other level gets the synthetic
-    environment with the level's spaces."""
+    """The `path` target of the parameter classes above: build the environment of a preset on `device`.  CartPole and
+    BitFlip are the levels whose simulators exist on the device (csrc/cartpole.hip, csrc/bit_flip.hip); every other
+    level gets the synthetic environment with the level's spaces."""
     from .synthetic_vector_environment import SyntheticVectorEnvironment
     name = env_params.level_name()
     if name in ('CartPole-v0', 'CartPole-v1') and not getattr(env_params, "synthetic", False):
@@ -129,4 +146,7 @@ def create(env_params, device, rank=0):
         return CartPoleVectorEnvironment(
             CartPoleVectorEnvironmentParameters(env_params.num_envs, name, env_params.seed, env_params.episode_length),
             device, rank=rank)
+    if name == BIT_FLIP_LEVEL:
+        from .bit_flip_vector_environment import BitFlipVectorEnvironment
+        return BitFlipVectorEnvironment(bit_flip_parameters(env_params), device, rank=rank)
     return SyntheticVectorEnvironment(vector_parameters(env_params), device, rank=rank)

@@ -1281,6 +1281,37 @@ int rlx_ppo_fc_heads(const rlx_ppo_fc_heads_desc *desc_host, void *stream);
 /* Measurement switch: workgroup 0 and the last arrivers record s_memtime into the workspace's last 16 int64. */
 int rlx_ppo_fc_heads_stamps(int enable);
 
+/* ------------------------------------------------- BitFlip on the device + hindsight relabelling (added entry points) -- */
+/* The reference's toy problem (environments/toy_problems/bit_flip.py:54-90) for n_env envs, shaped like rlx_cartpole_*.
+ * bits: uint8[n_env][2 * bit_length], [goal | state]; obs / next_obs / reset_obs: fp32[n_env][2 * bit_length] in the same
+ * layout, 0 / 1 or, with mean_zero, -1 / +1.  Action a flips state bit a; reward 0 when state == goal else -1; game over
+ * when they are equal or after max_steps steps.  next_obs is the stepped (terminal) observation; reset_obs (written only
+ * where game_over is set) the first observation of the env's next episode.  Reset draws: Philox, key (seed, env_id0 + e),
+ * counter (episode, word index, 0, 3), one bit per state / goal bit, low bit first; the goal is redrawn from the following
+ * words while it equals the state, at most 32 times, then its bit 0 is flipped (csrc/bit_flip.hip).  status bit 1 = an
+ * action outside [0, bit_length): nothing is flipped.  next_episode != 0: forced reset (every env starts its next episode). */
+int rlx_bitflip_reset(unsigned char *bits, float *obs, int *episode, int *steps, int n_env, int bit_length,
+                      int mean_zero, unsigned int seed, unsigned int env_id0, int next_episode, void *stream);
+int rlx_bitflip_step(const int *action, unsigned char *bits, int *episode, int *steps, float *next_obs,
+                     float *reset_obs, float *reward, unsigned char *game_over, int n_env, int bit_length,
+                     int max_steps, int mean_zero, unsigned int seed, unsigned int env_id0, int *status,
+                     void *stream);
+/* EpisodicHindsightExperienceReplay.store_episode (episodic_hindsight_experience_replay.py:108-145) for ONE finished
+ * episode of `length` steps stored time-major (row r(t) = ((first_step + t) mod ring_steps) * n_env + env < R =
+ * n_env * ring_steps); every column has (1 + k) * R rows and copy j of real row r is row R + r * k + j.  For base
+ * transition t < n_base and copy j, selected_steps[t * k + j] (device int32, in [0, length)) is the step whose STATE's
+ * achieved slice [achieved_at, +goal_dim) becomes the goal: it replaces [goal_at, +goal_dim) of obs and next_obs in the
+ * copy; the action row is copied; (reward, game_over) = distance(goal, achieved slice of next_obs[r(t)]) <= threshold ?
+ * (goal_reaching_reward, 1) : (default_reward, 0), the distance in fp64 summed in index order.  status bit 2 = a
+ * selected step outside the episode (that copy is not written). */
+#define RLX_HER_EUCLIDEAN 0
+#define RLX_HER_MANHATTAN 2
+int rlx_her_relabel_episode(float *obs, float *next_obs, void *action, float *reward, unsigned char *game_over,
+                            const int *selected_steps, long long first_step, int length, int n_base, int k, int env,
+                            int n_env, long long ring_steps, int obs_dim, int goal_at, int achieved_at, int goal_dim,
+                            int action_row_bytes, int metric, double threshold, float goal_reaching_reward,
+                            float default_reward, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
