@@ -3,15 +3,18 @@
 
 K copies of the Q head on one torso (nn.networks.BootstrappedDQNNet: one Dense(feat, K * A)).  Every stored transition
 carries a K-bit mask — which heads learn from it — in the replay's mask column; every env follows one head per episode
-while training and the heads' majority vote otherwise.
-Per step: every head's Q values -> rlx_bootstrapped_egreedy (selected head or vote, then the epsilon-greedy choice).
+while training and the heads' majority vote otherwise.  With UCBParameters as the exploration parameters
+(exploration_policies/ucb.py) the same ensemble is acted on by mean + lamb * std over the heads instead: no head is
+selected or staged, the masks are drawn as before.
+Per step: every head's Q values -> rlx_bootstrapped_egreedy (selected head or vote, then the epsilon-greedy choice) or
+rlx_ucb_egreedy.
 Per update: online(s'), target(s'), online(s) -> rlx_bootstrapped_dqn_head_loss (per head a Double-DQN target where the
 mask has its bit, the K head losses and their sum, dQ) -> backward (the torso gets 1 / K of the heads' summed gradient)
 -> TF1 Adam.
 
 Host draws, on the global legacy np.random stream, where the reference makes them (level_manager.py:215-269):
   * reset_internal_state -> select_head: np.random.randint(K) for every env that starts an episode, in env order, at
-    the start of the step (every phase);
+    the start of the step (every phase) -- Bootstrapped only, UCB draws nothing here;
   * observe -> np.random.binomial(1, p, K) per env, in env order: at the start of every step (the previous response —
     at an episode's first step the initial one, whose draw is discarded as in the reference) and once more right after
     the env step for every env whose episode ended on it (a terminal response is observed at once);
@@ -28,6 +31,7 @@ from ..architectures.head_parameters import DuelingQHeadParameters
 from ..core_types import RunPhase
 from ..exploration_policies.bootstrapped import Bootstrapped, BootstrappedParameters
 from ..exploration_policies.parameter_noise import network_is_noisy
+from ..exploration_policies.ucb import UCB, UCBParameters
 from ..memories.non_episodic.experience_replay import ExperienceReplay
 from ..nn.networks import BootstrappedDQNNet
 from .dqn_agent import DQNAgent, DQNAgentParameters, DQNNetworkParameters
@@ -62,6 +66,7 @@ def mask_words(bits):
 
 class BootstrappedDQNAgent(DQNAgent):
     MASK_COLUMN = True
+    ucb = False                      # True with UCBParameters: mean + lamb * std over the heads, no selected head
     PER_REFUSAL = ("BootstrappedDQNAgent does not use replay priorities (the reference agent passes no importance "
                    "weights to its heads and never updates priorities), and its transitions carry a head mask: use "
                    "an ExperienceReplay memory")
@@ -71,8 +76,10 @@ class BootstrappedDQNAgent(DQNAgent):
         VectorOffPolicyAgent.__init__(self, agent_parameters, environment, device, dist, use_graphs)
         ep, net, exp = environment.p, self.ap.network_wrappers["main"], self.ap.exploration
         head = net.heads_parameters[0]
-        if not isinstance(exp, BootstrappedParameters):
-            raise ValueError("BootstrappedDQNAgent explores with the Bootstrapped policy (BootstrappedParameters)")
+        if not isinstance(exp, (BootstrappedParameters, UCBParameters)):
+            raise ValueError("BootstrappedDQNAgent explores with the Bootstrapped policy (BootstrappedParameters) or "
+                             "with UCB over its heads (UCBParameters)")
+        self.ucb = isinstance(exp, UCBParameters)
         self.K = int(head.num_output_head_copies)
         if int(exp.architecture_num_q_heads) != self.K:
             raise ValueError("exploration.architecture_num_q_heads (%d) and the head's num_output_head_copies (%d) differ"
@@ -151,7 +158,8 @@ class BootstrappedDQNAgent(DQNAgent):
 
     # --------------------------------------------------------------------------------- acting
     def _make_exploration_policy(self):
-        return Bootstrapped(self.A, self.n_env, self.device, self.ap.exploration)
+        policy = UCB if isinstance(self.ap.exploration, UCBParameters) else Bootstrapped
+        return policy(self.A, self.n_env, self.device, self.ap.exploration)
 
     def choose_action(self, states):
         pol = self.exploration_policy
@@ -159,7 +167,7 @@ class BootstrappedDQNAgent(DQNAgent):
         draws = pol.draw()                                                   # EGreedy's, per env, in order
         self._run(("q", self.n_env), lambda: self._q_forward(states))
         eps, d = pol.stage(draws)
-        self._heads_dev = pol.stage_heads()
+        self._heads_dev = None if self.ucb else pol.stage_heads()
         self._select_actions(d["u"], d["ra"], d["tie"], eps)
         return self.actions
 
@@ -168,7 +176,14 @@ class BootstrappedDQNAgent(DQNAgent):
             self.n_env, self.K * self.A)
 
     def _select_actions(self, u, ra, tie, eps):
-        """Bootstrapped.get_action (bootstrapped.py:72-85): the selected head's values in TRAIN, the vote otherwise."""
+        """Bootstrapped.get_action (bootstrapped.py:72-85): the selected head's values in TRAIN, the vote otherwise.
+        UCB.get_action (ucb.py:76-86): the heads' mean + lamb * std in TRAIN, the mean otherwise."""
+        if self.ucb:
+            pol = self.exploration_policy
+            self.lib.ucb_egreedy(self._q_act, self.K * self.A, self.K, float(pol.lamb), int(pol.use_std), u, ra, tie,
+                                 float(eps), self.n_env, self.A, self.last_action_values, pol.std, self.actions,
+                                 _rlx.current_stream())
+            return
         self.lib.bootstrapped_egreedy(self._q_act, self.K * self.A, self.K, self._heads_dev,
                                       int(self.phase != RunPhase.TRAIN), u, ra, tie, float(eps), self.n_env, self.A,
                                       self.last_action_values, self.actions, _rlx.current_stream())

@@ -1,4 +1,5 @@
-// Bootstrapped DQN on gfx950: the K-head masked loss + gradient and the ensemble acting reduction.
+// Bootstrapped DQN on gfx950: the K-head masked loss + gradient and the ensemble acting reductions (selected head / vote,
+// and UCB's mean + lambda * std).
 //
 // Replaces, in the reference (paths under rl_coach/):
 //   * BootstrappedDQNAgent.learn_from_batch   agents/bootstrapped_dqn_agent.py:57-86  (per head and row: Double-DQN target
@@ -7,6 +8,8 @@
 //   * the K QHead losses and their sum        architectures/tensorflow_components/heads/q_head.py, head.py:172-181
 //   * Bootstrapped.get_action                 exploration_policies/bootstrapped.py:72-85 (selected head in TRAIN, majority
 //                                             vote otherwise) + EGreedy.get_action, e_greedy.py:84-101
+//   * UCB.get_action                          exploration_policies/ucb.py:76-86 (mean + lamb * std over the heads in TRAIN,
+//                                             the mean otherwise) + EGreedy.get_action
 //
 // Q is the head layer's output [rows][K*A]: column h*A + a is action a of head h.  The arithmetic of one (row, head) is
 // that of dqn_head_loss_kernel (targets.hip) for that head alone with a selector and no importance weights — the same
@@ -137,6 +140,25 @@ __global__ void __launch_bounds__(kBootThreads) bootstrapped_dqn_head_loss_kerne
     }
 }
 
+// EGreedy.get_action (e_greedy.py:84-101) on one env's action values v[0 .. A), by one lane: the random action when the
+// env explores, else the argmax of the tie-break draws over the entries close to the maximum.
+__device__ __forceinline__ int egreedy_choice(const float *v, int A, double explore_u, int random_act,
+                                              const double *tie, double epsilon) {
+    if (explore_u < epsilon) return random_act;                  // e_greedy.py:88
+    float mx = v[0];
+    for (int k = 1; k < A; ++k) mx = (v[k] > mx || v[k] != v[k]) ? v[k] : mx;   // egreedy_kernel's np.max
+    const float tol = 1e-8f + 1e-5f * fabsf(mx);                 // egreedy_kernel's isclose (explore.hip)
+    const bool mx_finite = fabsf(mx) <= 3.402823466e+38f;
+    int best = 0;
+    double bv = -1.0;
+    for (int k = 0; k < A; ++k) {
+        const bool close = (mx_finite && fabsf(v[k] - mx) <= tol) || v[k] == mx;
+        const double d = close ? tie[k] : 0.0;
+        if (d > bv) { bv = d; best = k; }
+    }
+    return best;
+}
+
 // One wave per env.  The env's [K*A] row is staged into the padded tile; TRAIN: the values are the selected head's;
 // otherwise lane h votes for head h's first maximum, the counts' first maximum wins (np.bincount + np.argmax: the
 // lowest action index on a tie) and the values are its one-hot vector.  Lane 0 then makes rlx_egreedy's choice on the
@@ -182,22 +204,48 @@ __global__ void __launch_bounds__(64) bootstrapped_egreedy_kernel(const float *_
     __syncthreads();
     if (values_out && t < A) values_out[(size_t)e * A + t] = v_s[t];
     if (t != 0) return;
-    if (explore_u[e] < epsilon) {                                // e_greedy.py:88
-        actions[e] = random_act[e];
-        return;
+    actions[e] = egreedy_choice(v_s, A, explore_u[e], random_act[e], tie_rand + (size_t)e * A, epsilon);
+}
+
+// One wave per env, lane a = action a.  UCB.get_action (exploration_policies/ucb.py:76-86): the values are the heads' mean
+// plus lamb times their (population) standard deviation while training, the mean alone otherwise; lane 0 then makes
+// rlx_egreedy's choice on them.  The sums run over the heads in head order, in fp32, one rounding per operation (the
+// file is compiled without FMA contraction) -- the order numpy's mean / std over axis 0 take (tests/ucb_ref.py).
+__global__ void __launch_bounds__(64) ucb_egreedy_kernel(const float *__restrict__ q, long long ld, int n_heads, float lamb,
+                                                         int use_std, const double *__restrict__ explore_u,
+                                                         const int *__restrict__ random_act,
+                                                         const double *__restrict__ tie_rand, double epsilon, int n_env,
+                                                         int n_actions, float *__restrict__ values_out,
+                                                         float *__restrict__ std_out, int *__restrict__ actions) {
+    __shared__ float q_s[kBootTile];
+    __shared__ float v_s[kBootMaxActions];
+    const int e = blockIdx.x, t = threadIdx.x, K = n_heads, A = n_actions, P = tile_pitch(A);
+    const float *qe = q + (size_t)e * ld;
+    for (int c = t; c < K * A; c += 64) q_s[(c / A) * P + c % A] = qe[c];
+    __syncthreads();
+    if (t < A) {
+        const float kf = (float)K;
+        float s = q_s[t];
+        for (int h = 1; h < K; ++h) s += q_s[h * P + t];
+        const float mean = s / kf;
+        float v = mean;
+        if (use_std) {
+            float d = q_s[t] - mean;
+            float acc = d * d;
+            for (int h = 1; h < K; ++h) {
+                d = q_s[h * P + t] - mean;
+                acc += d * d;
+            }
+            const float sd = sqrtf(acc / kf);
+            v = mean + lamb * sd;
+            if (std_out) std_out[(size_t)e * A + t] = sd;
+        }
+        v_s[t] = v;
+        values_out[(size_t)e * A + t] = v;
     }
-    float mx = v_s[0];
-    for (int k = 1; k < A; ++k) mx = (v_s[k] > mx || v_s[k] != v_s[k]) ? v_s[k] : mx;   // egreedy_kernel's np.max
-    const float tol = 1e-8f + 1e-5f * fabsf(mx);                 // egreedy_kernel's isclose (explore.hip)
-    const bool mx_finite = fabsf(mx) <= 3.402823466e+38f;
-    int best = 0;
-    double bv = -1.0;
-    for (int k = 0; k < A; ++k) {
-        const bool close = (mx_finite && fabsf(v_s[k] - mx) <= tol) || v_s[k] == mx;
-        const double v = close ? tie_rand[(size_t)e * A + k] : 0.0;
-        if (v > bv) { bv = v; best = k; }
-    }
-    actions[e] = best;
+    __syncthreads();
+    if (t != 0) return;
+    actions[e] = egreedy_choice(v_s, A, explore_u[e], random_act[e], tie_rand + (size_t)e * A, epsilon);
 }
 
 }  // namespace
@@ -244,6 +292,22 @@ int rlx_bootstrapped_egreedy(const float *q_values, long long ld, int n_heads, c
                 "rlx_bootstrapped_egreedy: bad shape (heads=%d <= 32, actions=%d <= 18)", n_heads, n_actions);
     RLX_LAUNCH((bootstrapped_egreedy_kernel), n_env, 64, 0, rlx::as_stream(stream), q_values, ld, n_heads, selected_head,
                vote, explore_uniforms, random_actions, tie_break_uniforms, epsilon, n_env, n_actions, values_out, actions);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_ucb_egreedy(const float *q_values, long long ld, int n_heads, float lamb, int use_std,
+                    const double *explore_uniforms, const int *random_actions, const double *tie_break_uniforms,
+                    double epsilon, int n_env, int n_actions, float *values_out, float *std_out, int *actions,
+                    void *stream) {
+    RLX_REQUIRE(q_values && explore_uniforms && random_actions && tie_break_uniforms && values_out && actions,
+                "rlx_ucb_egreedy: null pointer");
+    RLX_REQUIRE(n_env > 0 && n_heads >= 1 && n_heads <= kBootMaxHeads && n_actions >= 1 && n_actions <= kBootMaxActions &&
+                    ld >= (long long)n_heads * n_actions,
+                "rlx_ucb_egreedy: bad shape (heads=%d <= 32, actions=%d <= 18)", n_heads, n_actions);
+    RLX_LAUNCH((ucb_egreedy_kernel), n_env, 64, 0, rlx::as_stream(stream), q_values, ld, n_heads, lamb, use_std,
+               explore_uniforms, random_actions, tie_break_uniforms, epsilon, n_env, n_actions, values_out, std_out,
+               actions);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -135,10 +135,29 @@ def bit_flip_parameters(env_params):
                                               sim.get("mean_zero", False), seed=env_params.seed)
 
 
+EXPLORATION_CHAIN_LEVEL = 'rl_coach.environments.toy_problems.exploration_chain:ExplorationChain'
+_CHAIN_ARGUMENTS = ("chain_length", "start_state", "max_steps", "observation_type", "left_state_reward",
+                    "right_state_reward")
+
+
+def exploration_chain_parameters(env_params):
+    """env_params -> ExplorationChainVectorEnvironmentParameters from `additional_simulator_parameters` (the constructor
+    arguments of the reference's ExplorationChain class, with its defaults)."""
+    from .exploration_chain_vector_environment import ExplorationChainVectorEnvironmentParameters
+    sim = dict(env_params.additional_simulator_parameters or {})
+    unknown = set(sim) - set(_CHAIN_ARGUMENTS)
+    if unknown:
+        raise ValueError("ExplorationChain takes {}, not {}".format(", ".join(_CHAIN_ARGUMENTS), sorted(unknown)))
+    if env_params.episode_length is not None:
+        sim["max_steps"] = env_params.episode_length
+    return ExplorationChainVectorEnvironmentParameters(env_params.num_envs, **sim)
+
+
 def create(env_params, device, rank=0):
-    """The `path` target of the parameter classes above: build the environment of a preset on `device`.  CartPole and
-    BitFlip are the levels whose simulators exist on the device (csrc/cartpole.hip, csrc/bit_flip.hip); every other
-    level gets the synthetic environment with the level's spaces."""
+    """The `path` target of the parameter classes above: build the environment of a preset on `device`.  CartPole,
+    BitFlip and ExplorationChain are the levels whose simulators exist on the device (csrc/cartpole.hip,
+    csrc/bit_flip.hip, csrc/exploration_chain.hip); every other level gets the synthetic environment with the level's
+    spaces."""
     from .synthetic_vector_environment import SyntheticVectorEnvironment
     name = env_params.level_name()
     if name in ('CartPole-v0', 'CartPole-v1') and not getattr(env_params, "synthetic", False):
@@ -149,4 +168,7 @@ def create(env_params, device, rank=0):
     if name == BIT_FLIP_LEVEL:
         from .bit_flip_vector_environment import BitFlipVectorEnvironment
         return BitFlipVectorEnvironment(bit_flip_parameters(env_params), device, rank=rank)
+    if name == EXPLORATION_CHAIN_LEVEL:
+        from .exploration_chain_vector_environment import ExplorationChainVectorEnvironment
+        return ExplorationChainVectorEnvironment(exploration_chain_parameters(env_params), device, rank=rank)
     return SyntheticVectorEnvironment(vector_parameters(env_params), device, rank=rank)

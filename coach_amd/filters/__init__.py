@@ -6,4 +6,4 @@ non-batching filters once per data point, filter.py:331-335, after a copy.deepco
 from .observation import (ObservationNormalizationFilter, ObservationRescaleToSizeFilter,  # noqa: F401
                           ObservationRGBToYFilter, ObservationStackingFilter, ObservationToUInt8Filter)
 from .reward import RewardClippingFilter, RewardRescaleFilter  # noqa: F401
-from .filter import InputFilter, NoInputFilter  # noqa: F401
+from .filter import InputFilter, NoInputFilter, NoOutputFilter, OutputFilter  # noqa: F401

@@ -1,4 +1,5 @@
-"""InputFilter — mirror of rl_coach/filters/filter.py:224-350 for device batches."""
+"""InputFilter — mirror of rl_coach/filters/filter.py:224-350 for device batches — and the empty OutputFilter presets
+name (filter.py:96-110, 245-250)."""
 from collections import OrderedDict
 
 
@@ -38,3 +39,18 @@ class InputFilter(object):
 
 class NoInputFilter(InputFilter):                        # filter.py:353-358
     pass
+
+
+class OutputFilter(object):                              # filter.py:96-110
+    """actions pass from the agent to the environment unchanged: action filters have no device implementation"""
+
+    def __init__(self, action_filters=None, is_a_reference_filter=False):
+        if action_filters:
+            raise ValueError("action filters {} have no device implementation".format(list(action_filters)))
+        self._action_filters = OrderedDict()
+        self.i_am_a_reference_filter = is_a_reference_filter
+
+
+class NoOutputFilter(OutputFilter):                      # filter.py:245-250
+    def __init__(self):
+        super().__init__(is_a_reference_filter=False)

@@ -73,6 +73,7 @@ class BasicRLGraphManager(object):
         self.logger = CsvLogger(csv_path)
         self.total_steps_counters = {RunPhase.HEATUP: 0, RunPhase.TRAIN: 0, RunPhase.TEST: 0}
         self.training_steps = 0
+        self.train_episodes = 0          # episodes finished in train_and_act (every env's episode counts)
         self.phase = RunPhase.UNDEFINED
         self._episodes_logged = 0
         self._mid_episode = False        # some env is inside an episode that the next period must abandon
@@ -205,6 +206,7 @@ class BasicRLGraphManager(object):
                 agent.train()
             trained = agent.training_iteration - before
             self.training_steps += trained
+            self.train_episodes += self._episodes_ended_on_last_step()
             done += n if isinstance(steps, EnvironmentSteps) else \
                 self._episodes_ended_on_last_step() if isinstance(steps, EnvironmentEpisodes) else trained
         self._mid_episode = self._episodes_ended_on_last_step() != agent.n_env
@@ -274,8 +276,14 @@ class BasicRLGraphManager(object):
         self.verify_graph_was_created()
         self.heatup(self.schedule.heatup_steps)
         imp = self.schedule.improve_steps
-        counter = (lambda: self.training_steps) if isinstance(imp, TrainingSteps) else \
-            (lambda: self.total_steps_counters[RunPhase.TRAIN])
+        # improve_steps in its own unit (graph_manager.py:536-539): training iterations, TRAIN-phase episodes finished
+        # (every env's episode counts) or environment steps
+        if isinstance(imp, TrainingSteps):
+            counter = lambda: self.training_steps
+        elif isinstance(imp, EnvironmentEpisodes):
+            counter = lambda: self.train_episodes
+        else:
+            counter = lambda: self.total_steps_counters[RunPhase.TRAIN]
         count_end = counter() + imp.num_steps
         while counter() < count_end:
             self.train_and_act(self.schedule.steps_between_evaluation_periods)

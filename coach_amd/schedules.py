@@ -45,6 +45,31 @@ class LinearSchedule(Schedule):                           # schedules.py:39-63
         return value - self.decay_delta
 
 
+class PieceWiseSchedule(Schedule):                        # schedules.py:66-91
+    """[(schedule, EnvironmentSteps), ...] applied one after the other, with the reference's stepping rule as it is: a
+    step advances the current piece FIRST and then switches when the count of earlier steps on it has reached its length,
+    so the first piece is advanced num_steps + 1 times and the switching step reports the next piece's untouched initial
+    value; that step already counts 1 for the new piece, which is therefore advanced num_steps times before its own
+    switch.  The last piece is never left."""
+
+    def __init__(self, schedules):
+        super().__init__(schedules[0][0].initial_value)
+        self.schedules = schedules
+        self.current_schedule = schedules[0]
+        self.current_schedule_idx = 0
+        self.current_schedule_step_count = 0
+
+    def step(self):
+        piece, length = self.current_schedule
+        piece.step()
+        if self.current_schedule_idx < len(self.schedules) - 1 and self.current_schedule_step_count >= length.num_steps:
+            self.current_schedule_idx += 1
+            self.current_schedule = self.schedules[self.current_schedule_idx]
+            self.current_schedule_step_count = 0
+        self.current_value = self.current_schedule[0].current_value
+        self.current_schedule_step_count += 1
+
+
 class ExponentialSchedule(Schedule):                      # schedules.py:96-125
     """value *= decay_coefficient per step, stopping at final_value."""
 

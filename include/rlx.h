@@ -1043,6 +1043,17 @@ int rlx_bootstrapped_egreedy(const float *q_values, long long ld, int n_heads, c
                              const double *explore_uniforms, const int *random_actions,
                              const double *tie_break_uniforms, double epsilon, int n_env, int n_actions,
                              float *values_out, int *actions, void *stream);
+/* UCB.get_action (exploration_policies/ucb.py:76-86) + rlx_egreedy's choice, one wave per env, on the same [K*A] rows
+ * (K <= 32, A <= 18, ld >= K*A).  Per action a, in fp32, one rounding per operation and the heads in head order:
+ * s = q[0][a], s += q[h][a]; mean = s / (float)K; d_h = q[h][a] - mean; acc = d_0 * d_0, acc += d_h * d_h;
+ * std = sqrtf(acc / (float)K).  use_std != 0 (TRAIN): values = mean + lamb * std; use_std == 0: values = mean and std is
+ * not computed.  values_out [n_env][A]: the action values the choice was made on; std_out [n_env][A] (optional, written
+ * only with use_std); the draws and the fp32 isclose tie test as rlx_bootstrapped_egreedy takes them.  An added entry
+ * point. */
+int rlx_ucb_egreedy(const float *q_values, long long ld, int n_heads, float lamb, int use_std,
+                    const double *explore_uniforms, const int *random_actions, const double *tie_break_uniforms,
+                    double epsilon, int n_env, int n_actions, float *values_out, float *std_out, int *actions,
+                    void *stream);
 
 /* ------------------------------------------------- Normalized Advantage Functions (NAF) -- */
 /* The NAFHead (architectures/tensorflow_components/heads/naf_head.py:45-86), NAFAgent's TD targets
@@ -1311,6 +1322,21 @@ int rlx_her_relabel_episode(float *obs, float *next_obs, void *action, float *re
                             int n_env, long long ring_steps, int obs_dim, int goal_at, int achieved_at, int goal_dim,
                             int action_row_bytes, int metric, double threshold, float goal_reaching_reward,
                             float default_reward, int *status, void *stream);
+
+/* ------------------------------------------------- ExplorationChain on the device (added entry points) -- */
+/* The reference's toy problem (environments/toy_problems/exploration_chain.py:24-94) for n_env envs, shaped like
+ * rlx_bitflip_*.  state / steps: int32[n_env]; obs / next_obs / reset_obs: fp32[n_env][chain_length], ones at [0, state]
+ * (therm != 0) or at state alone (therm == 0).  Action 0 moves left unless state == 0, action 1 right unless state ==
+ * chain_length - 1; reward after the move: left_state_reward at state 0, right_state_reward at the last state, else 0;
+ * game over when steps >= max_steps.  next_obs is the stepped (terminal) observation; reset_obs (written only where
+ * game_over is set) the observation of start_state.  No random draws: every episode lasts exactly max_steps steps.
+ * status bit 1 = an action other than 0 / 1: nothing moves (the step counts).  chain_length > 3, 0 <= start_state <
+ * chain_length. */
+int rlx_chain_reset(int *state, int *steps, float *obs, int n_env, int chain_length, int start_state, int therm,
+                    void *stream);
+int rlx_chain_step(const int *action, int *state, int *steps, float *next_obs, float *reset_obs, float *reward,
+                   unsigned char *game_over, int n_env, int chain_length, int start_state, int max_steps, int therm,
+                   float left_state_reward, float right_state_reward, int *status, void *stream);
 
 #ifdef __cplusplus
 }
