@@ -27,7 +27,6 @@ import numpy as np
 import torch
 
 from .. import _rlx
-from ..architectures.head_parameters import DuelingQHeadParameters
 from ..core_types import RunPhase
 from ..exploration_policies.bootstrapped import Bootstrapped, BootstrappedParameters
 from ..exploration_policies.parameter_noise import network_is_noisy
@@ -35,7 +34,6 @@ from ..exploration_policies.ucb import UCB, UCBParameters
 from ..memories.non_episodic.experience_replay import ExperienceReplay
 from ..nn.networks import BootstrappedDQNNet
 from .dqn_agent import DQNAgent, DQNAgentParameters, DQNNetworkParameters
-from .vector_agent import VectorOffPolicyAgent
 
 
 class BootstrappedDQNNetworkParameters(DQNNetworkParameters):            # bootstrapped_dqn_agent.py:26-30
@@ -70,45 +68,34 @@ class BootstrappedDQNAgent(DQNAgent):
     PER_REFUSAL = ("BootstrappedDQNAgent does not use replay priorities (the reference agent passes no importance "
                    "weights to its heads and never updates priorities), and its transitions carry a head mask: use "
                    "an ExperienceReplay memory")
+    NET = BootstrappedDQNNet
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
-        # not DQNAgent.__init__ (it builds a DQNNet), but its order: network, memory, exploration policy, buffers
-        VectorOffPolicyAgent.__init__(self, agent_parameters, environment, device, dist, use_graphs)
-        ep, net, exp = environment.p, self.ap.network_wrappers["main"], self.ap.exploration
-        head = net.heads_parameters[0]
-        if not isinstance(exp, (BootstrappedParameters, UCBParameters)):
-            raise ValueError("BootstrappedDQNAgent explores with the Bootstrapped policy (BootstrappedParameters) or "
-                             "with UCB over its heads (UCBParameters)")
-        self.ucb = isinstance(exp, UCBParameters)
-        self.K = int(head.num_output_head_copies)
-        if int(exp.architecture_num_q_heads) != self.K:
-            raise ValueError("exploration.architecture_num_q_heads (%d) and the head's num_output_head_copies (%d) differ"
-                             % (exp.architecture_num_q_heads, self.K))
-        self.A = ep.num_actions
-        self.batch_size = net.batch_size
-        self.parameter_noise = False
-        obs_shape = tuple(ep.observation_shape) + (self.stack,) if self.image else tuple(ep.observation_shape)
-        self.networks = {"main": BootstrappedDQNNet(
-            self.device, obs_shape, self.A, self.K, dueling=isinstance(head, DuelingQHeadParameters),
-            noisy=network_is_noisy(net), activation=net.activation_function, embedder=net.embedder_scheme,
-            middleware=net.middleware_scheme, learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
-            adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon,
-            replace_mse_with_huber_loss=net.replace_mse_with_huber_loss, seed=self.ap.seed or 0,
-            head_activation=head.activation_function,
-            head_gradient_rescale=head.rescale_gradient_from_head_by_factor, clip_gradients=net.clip_gradients)}
-        self.memory = self._make_memory(action_dim=None)
-        if type(self.memory) is not ExperienceReplay:
-            raise ValueError(self.PER_REFUSAL)
-        self.exploration_policy = self._make_exploration_policy()
-        self.share_p = float(exp.bootstrapped_data_sharing_probability)
-        self.actions = torch.zeros(self.n_env, dtype=torch.int32, device=self.device)
-        self.td_errors = None
-        self.loss_acc = torch.zeros(1, dtype=torch.float32, device=self.device)
+        super().__init__(agent_parameters, environment, device, dist, use_graphs)
+        self.share_p = float(self.ap.exploration.bootstrapped_data_sharing_probability)
         self.last_action_values = torch.zeros(self.n_env, self.A, dtype=torch.float32, device=self.device)
         self._needs_head = np.ones(self.n_env, dtype=bool)          # envs whose next step starts an episode
         self._open_rows = None          # physical rows of the last stored step whose masks are not drawn yet, per env
         self.debug_masks = None         # tests set this to a list: (physical row, mask word) of every stored transition
-        self._finish_init()
+
+    def _check_parameters(self):
+        exp = self.ap.exploration
+        if not isinstance(exp, (BootstrappedParameters, UCBParameters)):
+            raise ValueError("BootstrappedDQNAgent explores with the Bootstrapped policy (BootstrappedParameters) or "
+                             "with UCB over its heads (UCBParameters)")
+        self.ucb = isinstance(exp, UCBParameters)
+        self.K = int(self.ap.network_wrappers["main"].heads_parameters[0].num_output_head_copies)
+        if int(exp.architecture_num_q_heads) != self.K:
+            raise ValueError("exploration.architecture_num_q_heads (%d) and the head's num_output_head_copies (%d) differ"
+                             % (exp.architecture_num_q_heads, self.K))
+        self.parameter_noise = False
+
+    def _network_arguments(self, net):
+        return (self.K,), dict(noisy=network_is_noisy(net))          # (a noisy network: refused by the network)
+
+    def _check_memory(self):
+        if type(self.memory) is not ExperienceReplay:
+            raise ValueError(self.PER_REFUSAL)
 
     # ------------------------------------------------------------------------ host draws (see the module text)
     def _draw_mask(self):
@@ -202,8 +189,6 @@ class BootstrappedDQNAgent(DQNAgent):
     def learn_from_batch(self, batch):
         """BootstrappedDQNAgent.learn_from_batch (bootstrapped_dqn_agent.py:57-86)."""
         self._run(("learn", False, False), lambda: self._learn_device(batch))
-        net = self.networks["main"]
         # 'Q': every head's online prediction on the batch's states (the reference samples its TD-target arrays in the
         # middle of the loop that fills them, :75)
-        self.signals = {"Loss": net.loss, "Grads (unclipped)": net.norm, "Q": net.last_q.view(-1)}
-        return net.loss
+        return self._loss_signals(Q=self.networks["main"].last_q.view(-1))

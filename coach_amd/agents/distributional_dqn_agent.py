@@ -15,39 +15,17 @@ import torch
 
 from ..memories.non_episodic.prioritized_experience_replay import PrioritizedExperienceReplay
 from .dqn_agent import DQNAgent
-from .vector_agent import VectorOffPolicyAgent
 
 
 class DistributionalDQNAgent(DQNAgent):
     NET = None
-    PER_REFUSAL = None            # None: the loss kernel's per-row errors are the priorities of a prioritized replay
 
-    def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
-        # not DQNAgent.__init__ (it builds a DQNNet), but its order: network, memory, exploration policy, buffers
-        VectorOffPolicyAgent.__init__(self, agent_parameters, environment, device, dist, use_graphs)
-        ep, net, alg = environment.p, self.ap.network_wrappers["main"], self.ap.algorithm
-        self.A, self.N = ep.num_actions, int(alg.atoms)
-        self.batch_size = net.batch_size
-        obs_shape = tuple(ep.observation_shape) + (self.stack,) if self.image else tuple(ep.observation_shape)
-        self.networks = {"main": self.NET(
-            self.device, obs_shape, self.A, self.N, **self._head_kwargs(alg),
-            activation=net.activation_function, embedder=net.embedder_scheme, middleware=net.middleware_scheme,
-            learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
-            adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon, seed=self.ap.seed or 0,
-            head_activation=net.heads_parameters[0].activation_function,
-            head_gradient_rescale=net.heads_parameters[0].rescale_gradient_from_head_by_factor,
-            clip_gradients=net.clip_gradients, noisy=self._parameter_noise())}
-        self._key_network_noise()
-        self.memory = self._make_memory(action_dim=None)
-        if self.PER_REFUSAL and isinstance(self.memory, PrioritizedExperienceReplay):
-            raise ValueError(self.PER_REFUSAL)
-        self.exploration_policy = self._make_exploration_policy()
-        self.actions = torch.zeros(self.n_env, dtype=torch.int32, device=self.device)
-        # the loss kernel's error per batch row: what update_priorities receives
-        self.td_errors = None if self.PER_REFUSAL else \
-            torch.zeros(self.batch_size, dtype=torch.float64, device=self.device)
-        self.loss_acc = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._finish_init()
+    def _check_parameters(self):
+        super()._check_parameters()
+        self.N = int(self.ap.algorithm.atoms)
+
+    def _network_arguments(self, net):
+        return (self.N,), dict(noisy=self.parameter_noise, **self._head_kwargs(self.ap.algorithm))
 
     # --------------------------------------------------------------------------------- acting
     def _q_buf(self):
@@ -73,11 +51,9 @@ class DistributionalDQNAgent(DQNAgent):
 
     def learn_from_batch(self, batch):
         """the reference agents' learn_from_batch (the subclass's text names the lines)."""
-        per = isinstance(self.memory, PrioritizedExperienceReplay)       # (only where td_errors exist: see __init__)
+        per = isinstance(self.memory, PrioritizedExperienceReplay)       # (only where td_errors exist: _has_td_errors)
         weights = batch.info("weight") if per else None
         self._run(("learn", per, False), lambda: self._learn_device(batch, weights))
         if per:
             self.memory.update_priorities(batch.info("idx"), self.td_errors)
-        loss = self.networks["main"].loss
-        self.signals = {"Loss": loss, "Grads (unclipped)": self.networks["main"].norm}
-        return loss
+        return self._loss_signals()

@@ -13,14 +13,14 @@ import numpy as np
 import torch
 
 from .. import _rlx
-from ..architectures.head_parameters import DuelingQHeadParameters, QHeadParameters
+from ..architectures.head_parameters import QHeadParameters
 from ..architectures.scheme_views import SchemeViews
 from ..core_types import DeviceBatch, EnvironmentSteps, RunPhase
 from ..exploration_policies.e_greedy import EGreedy, EGreedyParameters
 from ..exploration_policies.parameter_noise import ParameterNoise, ParameterNoiseParameters, network_is_noisy
 from ..memories.non_episodic.experience_replay import ExperienceReplayParameters
 from ..memories.non_episodic.prioritized_experience_replay import PrioritizedExperienceReplay
-from ..nn.networks import DQNNet
+from ..nn.networks import DQNNet, dqn_net_kwargs
 from ..schedules import LinearSchedule
 from .vector_agent import AlgorithmParameters, VectorOffPolicyAgent
 
@@ -68,32 +68,51 @@ class DQNAgentParameters(object):                        # dqn_agent.py:56-66
 
 
 class DQNAgent(VectorOffPolicyAgent):
+    """The one constructor of the DQN family.  A subclass states what differs: NET and _network_arguments (its network),
+    _check_parameters and _check_memory (what it refuses), PER_REFUSAL / _has_td_errors (its prioritized-replay policy)."""
     double_dqn = False
     SIGNAL_NAMES = VectorOffPolicyAgent.SIGNAL_NAMES + ["Q"]            # value_optimization_agent.py:36
+    NET = DQNNet
+    PER_REFUSAL = None            # a text: the agent refuses a prioritized replay memory with it; None: the loss launch's
+                                  # per-row errors are the memory's new priorities
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
+        # the order is load-bearing: the base constructor seeds the host generators, _finish_init seeds them again
         super().__init__(agent_parameters, environment, device, dist, use_graphs)
+        self._check_parameters()
         ep, net = environment.p, self.ap.network_wrappers["main"]
         self.A = ep.num_actions
         self.batch_size = net.batch_size
         obs_shape = tuple(ep.observation_shape) + (self.stack,) if self.image else tuple(ep.observation_shape)
-        self.networks = {"main": DQNNet(
-            self.device, obs_shape, self.A, activation=net.activation_function,
-            embedder=net.embedder_scheme, middleware=net.middleware_scheme,
-            learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
-            adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon,
-            replace_mse_with_huber_loss=net.replace_mse_with_huber_loss, seed=self.ap.seed or 0,
-            dueling=isinstance(net.heads_parameters[0], DuelingQHeadParameters),
-            head_activation=net.heads_parameters[0].activation_function,
-            head_gradient_rescale=net.heads_parameters[0].rescale_gradient_from_head_by_factor,
-            clip_gradients=net.clip_gradients, noisy=self._parameter_noise())}
+        args, kwargs = self._network_arguments(net)
+        self.networks = {"main": self.NET(self.device, obs_shape, self.A, *args, **kwargs,
+                                          **dqn_net_kwargs(net, self.ap.seed or 0))}
         self._key_network_noise()
         self.memory = self._make_memory(action_dim=None)
+        self._check_memory()
         self.exploration_policy = self._make_exploration_policy()
         self.actions = torch.zeros(self.n_env, dtype=torch.int32, device=self.device)
-        self.td_errors = torch.zeros(self.batch_size, dtype=torch.float64, device=self.device)
-        self.loss_acc = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.td_errors = torch.zeros(self.batch_size, dtype=torch.float64, device=self.device) \
+            if self._has_td_errors() else None
         self._finish_init()
+
+    def _check_parameters(self):
+        """what the agent refuses before anything is built, and what of the parameters the network's arguments need
+        (here: is the exploration policy ParameterNoise?)"""
+        self._parameter_noise()
+
+    def _network_arguments(self, net):
+        """-> (positional arguments behind n_actions, keywords next to dqn_net_kwargs) of NET's constructor"""
+        return (), dict(noisy=self.parameter_noise)
+
+    def _check_memory(self):
+        if self.PER_REFUSAL and isinstance(self.memory, PrioritizedExperienceReplay):
+            raise ValueError(self.PER_REFUSAL)
+
+    def _has_td_errors(self):
+        """does the loss launch leave an error per batch row in self.td_errors?  They are a prioritized replay's new
+        priorities, so not where the agent refuses one."""
+        return not self.PER_REFUSAL
 
     # ------------------------------------------------------------------------- ParameterNoise
     def _parameter_noise(self):
@@ -103,7 +122,6 @@ class DQNAgent(VectorOffPolicyAgent):
         if isinstance(self.ap.exploration, ParameterNoiseParameters) != noisy:
             raise ValueError("noisy dense layers and the ParameterNoise exploration policy come together")
         self.parameter_noise = noisy
-        return noisy
 
     def _key_network_noise(self):
         """the key of the noisy layers' generator, as for noise_source = "device": (noise seed, rank)"""
@@ -184,11 +202,6 @@ class DQNAgent(VectorOffPolicyAgent):
             net.ctx.per_tail = None
             _rlx.lib().per_update(*per_ride, _rlx.current_stream())
 
-    def _grad_scale(self):
-        netp = self.ap.network_wrappers["main"]
-        return self.dist.grad_scale(netp.scale_down_gradients_by_number_of_workers_for_sync_training) \
-            if self.dist else 1.0
-
     def learn_from_batch(self, batch):
         """DQNAgent.learn_from_batch (dqn_agent.py:81-113)."""
         per = isinstance(self.memory, PrioritizedExperienceReplay)
@@ -200,9 +213,13 @@ class DQNAgent(VectorOffPolicyAgent):
         self._run(("learn", per, ride is not None), lambda: self._learn_device(batch, weights, ride))
         if per and ride is None:
             self.memory.update_priorities(batch.info("idx"), self.td_errors)
-        loss = self.networks["main"].loss
-        self.signals = {"Loss": loss, "Grads (unclipped)": self.networks["main"].norm}
-        return loss
+        return self._loss_signals()
+
+    def _loss_signals(self, **more):
+        """the tail of every learn_from_batch of the family: the update's signals, -> its loss (a device scalar)"""
+        net = self.networks["main"]
+        self.signals = {"Loss": net.loss, "Grads (unclipped)": net.norm, **more}
+        return net.loss
 
 
     # ------------------------------------------------------------- one staged record + one graph per env-step
@@ -343,8 +360,7 @@ class DQNAgent(VectorOffPolicyAgent):
             if end in target_after:
                 self.update_target_networks(alg.rate_for_copying_weights_to_target)
             start = end
-        loss = self.networks["main"].loss
-        self.signals = {"Loss": loss, "Grads (unclipped)": self.networks["main"].norm}
+        loss = self._loss_signals()
         return loss if k else None
 
 

@@ -18,11 +18,10 @@ import torch
 from ..architectures.head_parameters import NAFHeadParameters
 from ..architectures.scheme_views import SchemeViews
 from ..core_types import EnvironmentSteps, GradientClippingMethod
-from ..exploration_policies.additive_noise import AdditiveNoise
-from ..exploration_policies.ou_process import OUProcess, OUProcessParameters
+from ..exploration_policies.ou_process import OUProcessParameters
 from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
 from ..nn.networks import NAFNet
-from .vector_agent import AlgorithmParameters, VectorOffPolicyAgent
+from .vector_agent import AlgorithmParameters, BoxActionAgent, VectorOffPolicyAgent
 
 
 class NAFNetworkParameters(SchemeViews):                  # naf_agent.py:34-43 + NetworkParameters defaults
@@ -66,8 +65,7 @@ class NAFAgentParameters(object):                         # naf_agent.py:54-63
         return 'coach_amd.agents.naf_agent:NAFAgent'
 
 
-class NAFAgent(VectorOffPolicyAgent):
-    continuous = True
+class NAFAgent(BoxActionAgent):
     # value_optimization_agent.py:36 ("Q"), naf_agent.py:70-74
     SIGNAL_NAMES = VectorOffPolicyAgent.SIGNAL_NAMES + ["Q", "L", "Advantage", "Action", "V", "TD targets"]
 
@@ -78,10 +76,9 @@ class NAFAgent(VectorOffPolicyAgent):
         if self.image:
             raise ValueError('NAF works only for continuous control problems (vector observations)')
         ep, net = environment.p, self.ap.network_wrappers["main"]
-        self.obs_dim, self.A = int(ep.observation_shape[0]), int(ep.action_dim)
+        self.obs_dim = int(ep.observation_shape[0])
+        self._set_action_bounds(ep)
         self.batch_size = net.batch_size
-        self.low = np.broadcast_to(np.asarray(ep.action_low, dtype=np.float32), (self.A,)).copy()
-        self.high = np.broadcast_to(np.asarray(ep.action_high, dtype=np.float32), (self.A,)).copy()
         scale = np.maximum(np.abs(self.low), np.abs(self.high))                         # BoxActionSpace.max_abs_range
         method = getattr(net, "gradients_clipping_method", GradientClippingMethod.ClipByGlobalNorm)
         if net.clip_gradients and method == GradientClippingMethod.ClipByNorm:
@@ -101,18 +98,7 @@ class NAFAgent(VectorOffPolicyAgent):
         self.td_targets = torch.zeros(B, dtype=torch.float32, device=dev)
         self._finish_init()
 
-    def _make_exploration(self):
-        p = self.ap.exploration
-        cls = OUProcess if isinstance(p, OUProcessParameters) else AdditiveNoise
-        return cls(self.low, self.high, self.n_env, self.device, p)
-
     # --------------------------------------------------------------------------------- acting
-    def random_actions(self):
-        """BoxActionSpace.sample (spaces.py:151-162): np.random.uniform(low, high, shape) per env."""
-        a = np.random.uniform(self.low, self.high, (self.n_env, self.A)).astype(np.float32)
-        self.actions.copy_(self._to_device("rand_act", a, torch.float32))
-        return self.actions
-
     def choose_action(self, states):
         """naf_agent.py:101-131: mu from the online network, the exploration policy's noise on it; with statistics
         enabled the head's values at u = mu (the reference feeds the network's own mu back as the action, :116-119)."""
@@ -130,23 +116,11 @@ class NAFAgent(VectorOffPolicyAgent):
         self._act_out = self.networks["main"].head_forward(states, self.n_env, tag="act", mu_out=self.mu,
                                                            with_signals=with_signals)
 
-    def handle_episode_ended(self):
-        ended = np.nonzero(self._episode_steps == 0)[0] if self._episode_just_ended else None
-        try:                                                              # Agent.reset_internal_state, per env
-            self.exploration_policy.reset(ended)
-        except TypeError:
-            self.exploration_policy.reset()
-
     # ------------------------------------------------------------------------------- training
-    def _scale(self):
-        netp = self.ap.network_wrappers["main"]
-        return self.dist.grad_scale(netp.scale_down_gradients_by_number_of_workers_for_sync_training) \
-            if self.dist else 1.0
-
     def _learn_device(self, b, mix=None):
         net = self.networks["main"]
         net.learn_from_batch(b._states["observation"], b._next_states["observation"], self.batch_size, b.actions(),
-                             b.rewards(), b.game_overs(), float(self.ap.algorithm.discount), self._scale(),
+                             b.rewards(), b.game_overs(), float(self.ap.algorithm.discount), self._grad_scale(),
                              sync=self if self.dist is not None else None, td_targets_out=self.td_targets,
                              mix_rate=mix)
 

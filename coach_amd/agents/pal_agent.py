@@ -12,14 +12,10 @@ dQ: csrc/pal.hip) -> backward -> TF1 Adam.
 MixedTargetDQNAgent is the part PALAgent shares with MixedMonteCarloAgent (mmc_agent.py): the network, the memory's
 type, what an update passes to the launch.
 """
-import torch
-
-from ..architectures.head_parameters import DuelingQHeadParameters
 from ..exploration_policies.parameter_noise import ParameterNoiseParameters, network_is_noisy
 from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplay, EpisodicExperienceReplayParameters
 from ..nn.networks import MixedTargetDQNNet
 from .dqn_agent import DQNAgent, DQNAgentParameters, DQNAlgorithmParameters
-from .vector_agent import VectorOffPolicyAgent
 
 
 class PALAlgorithmParameters(DQNAlgorithmParameters):                    # pal_agent.py:26-44
@@ -44,12 +40,12 @@ class PALAgentParameters(DQNAgentParameters):                            # pal_a
 class MixedTargetDQNAgent(DQNAgent):
     MODE = None              # MixedTargetDQNNet.learn_from_batch's mode
 
-    def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
-        # not DQNAgent.__init__ (it builds a DQNNet), but its order: network, memory, exploration policy, buffers
-        VectorOffPolicyAgent.__init__(self, agent_parameters, environment, device, dist, use_graphs)
+    NET = MixedTargetDQNNet
+
+    def _check_parameters(self):
         name = type(self).__name__
-        ep, net = environment.p, self.ap.network_wrappers["main"]
-        if isinstance(self.ap.exploration, ParameterNoiseParameters) or network_is_noisy(net):
+        if isinstance(self.ap.exploration, ParameterNoiseParameters) or \
+                network_is_noisy(self.ap.network_wrappers["main"]):
             raise ValueError("the ParameterNoise exploration policy (noisy dense layers) is not implemented for %s"
                              % name)
         if not isinstance(self.ap.memory, EpisodicExperienceReplayParameters):
@@ -61,24 +57,12 @@ class MixedTargetDQNAgent(DQNAgent):
             raise ValueError("%s reads the transitions' Monte Carlo returns (n_step_discounted_rewards), which the "
                              "hindsight replay does not provide: use EpisodicExperienceReplayParameters" % name)
         self.parameter_noise = False
-        self.A = ep.num_actions
-        self.batch_size = net.batch_size
-        obs_shape = tuple(ep.observation_shape) + (self.stack,) if self.image else tuple(ep.observation_shape)
-        head = net.heads_parameters[0]
-        self.networks = {"main": MixedTargetDQNNet(
-            self.device, obs_shape, self.A, activation=net.activation_function, embedder=net.embedder_scheme,
-            middleware=net.middleware_scheme, learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
-            adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon,
-            replace_mse_with_huber_loss=net.replace_mse_with_huber_loss, seed=self.ap.seed or 0,
-            dueling=isinstance(head, DuelingQHeadParameters), head_activation=head.activation_function,
-            head_gradient_rescale=head.rescale_gradient_from_head_by_factor, clip_gradients=net.clip_gradients)}
-        self.memory = self._make_memory(action_dim=None)           # (image observations: refused by the memory)
+
+    def _check_memory(self):                                        # (image observations: refused by the memory)
         assert isinstance(self.memory, EpisodicExperienceReplay)
-        self.exploration_policy = self._make_exploration_policy()
-        self.actions = torch.zeros(self.n_env, dtype=torch.int32, device=self.device)
-        self.td_errors = None
-        self.loss_acc = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._finish_init()
+
+    def _has_td_errors(self):
+        return False
 
     def _step_graph_ok(self):
         """the one-graph-per-env-step path of DQNAgent is declined: it draws from the flat replay and its update is

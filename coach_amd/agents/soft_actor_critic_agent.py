@@ -21,7 +21,7 @@ from ..core_types import EnvironmentSteps, RunPhase
 from ..memories.non_episodic.experience_replay import ExperienceReplayParameters
 from ..nn.actor_critic_nets import SACPolicyNet, SACQNet, SACValueNet
 from ..architectures.scheme_views import SchemeViews
-from .vector_agent import AlgorithmParameters, VectorOffPolicyAgent
+from .vector_agent import AlgorithmParameters, BoxActionAgent, VectorOffPolicyAgent
 
 
 class _SACNetParams(SchemeViews):
@@ -103,11 +103,10 @@ class SoftActorCriticAgentParameters(object):            # :129-141
         return 'coach_amd.agents.soft_actor_critic_agent:SoftActorCriticAgent'
 
 
-class SoftActorCriticAgent(VectorOffPolicyAgent):
+class SoftActorCriticAgent(BoxActionAgent):
     SIGNAL_NAMES = VectorOffPolicyAgent.SIGNAL_NAMES + [                  # soft_actor_critic_agent.py:151-162
         "Policy_mu_avg", "Policy_logsig", "Policy_logp_sampled", "Policy_grads_sumabs", "Q1", "TD err1", "Q2",
         "TD err2", "V_tgt_ns", "V_onl_ys", "actions"]
-    continuous = True
     NOISE_STREAMS = (1, 3)           # device noise: streams 1-3, the update's three normal draws
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
@@ -116,10 +115,9 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
             raise ValueError("SAC works only for continuous control problems")
         ep = environment.p
         pn, qn, vn = (self.ap.network_wrappers[k] for k in ("policy", "q", "v"))
-        self.obs_dim, self.A = int(ep.observation_shape[0]), int(ep.action_dim)
+        self.obs_dim = int(ep.observation_shape[0])
+        self._set_action_bounds(ep)
         self.batch_size = pn.batch_size
-        self.low = np.broadcast_to(np.asarray(ep.action_low, dtype=np.float32), (self.A,)).copy()
-        self.high = np.broadcast_to(np.asarray(ep.action_high, dtype=np.float32), (self.A,)).copy()
         seed, dev = self.ap.seed or 0, self.device
         adam = lambda n: (n.learning_rate, n.adam_optimizer_beta1, n.adam_optimizer_beta2, n.optimizer_epsilon)
         self.networks = OrderedDict([
@@ -144,11 +142,6 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
         self._finish_init()
 
     # --------------------------------------------------------------------------------- acting
-    def random_actions(self):
-        a = np.random.uniform(self.low, self.high, (self.n_env, self.A)).astype(np.float32)
-        self.actions.copy_(self._to_device("rand_act", a, torch.float32))
-        return self.actions
-
     def choose_action(self, states):
         """choose_action (:296-322): the squashed sample, or the (un-squashed) mean in TEST."""
         alg = self.ap.algorithm
@@ -171,11 +164,6 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
     # ------------------------------------------------------------------------------- training
     def _sync(self, net):
         self._allreduce(net.params.grads)
-
-    def _scale(self, name):
-        netp = self.ap.network_wrappers[name]
-        return self.dist.grad_scale(netp.scale_down_gradients_by_number_of_workers_for_sync_training) \
-            if self.dist else 1.0
 
     # The three networks' passes as parallel branches of the captured update (fork / join of side streams): the policy
     # chain, V's training pass and Q's training pass touch different networks until their losses meet.  Same calls,
@@ -212,7 +200,7 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
             if wg:
                 for name, net in (("policy", pol), ("q", q), ("v", v)):
                     self._sync(net)
-                    net.apply_gradients(self._scale(name), **({"with_norm": True} if name == "q" else
+                    net.apply_gradients(self._grad_scale(name), **({"with_norm": True} if name == "q" else
                                                               {"mix_rate": mix} if name == "v" else {}))
             return
         alg, B, s_ = self.ap.algorithm, self.batch_size, _rlx.current_stream
@@ -256,7 +244,7 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
             pol.backward(p_saved, B, logprob_mean_weight=1.0, action_weights=self.dq_da,
                          action_weight_scale=-1.0)
         self._sync(pol)
-        pol.apply_gradients(self._scale("policy"))                               # :229
+        pol.apply_gradients(self._grad_scale("policy"))                               # :229
 
         # ---- branch B: (4) V, train_on_batch on the targets computed in (2) (:250)
         import contextlib
@@ -274,7 +262,7 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
             self._sync(v)
             # a soft update of V's target due after this update rides in V's Adam pass — only when V_target(s') was
             # already evaluated above (paired pass); otherwise it is still needed unmixed below
-            v.apply_gradients(self._scale("v"), mix_rate=mix if obs2 is not None else None)
+            v.apply_gradients(self._grad_scale("v"), mix_rate=mix if obs2 is not None else None)
 
         # ---- branch C: (5) Q, y = r + (1 - done) gamma V_target(s') (:259-266), train_on_batch (:268)
         with (br.on(1) if br else contextlib.nullcontext()):
@@ -290,7 +278,7 @@ class SoftActorCriticAgent(VectorOffPolicyAgent):
             self._sync(q)
             if br:
                 br.after(q_weights_free)
-            q.apply_gradients(self._scale("q"), with_norm=True)
+            q.apply_gradients(self._grad_scale("q"), with_norm=True)
         if br:
             br.join()
 

@@ -155,7 +155,7 @@ class TD3Agent(DDPGAgent):
                                   critic.loss, s_)
         critic.train_backward(c_saved, self.td_targets, B, losses_done=True)
         self._sync(critic)
-        critic.apply_gradients(self._scale("critic"), with_norm=True, mix_rate=mix)
+        critic.apply_gradients(self._grad_scale("critic"), with_norm=True, mix_rate=mix)
         self._loss_total = critic.loss[critic.T]                 # written by the loss launch: no reduction launch
 
     def _critic_device(self, b, mix=None):
@@ -168,7 +168,7 @@ class TD3Agent(DDPGAgent):
             fused.critic_update(b, mix, write_grads=wg)
             if wg:
                 self._sync(critic)
-                critic.apply_gradients(self._scale("critic"), with_norm=True, mix_rate=mix)
+                critic.apply_gradients(self._grad_scale("critic"), with_norm=True, mix_rate=mix)
             self._loss_total = critic.loss[critic.T]
             self._agrad_merged = None
             return
@@ -190,7 +190,7 @@ class TD3Agent(DDPGAgent):
         _, c_saved = critic.forward(s, b.actions(), B, tag="train")
         critic.train_backward(c_saved, self.td_targets, B)
         self._sync(critic)
-        critic.apply_gradients(self._scale("critic"), with_norm=True, mix_rate=mix)
+        critic.apply_gradients(self._grad_scale("critic"), with_norm=True, mix_rate=mix)
         self._loss_total = None
 
     def _actor_device(self, b, mix=None):
@@ -201,7 +201,7 @@ class TD3Agent(DDPGAgent):
             fused.actor_update(b, mix, write_grads=wg)
             if wg:
                 self._sync(actor)
-                actor.apply_gradients(self._scale("actor"), mix_rate=mix)
+                actor.apply_gradients(self._grad_scale("actor"), mix_rate=mix)
             return
         B = self.batch_size
         s = b._states["observation"]
@@ -218,7 +218,7 @@ class TD3Agent(DDPGAgent):
             critic.action_gradient(c_saved, B, self.neg_action_grad, scale=-1.0)
             actor.backward(self._a_saved, self.neg_action_grad, B)
         self._sync(actor)
-        actor.apply_gradients(self._scale("actor"), mix_rate=mix)
+        actor.apply_gradients(self._grad_scale("actor"), mix_rate=mix)
 
     def _update_record_fields(self):
         if self.noise_source == "device":

@@ -359,6 +359,13 @@ class VectorOffPolicyAgent(GraphRunner):
             kw["mask_column"] = True
         return ExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling, **kw)
 
+    def _grad_scale(self, name="main"):
+        """what network `name`'s gradients are scaled by before its Adam step (data parallel: 1 / workers where the
+        network's parameters ask for it)"""
+        netp = self.ap.network_wrappers[name]
+        return self.dist.grad_scale(netp.scale_down_gradients_by_number_of_workers_for_sync_training) \
+            if self.dist else 1.0
+
     def _to_device(self, key, array, dtype):
         """host draws -> a static device buffer through a ring of pinned staging slots."""
         return self._stagers.push(key, array, dtype)
@@ -880,3 +887,37 @@ class VectorOffPolicyAgent(GraphRunner):
         self.memory.check_status()
         for net in self.networks.values():
             net.check_status()
+
+
+class BoxActionAgent(VectorOffPolicyAgent):
+    """What the agents of a box action space share (DDPG / TD3, NAF, SAC): the bounds, the heat-up actions, and — for
+    those that explore with a policy object — its construction and its reset at an episode's end."""
+    continuous = True
+
+    def _set_action_bounds(self, ep):
+        """self.A, and self.low / self.high [A] from the environment's scalar or per-dimension bounds"""
+        self.A = int(ep.action_dim)
+        self.low = np.broadcast_to(np.asarray(ep.action_low, dtype=np.float32), (self.A,)).copy()
+        self.high = np.broadcast_to(np.asarray(ep.action_high, dtype=np.float32), (self.A,)).copy()
+
+    def _make_exploration(self):
+        from ..exploration_policies.additive_noise import AdditiveNoise
+        from ..exploration_policies.ou_process import OUProcess, OUProcessParameters
+        p = self.ap.exploration
+        cls = OUProcess if isinstance(p, OUProcessParameters) else AdditiveNoise
+        return cls(self.low, self.high, self.n_env, self.device, p)
+
+    def random_actions(self):
+        """BoxActionSpace.sample (spaces.py:151-162): np.random.uniform(low, high, shape) per env."""
+        a = np.random.uniform(self.low, self.high, (self.n_env, self.A)).astype(np.float32)
+        self.actions.copy_(self._to_device("rand_act", a, torch.float32))
+        return self.actions
+
+    def handle_episode_ended(self):
+        pol = getattr(self, "exploration_policy", None)           # (SAC has none)
+        if hasattr(pol, "reset"):
+            ended = np.nonzero(self._episode_steps == 0)[0] if self._episode_just_ended else None
+            try:                                                              # Agent.reset_internal_state, per env
+                pol.reset(ended)
+            except TypeError:
+                pol.reset()

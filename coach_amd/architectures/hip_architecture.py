@@ -36,9 +36,8 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import ClippedPPONet, DQNNet
+from ..nn.networks import ClippedPPONet, DQNNet, dqn_net_kwargs
 from .architecture import Architecture
-from .head_parameters import DuelingQHeadParameters
 
 
 def squeeze_list(var):
@@ -268,16 +267,8 @@ class QArchitecture(HipArchitecture):
     """embedder -> FC middleware -> QHead | DuelingQHead; regression against explicit [B, A] targets."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        head = np_.heads_parameters[0]
-        return DQNNet(
-            self.device, tuple(int(x) for x in spaces.state['observation'].shape), len(spaces.action.actions),
-            activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
-            learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
-            adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
-            replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss, seed=seed,
-            dueling=isinstance(head, DuelingQHeadParameters), head_activation=head.activation_function,
-            head_gradient_rescale=head.rescale_gradient_from_head_by_factor,
-            clip_gradients=getattr(np_, "clip_gradients", None))
+        return DQNNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
+                      len(spaces.action.actions), **dqn_net_kwargs(np_, seed))
 
     def _queue(self, inputs, tag):
         obs, B = self._observation(inputs)

@@ -101,8 +101,8 @@ class FusedTD3(object):
     def _fill(self, b, mix):
         a, d = self.agent, self.desc
         actor, critic = a.networks["actor"], a.networks["critic"]
-        d.actor = fused_net(actor, a._scale("actor"), mix)
-        d.critic = fused_net(critic, a._scale("critic"), mix, with_norm=True)
+        d.actor = fused_net(actor, a._grad_scale("actor"), mix)
+        d.critic = fused_net(critic, a._grad_scale("critic"), mix, with_norm=True)
         d.obs = b._states["observation"].data_ptr()
         d.next_obs = b._next_states["observation"].data_ptr()
         d.actions, d.rewards, d.game_overs = b.actions().data_ptr(), b.rewards().data_ptr(), b.game_overs().data_ptr()
@@ -174,9 +174,9 @@ class FusedSAC(object):
     def update(self, b, mix=None, write_grads=False):
         a, d = self.agent, self.desc
         pol, q, v = (a.networks[k] for k in ("policy", "q", "v"))
-        d.policy = fused_net(pol, a._scale("policy"))
-        d.q = fused_net(q, a._scale("q"), with_norm=True)
-        d.v = fused_net(v, a._scale("v"), mix)
+        d.policy = fused_net(pol, a._grad_scale("policy"))
+        d.q = fused_net(q, a._grad_scale("q"), with_norm=True)
+        d.v = fused_net(v, a._grad_scale("v"), mix)
         d.obs = b._states["observation"].data_ptr()
         d.next_obs = b._next_states["observation"].data_ptr()
         d.actions, d.rewards, d.game_overs = b.actions().data_ptr(), b.rewards().data_ptr(), b.game_overs().data_ptr()

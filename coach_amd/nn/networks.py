@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import _rlx
+from ..architectures.head_parameters import DuelingQHeadParameters
 from . import graph as G
 
 IMAGE_EMBEDDER = {"Medium": [(32, 8, 4), (64, 4, 2), (64, 3, 1)], "Shallow": [(32, 3, 1)]}
@@ -383,6 +384,19 @@ class ClippedPPONet(_NetBase):
         return self.scalars
 
 
+def dqn_net_kwargs(np_, seed):
+    """a DQN-family network's parameters object (DQNNetworkParameters and its subclasses) -> the keywords of DQNNet's
+    constructor; `noisy` and a subclass's own arguments (atoms, heads) are the caller's."""
+    head = np_.heads_parameters[0]
+    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
+                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
+                adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
+                replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss, seed=seed,
+                dueling=isinstance(head, DuelingQHeadParameters), head_activation=head.activation_function,
+                head_gradient_rescale=head.rescale_gradient_from_head_by_factor,
+                clip_gradients=getattr(np_, "clip_gradients", None))
+
+
 class DQNNet(_NetBase):
     """DQNNetworkParameters (agents/dqn_agent.py:43-56): embedder -> FC middleware -> QHead;
     MSE or Huber loss, importance weights from prioritized replay."""
@@ -467,43 +481,39 @@ class DQNNet(_NetBase):
                               self.noise_seed, self.noise_rank, self.ctx.stream)
 
     # ---------------------------------------------------------------- fused small-MLP update (one launch)
-    def _fused_mlp_setup(self):
-        """obs -> Dense(relu) -> Dense(relu) -> Dense(A) Q networks (CartPole_DQN's shape) qualify for
-        rlx_mlp_dqn_update: the whole learn_from_batch in ONE launch (csrc/mlp_fused.hip).
-        DQNNet.FUSED_MLP = False keeps the layer-by-layer path (the tests cross-check the two)."""
-        if not self.FUSED_MLP or self.image or self.dueling:
-            return None
+    def _small_mlp(self):
+        """obs -> Dense(relu) -> Dense(relu) -> head (CartPole_DQN's shape), which the one-launch kernels of
+        csrc/mlp_fused.hip take -> ((obs_dim, h1, h2), the six offsets of w1, b1, w2, b2, w3, b3 in the flat buffer),
+        or None for any other network."""
         ls = self.torso.layers
-        if len(ls) != 2 or any(not isinstance(l, G.Dense) or l.act != "relu" or l.T != 1 for l in ls):
+        if self.image or self.dueling or len(ls) != 2 or \
+                any(not isinstance(l, G.Dense) or l.act != "relu" or l.T != 1 for l in ls):
             return None
-        if self.head_gradient_rescale != 1.0 or self.clip_gradients:
+        offs = tuple(self.params.entries[n][0] for l in (ls[0], ls[1], self.q_head) for n in (l.kname, l.bname))
+        return (ls[0].K, ls[0].N, ls[1].N), offs
+
+    def _fused_mlp_setup(self):
+        """small MLPs qualify for rlx_mlp_dqn_update: the whole learn_from_batch in ONE launch.
+        DQNNet.FUSED_MLP = False keeps the layer-by-layer path (the tests cross-check the two)."""
+        mlp = self._small_mlp() if self.FUSED_MLP else None
+        if mlp is None or self.head_gradient_rescale != 1.0 or self.clip_gradients:
             return None
-        d0, h1, h2 = ls[0].K, ls[0].N, ls[1].N
-        if not self.lib.rlx_mlp_dqn_supported(1, d0, h1, h2, self.A):
+        dims, offs = mlp
+        if not self.lib.rlx_mlp_dqn_supported(1, *dims, self.A):
             return None
         import ctypes
         n = ctypes.c_longlong()
-        self.lib.mlp_dqn_workspace_floats(h1, h2, self.A, ctypes.byref(n))
-        off = lambda name: self.params.entries[name][0]
-        return dict(dims=(d0, h1, h2), ws=torch.zeros(n.value, dtype=torch.float32, device=self.device),
-                    sync=torch.zeros(4, dtype=torch.int32, device=self.device),
-                    offs=(off(ls[0].kname), off(ls[0].bname), off(ls[1].kname), off(ls[1].bname),
-                          off(self.q_head.kname), off(self.q_head.bname)))
+        self.lib.mlp_dqn_workspace_floats(dims[1], dims[2], self.A, ctypes.byref(n))
+        return dict(dims=dims, ws=torch.zeros(n.value, dtype=torch.float32, device=self.device),
+                    sync=torch.zeros(4, dtype=torch.int32, device=self.device), offs=offs)
 
     def _act_setup(self):
         """the same network shape qualifies for rlx_mlp_q_act: Q(s) of a few envs + the epsilon-greedy choice as one
         launch (DQNNet.FUSED_ACT = False keeps the layer launches + rlx_egreedy)."""
-        if not self.FUSED_ACT or self.image or self.dueling:
+        mlp = self._small_mlp() if self.FUSED_ACT else None
+        if mlp is None or getattr(self.q_head, "act", None) is not None:
             return None
-        ls = self.torso.layers
-        if len(ls) != 2 or any(not isinstance(l, G.Dense) or l.act != "relu" or l.T != 1 for l in ls):
-            return None
-        if getattr(self.q_head, "act", None) is not None:
-            return None
-        off = lambda name: self.params.entries[name][0]
-        return dict(dims=(ls[0].K, ls[0].N, ls[1].N),
-                    offs=(off(ls[0].kname), off(ls[0].bname), off(ls[1].kname), off(ls[1].bname),
-                          off(self.q_head.kname), off(self.q_head.bname)))
+        return dict(dims=mlp[0], offs=mlp[1])
 
     def can_act_fused(self, n_env):
         a = self._act
@@ -668,6 +678,18 @@ class DQNNet(_NetBase):
             sync.all_reduce_sum(self.params.grads)
         self.apply_gradients(grad_scale, with_norm=not clipped)
 
+    def _update(self, obs, next_obs, B, states_pair, grad_scale, sync, head_loss):
+        """One update of every network of the family: the target's head output on s' and the online one on s (two towers
+        of the same launches where the replay collated states_pair), head_loss(acts, q, saved, q_next, dq) — the
+        class's own launch, which leaves the loss in self.loss and the head output's gradient in dq — backward, clip,
+        Adam.  Passes that only the class's targets read (the online selector on s') run before this is called.
+        head_loss returns true when its launch ran the head's backward pass as well (DQNNet's one-launch form)."""
+        acts, q, saved, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
+        if not head_loss(acts, q, saved, q_next, q.ensure_grad()):
+            self._backward_from_q(acts, q, saved, B)
+        self._apply_update(grad_scale, sync)
+        return self.loss
+
     def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount,
                          importance_weights=None, td_errors=None, double_dqn=False, grad_scale=1.0,
                          sync=None, states_pair=None):
@@ -681,45 +703,47 @@ class DQNNet(_NetBase):
                                      double_dqn, grad_scale)
         sel = self.q_values(next_obs, B, tag="next_o", noise_pass="online_next").data.view(B, self.A) \
             if double_dqn else None
-        acts, q, saved, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
-        dq = q.ensure_grad()
-        # TD targets, |TD errors|, QHead loss and its gradient in one launch (importance weights are
-        # the fp64 weights of the prioritized replay, or fp32 -> converted, or None)
-        w = importance_weights
-        if w is not None and w.dtype != torch.float64:
-            w = w.double()
-        feat = acts[-1]
-        if self.HEAD_LOSS_BACKWARD_ONE_LAUNCH and not self.dueling and self.head_gradient_rescale == 1.0 and \
-                self.q_head.T == 1 and self.A <= G.SMALL_N and B * self.A <= 1024 and B <= 256 and not feat.u8 and \
-                feat.towers == 1 and not self.noisy:
-            # TD targets, |TD errors|, loss, dQ AND the Q head's backward pass (dW, db, dz of the last dense layer) in one
-            # launch (rlx_dqn_head_loss_backward): what the two calls of the else branch compute, bit for bit
-            import ctypes
-            prob = _rlx.SmallDenseProblem()
-            G._small_backward_problem(prob, self.q_head, feat, q)
-            self.lib.dqn_head_loss_backward(ctypes.byref(prob), q.data, self.A, q_next, sel, self.A, actions, rewards,
-                                            game_overs, w, float(discount), B, self.A, int(self.huber), 1.0, td_errors,
-                                            self.loss, self.status, ctx.stream)
-            self.torso.backward(ctx, acts)
-        else:
+
+        def head_loss(acts, q, saved, q_next, dq):
+            # TD targets, |TD errors|, QHead loss and its gradient in one launch (importance weights are
+            # the fp64 weights of the prioritized replay, or fp32 -> converted, or None)
+            w = importance_weights
+            if w is not None and w.dtype != torch.float64:
+                w = w.double()
+            feat = acts[-1]
+            if self.HEAD_LOSS_BACKWARD_ONE_LAUNCH and not self.dueling and self.head_gradient_rescale == 1.0 and \
+                    self.q_head.T == 1 and self.A <= G.SMALL_N and B * self.A <= 1024 and B <= 256 and not feat.u8 and \
+                    feat.towers == 1 and not self.noisy:
+                # TD targets, |TD errors|, loss, dQ AND the Q head's backward pass (dW, db, dz of the last dense layer) in
+                # one launch (rlx_dqn_head_loss_backward): what the two calls of the other branch compute, bit for bit
+                import ctypes
+                prob = _rlx.SmallDenseProblem()
+                G._small_backward_problem(prob, self.q_head, feat, q)
+                self.lib.dqn_head_loss_backward(ctypes.byref(prob), q.data, self.A, q_next, sel, self.A, actions, rewards,
+                                                game_overs, w, float(discount), B, self.A, int(self.huber), 1.0, td_errors,
+                                                self.loss, self.status, ctx.stream)
+                self.torso.backward(ctx, acts)
+                return True
             self.lib.dqn_head_loss(q.data, self.A, q_next, sel, self.A, actions, rewards, game_overs, w,
                                    float(discount), B, self.A, int(self.huber), 1.0, dq, self.A, td_errors,
                                    None, self.A, self.loss, self.status, ctx.stream)
-            self._backward_from_q(acts, q, saved, B)
-        self._apply_update(grad_scale, sync)
-        return self.loss
+        return self._update(obs, next_obs, B, states_pair, grad_scale, sync, head_loss)
 
 
-class DistributionalDQNNet(DQNNet):
-    """The DQN torso (vector or image) under a head that outputs N atoms per action: ONE Dense(feat, A * atoms) whose
-    output column a * atoms + j is atom j of action a.  Forward and backward go through the torso's and the Dense
-    layer's generic launches; what the atoms mean, and so the loss and its gradient, is the subclass's `_head_loss`
-    (one launch, csrc/qr_dqn.hip or csrc/c51.hip; their shared parts: csrc/distributional_head.hpp).  The fused
-    small-MLP update / acting kernels and the Q head inside the torso's last launch are DQN's alone: with these flags
-    _fused and _act stay None and the head's forward is a launch of its own."""
+class _OwnHeadLossDQNNet(DQNNet):
+    """A DQN torso under a head with its own loss launch.  The fused small-MLP update computes DQN's targets, the fused
+    acting kernel reduces DQN's head, and the head inside the torso's last launch is the plain Q head: all three are
+    DQN's alone.  With these flags _fused and _act stay None and the head's forward is a launch of its own."""
     FUSED_MLP = False
     FUSED_ACT = False
     HEAD_FORWARD_WITH_TORSO = False
+
+
+class DistributionalDQNNet(_OwnHeadLossDQNNet):
+    """The DQN torso (vector or image) under a head that outputs N atoms per action: ONE Dense(feat, A * atoms) whose
+    output column a * atoms + j is atom j of action a.  Forward and backward go through the torso's and the Dense
+    layer's generic launches; what the atoms mean, and so the loss and its gradient, is the subclass's `_head_loss`
+    (one launch, csrc/qr_dqn.hip or csrc/c51.hip; their shared parts: csrc/distributional_head.hpp)."""
 
     def __init__(self, device, obs_shape, n_actions, atoms, **kw):
         kw.pop("replace_mse_with_huber_loss", None)
@@ -738,12 +762,9 @@ class DistributionalDQNNet(DQNNet):
         """the agents' learn_from_batch, all on device: the target's head output on s' and the online one on s (two
         towers of the same launches where the replay collated states_pair), _head_loss, backward, Adam.
         head_outs: the optional outputs of the subclass's _head_loss, by keyword."""
-        acts, q, _, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
-        dq = q.ensure_grad()
-        self._head_loss(q.data, q_next, dq, actions, rewards, game_overs, float(discount), B, **head_outs)
-        self._backward_from_q(acts, q, None, B)
-        self._apply_update(grad_scale, sync)
-        return self.loss
+        def head_loss(acts, q, saved, q_next, dq):
+            self._head_loss(q.data, q_next, dq, actions, rewards, game_overs, float(discount), B, **head_outs)
+        return self._update(obs, next_obs, B, states_pair, grad_scale, sync, head_loss)
 
 
 class QRDQNNet(DistributionalDQNNet):
@@ -805,16 +826,12 @@ class _HeadCopiesDense(G.Dense):
         self.params.w(self.kname, 0).copy_(torch.from_numpy(np.ascontiguousarray(w)))
 
 
-class BootstrappedDQNNet(DQNNet):
+class BootstrappedDQNNet(_OwnHeadLossDQNNet):
     """BootstrappedDQNNetworkParameters (agents/bootstrapped_dqn_agent.py:26-30): the DQN torso under K copies of the
     QHead (num_output_head_copies), held as ONE Dense(feat, K * A) whose output column h * A + a is action a of head h;
     rescale_gradient_from_head_by_factor = 1 / K acts on what flows from the heads into the torso (the head's own
     weights get the full gradient).  Forward and backward go through the generic launches; the K masked losses and
-    their gradient are one launch (rlx_bootstrapped_dqn_head_loss, csrc/bootstrapped_dqn.hip).  The fused small-MLP
-    kernels and the head inside the torso's last launch are DQN's alone."""
-    FUSED_MLP = False
-    FUSED_ACT = False
-    HEAD_FORWARD_WITH_TORSO = False
+    their gradient are one launch (rlx_bootstrapped_dqn_head_loss, csrc/bootstrapped_dqn.hip)."""
     MAX_HEADS = 32
 
     def __init__(self, device, obs_shape, n_actions, heads, dueling=False, noisy=False, **kw):
@@ -843,30 +860,24 @@ class BootstrappedDQNNet(DQNNet):
         """BootstrappedDQNAgent.learn_from_batch (agents/bootstrapped_dqn_agent.py:57-86), all on device: online on
         s' (the selector), target on s' and online on s, the K masked head losses, backward, Adam.
         masks: int32 [B], bit h = the transition trains head h."""
-        sel = self.head_output(next_obs, B, tag="next_o").data.view(B, self.KA)
-        acts, q, _, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
-        dq = q.ensure_grad()
-        self.last_q, self.last_q_next, self.last_q_sel = q.data, q_next, sel     # (views of the pass's buffers)
         KA = self.KA
-        self.lib.bootstrapped_dqn_head_loss(q.data, KA, q_next, sel, KA, actions, rewards, game_overs, masks,
-                                            float(discount), B, self.K, self.A, int(self.huber), 1.0, dq, KA,
-                                            self.partials, self.ticket, self.loss, self.status, self.head_losses,
-                                            td_targets_out, target_actions_out, self.ctx.stream)
-        self._backward_from_q(acts, q, None, B)
-        self._apply_update(grad_scale, sync)
-        return self.loss
+        sel = self.head_output(next_obs, B, tag="next_o").data.view(B, KA)
+
+        def head_loss(acts, q, saved, q_next, dq):
+            self.last_q, self.last_q_next, self.last_q_sel = q.data, q_next, sel     # (views of the pass's buffers)
+            self.lib.bootstrapped_dqn_head_loss(q.data, KA, q_next, sel, KA, actions, rewards, game_overs, masks,
+                                                float(discount), B, self.K, self.A, int(self.huber), 1.0, dq, KA,
+                                                self.partials, self.ticket, self.loss, self.status, self.head_losses,
+                                                td_targets_out, target_actions_out, self.ctx.stream)
+        return self._update(obs, next_obs, B, states_pair, grad_scale, sync, head_loss)
 
 
-class MixedTargetDQNNet(DQNNet):
+class MixedTargetDQNNet(_OwnHeadLossDQNNet):
     """The DQN network (plain or dueling head) of the agents whose TD target mixes the Double-DQN target with other
     estimates: PALAgent (agents/pal_agent.py:70-111, the advantage-learning correction from the target network on s
     and the Monte Carlo return) and MixedMonteCarloAgent (agents/mmc_agent.py:57-83, the Monte Carlo return).  The
     passes are DQN's; the targets, the head's loss and its gradient are one launch (rlx_mixed_target_head_loss,
-    csrc/pal.hip).  The fused small-MLP update computes DQN targets, so the fused kernels and the head inside the
-    torso's last launch stay DQN's alone."""
-    FUSED_MLP = False
-    FUSED_ACT = False
-    HEAD_FORWARD_WITH_TORSO = False
+    csrc/pal.hip)."""
     MODES = ("pal", "mmc")
 
     def __init__(self, device, obs_shape, n_actions, noisy=False, **kw):
@@ -886,16 +897,14 @@ class MixedTargetDQNNet(DQNNet):
         sel = self.q_values(next_obs, B, tag="next_o", noise_pass="online_next").data.view(B, A)
         cur = self.q_values(obs, B, use_target=True, tag="cur_t", noise_pass="target").data.view(B, A) \
             if mode == "pal" else None
-        acts, q, saved, q_next = self._online_and_target_forward(obs, next_obs, B, states_pair)
-        dq = q.ensure_grad()
-        self.last_q, self.last_q_cur, self.last_q_next, self.last_q_sel = q.data, cur, q_next, sel    # (views)
-        self.lib.mixed_target_head_loss(q.data, A, cur, q_next, sel, A, actions, rewards, game_overs, total_returns,
-                                        float(discount), float(pal_alpha), int(bool(persistent)), float(mixing_rate),
-                                        B, A, int(self.huber), 1.0, dq, A, td_targets_out, A, self.loss, self.status,
-                                        self.ctx.stream)
-        self._backward_from_q(acts, q, saved, B)
-        self._apply_update(grad_scale, sync)
-        return self.loss
+
+        def head_loss(acts, q, saved, q_next, dq):
+            self.last_q, self.last_q_cur, self.last_q_next, self.last_q_sel = q.data, cur, q_next, sel    # (views)
+            self.lib.mixed_target_head_loss(q.data, A, cur, q_next, sel, A, actions, rewards, game_overs, total_returns,
+                                            float(discount), float(pal_alpha), int(bool(persistent)),
+                                            float(mixing_rate), B, A, int(self.huber), 1.0, dq, A, td_targets_out, A,
+                                            self.loss, self.status, self.ctx.stream)
+        return self._update(obs, next_obs, B, states_pair, grad_scale, sync, head_loss)
 
 
 class NAFNet(_NetBase):
