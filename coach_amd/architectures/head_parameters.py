@@ -66,3 +66,14 @@ class NAFHeadParameters(HeadParameters):
     def __init__(self, activation_function='tanh', name='naf_head_params', rescale_gradient_from_head_by_factor=1.0,
                  loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class PolicyHeadParameters(HeadParameters):
+    """PolicyHeadParameters (head_parameters.py:162-169): for a discrete action space one Dense layer of A policy values
+    ('fc') under a softmax (heads/policy_head.py:89-100; the activation is the continuous branch's, which has no device
+    form).  The loss -mean(log pi(a) * advantage) and the entropy regularisation come from rlx_pg_head_loss."""
+    head_type = "PolicyHead"
+
+    def __init__(self, activation_function='tanh', name='policy_head_params', rescale_gradient_from_head_by_factor=1.0,
+                 loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

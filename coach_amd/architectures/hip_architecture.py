@@ -22,7 +22,10 @@ the calls of architecture.py:26-237 and tensorflow_components/architecture.py:31
     [min(Q1, Q2), its mean], outputs=[q_head.q1_output, q_head.q2_output],
     gradients_wrt_inputs[1]['output_0_0'], train_on_batch with q1_loss / q2_loss fetches) and the value
     network (`SACValueNetworkParameters`).  Gradients of the policy network are handed out as a list of
-    per-variable tensors, because the agent text combines them variable by variable.
+    per-variable tensors, because the agent text combines them variable by variable;
+  * Policy Gradients (`PolicyGradientNetworkParameters`): embedder -> FC middleware -> discrete PolicyHead, fed the way
+    PolicyGradientsAgent.learn_from_batch feeds it (policy_gradients_agent.py:128-130): inputs 'observation' and
+    'output_0_0' = actions, targets = the rescaled returns; predict -> the action probabilities.
 
 One device network (`coach_amd.nn.networks.DQNNet`) holds the online and the target weights in one
 allocation; the `…/online` and `…/target` HipArchitecture objects of a NetworkWrapper are two views of
@@ -36,7 +39,7 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import ClippedPPONet, DQNNet, dqn_net_kwargs
+from ..nn.networks import ClippedPPONet, DQNNet, PolicyGradientNet, dqn_net_kwargs, policy_gradient_net_kwargs
 from .architecture import Architecture
 
 
@@ -592,7 +595,52 @@ class SACValueArchitecture(HipArchitecture):
         return total, [total], float(net.norm.item()), []
 
 
-_BY_PARAMETER_CLASS = {"SACPolicyNetworkParameters": SACPolicyArchitecture,
+# ========================================================================== Policy Gradients
+class PolicyGradientArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> discrete PolicyHead, fed the way PolicyGradientsAgent.learn_from_batch feeds it
+    (policy_gradients_agent.py:128-130): inputs 'observation' and 'output_0_0' = actions, targets = the rescaled
+    returns (the head's `advantages` placeholder, fp32).  predict -> [action probabilities (B, A)]."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        if not hasattr(spaces.action, "actions"):
+            raise ValueError("the continuous PolicyHead (a Box action space) is not served: the policy-gradient "
+                             "network has the discrete head only")
+        return PolicyGradientNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
+                                 len(spaces.action.actions), **policy_gradient_net_kwargs(np_, agent_parameters.algorithm,
+                                                                                          seed))
+
+    def _handles(self):
+        self.inputs = ['observation', 'output_0_0']
+        self.output_heads = [_HeadFetches(0, ['entropy', 'output'])]
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        net = self.net
+        z = net.policy_values(obs, B, tag="%s_%d" % (tag, B)).data.view(B, net.A)
+        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
+        net.lib.softmax(z, net.A, B, net.A, probs, net.A, _rlx.current_stream())
+        return [probs]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        obs, B = self._observation(inputs)
+        if 'output_0_0' not in inputs:
+            raise ValueError("the policy head needs the input output_0_0 (the actions)")
+        actions = self._to_device(inputs['output_0_0'], torch.int32).reshape(-1).contiguous()
+        if actions.numel() != B:
+            raise ValueError("output_0_0 must hold one action per sample")
+        advantages = self._per_sample(targets, B, "targets (the rescaled returns)")
+        net.window_gradients(obs, B, actions, advantages)
+        sc = net.scalars.cpu().numpy()
+        net.check_status()
+        table = {self.output_heads[0].entropy: lambda: sc[1]}
+        if any(f not in table for f in additional_fetches):
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        return float(sc[0]), [float(sc[0])], float(net.norm.item()), [table[f]() for f in additional_fetches]
+
+
+_BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
+                       "SACPolicyNetworkParameters": SACPolicyArchitecture,
                        "SACCriticNetworkParameters": SACQArchitecture,
                        "SACValueNetworkParameters": SACValueArchitecture,
                        "ClippedPPONetworkParameters": PPOArchitecture}

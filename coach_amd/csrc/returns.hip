@@ -18,6 +18,7 @@
 // HBM-bound: 17 B per step (r, V, done in; advantage, value target out) — SURVEY.md §8(d).
 // Compiled with -ffp-contract=off (see Makefile).
 #include "rlx_common.hpp"
+#include "episode_returns.hpp"
 
 namespace {
 
@@ -385,11 +386,9 @@ __global__ void signals_reset_kernel(double *table, int rows) {
 
 namespace {
 // Episode.update_discounted_rewards (core_types.py:771-801) for ONE completed episode whose T transitions sit in a
-// time-major ring (row of step k = ((s0 + k) mod ring_steps) * n_env + env).  The reference adds
-// current_discount * rewards[i:] for i = 1 .. n-1 onto a float64 copy of the rewards, current_discount growing by
-// repeated multiplication: out[t] = ((r[t] + g1 r[t+1]) + g2 r[t+2]) + ...  with g_j = g_{j-1} * discount — the same
-// order and the same products here, so the column is bit-identical to the reference's n_step_discounted_rewards.
-// (-ffp-contract=off: no fused multiply-add.)  O(T * n) like the reference; one thread per transition.
+// time-major ring (row of step k = ((s0 + k) mod ring_steps) * n_env + env).  The sum itself is
+// rlx::episode_nstep_return (episode_returns.hpp): the reference's order and products, so the column is bit-identical
+// to the reference's n_step_discounted_rewards.  O(T * n) like the reference; one thread per transition.
 __global__ void episode_nstep_returns_kernel(const float *__restrict__ rewards, double *__restrict__ out,
                                              double *__restrict__ compact, long long s0, int T, int env,
                                              int n_env, long long ring_steps, double discount, int n_step) {
@@ -397,12 +396,7 @@ __global__ void episode_nstep_returns_kernel(const float *__restrict__ rewards, 
     if (t >= T) return;
     const int n = (n_step == -1 || n_step > T) ? T : n_step;
     auto row = [&](int k) { return ((s0 + k) % ring_steps) * n_env + env; };
-    double acc = (double)rewards[row(t)];
-    double g = discount;
-    for (int j = 1; j < n; ++j) {
-        if (t + j < T) acc += g * (double)rewards[row(t + j)];
-        g *= discount;
-    }
+    const double acc = rlx::episode_nstep_return(rewards, t, T, n, discount, row);
     if (out) out[row(t)] = acc;
     if (compact) compact[t] = acc;
 }

@@ -1042,3 +1042,70 @@ class NAFNet(_NetBase):
         self.torso.backward(ctx, acts)
         self._apply_update(grad_scale, sync, mix_rate)
         return self.loss
+
+
+def policy_gradient_net_kwargs(np_, alg, seed):
+    """PolicyGradientNetworkParameters + the algorithm's beta_entropy -> the keywords of PolicyGradientNet's constructor"""
+    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
+                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
+                adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
+                clip_gradients=getattr(np_, "clip_gradients", None), beta_entropy=getattr(alg, "beta_entropy", 0) or 0,
+                seed=seed)
+
+
+class PolicyGradientNet(_NetBase):
+    """PolicyGradientNetworkParameters (agents/policy_gradients_agent.py:35-41): one embedder + FC middleware tower under
+    a discrete PolicyHead (heads/policy_head.py:89-100): Dense(feat, A) named 'fc', default initialisation, whose outputs
+    are the policy values (logits).  No target copy.  The head's loss and its gradient come from rlx_pg_head_loss
+    (csrc/policy_gradient.hip); an update window's gradient is ADDED onto `accumulated`, which one Adam step consumes
+    and clears (Architecture.accumulate_gradients / apply_and_reset_gradients)."""
+
+    def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
+                 learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None,
+                 beta_entropy=0.0, seed=0):
+        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        if not 1 <= self.A <= 18:
+            raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % self.A)
+        self.clip_gradients = clip_gradients
+        self.beta_entropy = float(beta_entropy)
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        self.head = G.Dense(self.params, "main/policy_values_head/fc", feat, self.A, None, 1)
+        self.modules = [self.torso, self.head]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self.scalars = torch.zeros(2, dtype=torch.float32, device=device)       # loss, mean entropy of the last window
+        self.loss, self.entropy = self.scalars[0:1], self.scalars[1:2]
+        self.accumulated = torch.zeros_like(self.params.grads)
+
+    def policy_values(self, obs, B, tag="act"):
+        """the head's Dense output [B, A] (a Tensor; .data is the buffer): logits of the action probabilities"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
+        return self.head.forward(self.ctx, acts[-1], tag=tag)
+
+    def window_gradients(self, obs, T, actions, advantages):
+        """forward on the T states of one update window, the head loss against (actions, advantages), backward: the
+        gradients in params.grads (clipped when clip_gradients is set), the loss and the mean entropy in self.scalars,
+        tf.global_norm of the raw gradients in self.norm.  The context's buffers are keyed by shape, so every window
+        length has its own activations and the means divide by the window's true length."""
+        ctx = self.ctx
+        acts = self.torso.forward(ctx, self.obs_tensor(obs, T), tag="train")
+        z = self.head.forward(ctx, acts[-1], tag="train")
+        self.lib.pg_head_loss(z.data, self.A, actions, advantages, self.beta_entropy, T, T, self.A, z.ensure_grad(),
+                              self.A, self.scalars, self.status, ctx.stream)
+        self.head.backward(ctx, acts[-1], z)
+        self.torso.backward(ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss
+
+    def accumulate_window(self, obs, T, actions, advantages):
+        """accumulate_gradients (architecture.py:312-385): window_gradients, then accumulated += gradients"""
+        loss = self.window_gradients(obs, T, actions, advantages)
+        self.lib.axpby(self.accumulated, 1.0, self.accumulated, 1.0, self.params.grads, self.params.size, self.ctx.stream)
+        return loss
+
+    def apply_accumulated(self, grad_scale=1.0):
+        """apply_and_reset_gradients (architecture.py:469-521): one Adam step on the accumulated gradients, which are
+        then cleared"""
+        self.adam.step(float(grad_scale), grads=self.accumulated)
+        self.accumulated.zero_()

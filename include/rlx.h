@@ -1338,6 +1338,44 @@ int rlx_chain_step(const int *action, int *state, int *steps, float *next_obs, f
                    unsigned char *game_over, int n_env, int chain_length, int start_state, int max_steps, int therm,
                    float left_state_reward, float right_state_reward, int *status, void *stream);
 
+/* ------------------------------------------------------- Policy Gradients (added entry points) -- */
+/* One update window of PolicyOptimizationAgent.train for a PolicyGradientsAgent (agents/policy_optimization_agent.py:
+ * 85-135, agents/policy_gradients_agent.py:98-126), one workgroup, fp64 in the reference's operation order:
+ *   returns_out[0 .. length)   Episode.update_discounted_rewards with n_step -1 over the WHOLE episode so far
+ *                              (core_types.py:780-801; the sum of rlx_episode_nstep_returns) — bit-identical;
+ *   the two normalised rescalers: update_episode_statistics (:72-83) over the whole episode: episodes_seen[i] += 1,
+ *                              m[i] -= m[i] / n[i]; m[i] += r[i] / n[i] (bit-identical), and the episode's np.mean /
+ *                              np.std into stats_out[2], [3] (numpy's pairwise summation restated; 0, 0 otherwise);
+ *   rescaled_out[i], i < length - start: the rescaling loop on the window episode[start:] — TOTAL_RETURN copies entry 0
+ *                              of the window, FUTURE_RETURN_NORMALIZED_BY_TIMESTEP subtracts mean_over_episodes[i] with i
+ *                              the position in the BATCH, FUTURE_RETURN_NORMALIZED_BY_EPISODE gives 0 when std == 0;
+ *   advantages_out[i]          the same value rounded to fp32 once (the head's placeholder);
+ *   stats_out[0], [1]          'Returns Mean' = np.mean, 'Returns Variance' = np.std of rescaled_out.
+ * rewards: the episode's filtered rewards [length], contiguous.  mean_over_episodes / episodes_seen / returns_out /
+ * rescaled_out / advantages_out have max_length entries; an episode longer than max_length raises
+ * RLX_PG_STATUS_EPISODE_TOO_LONG in *status and nothing else is read or written. */
+#define RLX_PG_TOTAL_RETURN 0
+#define RLX_PG_FUTURE_RETURN 1
+#define RLX_PG_FUTURE_RETURN_NORMALIZED_BY_EPISODE 2
+#define RLX_PG_FUTURE_RETURN_NORMALIZED_BY_TIMESTEP 3
+#define RLX_PG_STATUS_EPISODE_TOO_LONG 2
+int rlx_pg_episode_window(const float *rewards, int length, int start, double discount, int rescaler,
+                          double *mean_over_episodes, double *episodes_seen, int max_length, double *returns_out,
+                          double *rescaled_out, float *advantages_out, double *stats_out, int *status, void *stream);
+/* PolicyHead, discrete branch (architectures/tensorflow_components/heads/policy_head.py:75-100) as one launch of one
+ * workgroup.  logits [rows][ld]; rows [true_rows, rows) are padding (zero gradient, no term); every mean divides by
+ * true_rows.  Per row, fp32, eps = np.finfo(np.float32).eps: p = softmax(z) as rlx_c51_head_loss defines it, q = p + eps,
+ * S = sum q (index order), log pi = log q - log S with log x = (float)log((double)x) (tf Categorical(probs = q)),
+ * H = -sum (q / S) log pi.  scalars[0] = loss = -(1/T) sum_b log pi_b(a_b) adv_b - beta_entropy * scalars[1],
+ * scalars[1] = (1/T) sum_b H_b (thread partials in row order, then a fixed tree: no atomics); dlogits = dloss/dz.
+ * status bit 0 = an action outside [0, n_actions): that row has no term and a zero gradient.  1 <= n_actions <= 18. */
+int rlx_pg_head_loss(const float *logits, long long ld, const int *actions, const float *advantages, float beta_entropy,
+                     int rows, int true_rows, int n_actions, float *dlogits, long long ld_dlogits, float *scalars,
+                     int *status, void *stream);
+/* The 'Entropy' sample of PolicyOptimizationAgent.choose_action (policy_optimization_agent.py:154), per env, fp32:
+ * -sum_j p_j * log(p_j + eps) on action probabilities [n_env][ld]. */
+int rlx_action_entropy(const float *probs, long long ld, int n_env, int n_actions, float *entropy_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
