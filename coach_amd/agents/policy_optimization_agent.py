@@ -1,7 +1,8 @@
 """The on-policy base of the policy-optimisation family on one MI355X — host-side mirror of
 rl_coach/agents/policy_optimization_agent.py (PolicyGradientRescaler :30-39, PolicyOptimizationAgent :45-162) for N
-lockstep envs.  Its simplest member is PolicyGradientsAgent (agents/policy_gradients_agent.py); an Actor-Critic or ACER
-agent is a subclass with its own network, its own `_window_device` and, where it bootstraps, its own head.
+lockstep envs.  Its simplest member is PolicyGradientsAgent (agents/policy_gradients_agent.py); ActorCriticAgent
+(agents/actor_critic_agent.py) bootstraps; an ACER agent would be a subclass with its own network, its own
+`_window_device` and its own head.
 
 Every env is ONE reference agent's episode buffer (memories/episodic/single_episode_buffer.py: a staging buffer
 [n_env, L]) with its own `last_gradient_update_step_idx`; the envs share the network, the per-timestep statistics and

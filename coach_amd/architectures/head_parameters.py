@@ -77,3 +77,14 @@ class PolicyHeadParameters(HeadParameters):
     def __init__(self, activation_function='tanh', name='policy_head_params', rescale_gradient_from_head_by_factor=1.0,
                  loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class VHeadParameters(HeadParameters):
+    """VHeadParameters (head_parameters.py:50-60): one Dense layer of one output on the middleware's output, normalized-
+    columns initialisation with std 1.0 (heads/v_head.py:43-48), MSE against the value targets under `loss_weight`.
+    Actor-Critic's loss and gradient come from rlx_a3c_window_loss."""
+    head_type = "VHead"
+
+    def __init__(self, activation_function='relu', name='v_head_params', rescale_gradient_from_head_by_factor=1.0,
+                 loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

@@ -25,7 +25,10 @@ the calls of architecture.py:26-237 and tensorflow_components/architecture.py:31
     per-variable tensors, because the agent text combines them variable by variable;
   * Policy Gradients (`PolicyGradientNetworkParameters`): embedder -> FC middleware -> discrete PolicyHead, fed the way
     PolicyGradientsAgent.learn_from_batch feeds it (policy_gradients_agent.py:128-130): inputs 'observation' and
-    'output_0_0' = actions, targets = the rescaled returns; predict -> the action probabilities.
+    'output_0_0' = actions, targets = the rescaled returns; predict -> the action probabilities;
+  * Actor-Critic (`ActorCriticNetworkParameters`): embedder -> FC middleware -> VHead + discrete PolicyHead, fed the way
+    ActorCriticAgent.learn_from_batch feeds it (actor_critic_agent.py:175-177): inputs 'observation' and 'output_1_0' =
+    actions, targets = [value targets, advantages]; predict -> [V, the action probabilities].
 
 One device network (`coach_amd.nn.networks.DQNNet`) holds the online and the target weights in one
 allocation; the `…/online` and `…/target` HipArchitecture objects of a NetworkWrapper are two views of
@@ -39,7 +42,8 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import ClippedPPONet, DQNNet, PolicyGradientNet, dqn_net_kwargs, policy_gradient_net_kwargs
+from ..nn.networks import (ActorCriticNet, ClippedPPONet, DQNNet, PolicyGradientNet, actor_critic_net_kwargs,
+                           dqn_net_kwargs, policy_gradient_net_kwargs)
 from .architecture import Architecture
 
 
@@ -639,7 +643,60 @@ class PolicyGradientArchitecture(HipArchitecture):
         return float(sc[0]), [float(sc[0])], float(net.norm.item()), [table[f]() for f in additional_fetches]
 
 
+# ========================================================================== Actor-Critic
+class ActorCriticArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> VHead (head 0) + discrete PolicyHead (head 1), fed the way
+    ActorCriticAgent.learn_from_batch feeds it (actor_critic_agent.py:175-177): inputs 'observation' and 'output_1_0' =
+    actions, targets = [value targets (B, 1), advantages (B,)], fp64, rounded to fp32 once at the heads' placeholders
+    (rlx_a3c_window_loss with RLX_A3C_TARGETS_GIVEN).  predict -> [V (B, 1), action probabilities (B, A)];
+    accumulate_gradients -> total loss, [value loss, policy loss, the entropy regulariser], the gradients' norm."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        if not hasattr(spaces.action, "actions"):
+            raise ValueError("the continuous PolicyHead (a Box action space) is not served: the actor-critic network has "
+                             "the discrete head only")
+        return ActorCriticNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
+                              len(spaces.action.actions), **actor_critic_net_kwargs(np_, agent_parameters.algorithm, seed))
+
+    def _handles(self):
+        self.inputs = ['observation', 'output_1_0']
+        self.output_heads = [_HeadFetches(0, ['output']), _HeadFetches(1, ['entropy', 'output'])]
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        net = self.net
+        v, z = net.predict(obs, B, tag="%s_%d" % (tag, B))
+        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
+        net.lib.softmax(z, net.A, B, net.A, probs, net.A, _rlx.current_stream())
+        return [v.view(B, 1), probs]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        obs, B = self._observation(inputs)
+        if 'output_1_0' not in inputs:
+            raise ValueError("the policy head needs the input output_1_0 (the actions)")
+        actions = self._to_device(inputs['output_1_0'], torch.int32).reshape(-1).contiguous()
+        if actions.numel() != B:
+            raise ValueError("output_1_0 must hold one action per sample")
+        if not isinstance(targets, (list, tuple)) or len(targets) != 2:
+            raise ValueError("targets must be [the V head's targets, the policy head's advantages]")
+        value_targets, advantages = (self._to_device(t, torch.float64).reshape(-1).contiguous() for t in targets)
+        if value_targets.numel() != B or advantages.numel() != B:
+            raise ValueError("the value targets and the advantages must hold one value per sample")
+        net.window_gradients(obs, B, False, actions, value_targets, advantages)
+        sc = net.scalars.cpu().numpy()
+        net.check_status()
+        table = {self.output_heads[1].entropy: lambda: sc[3]}
+        if any(f not in table for f in additional_fetches):
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        losses = [float(sc[1]), float(sc[2])]
+        if net.beta_entropy:                             # the regulariser is a loss of its own (policy_head.py:77-79)
+            losses.append(float(-np.float32(net.beta_entropy) * sc[3]))
+        return float(sc[0]), losses, float(net.norm.item()), [table[f]() for f in additional_fetches]
+
+
 _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
+                       "ActorCriticNetworkParameters": ActorCriticArchitecture,
                        "SACPolicyNetworkParameters": SACPolicyArchitecture,
                        "SACCriticNetworkParameters": SACQArchitecture,
                        "SACValueNetworkParameters": SACValueArchitecture,

@@ -11,15 +11,15 @@
 // workgroup, so every sum has a fixed order and no float atomics or hand-offs between workgroups are needed.
 // tests/pg_ref.py is the numpy restatement; it states every fp32 / fp64 rounding point named here.
 // Compiled with -ffp-contract=off so the fp64 arithmetic rounds like numpy.
-#include "distributional_head.hpp"
+#include "policy_head.hpp"
 #include "episode_returns.hpp"
 
 namespace {
 
-constexpr int kPgThreads = 256;
-constexpr int kPgMaxActions = rlx::kDistMaxActions;
+constexpr int kPgThreads = rlx::kPgThreads;
+constexpr int kPgMaxActions = rlx::kPgMaxActions;
 constexpr int kPgStage = 2048;            // fp64 values staged in LDS for the serial sums (longer windows read HBM)
-constexpr float kEps = 1.1920928955078125e-07f;   // np.finfo(np.float32).eps (rl_coach/utils.py: eps)
+constexpr float kEps = rlx::kPgEps;
 
 // numpy's pairwise summation of n fp64 values elem(0) .. elem(n-1) (numpy/core/src/umath/loops_utils.h, pairwise_sum),
 // as np.add.reduce runs it over a contiguous array: blocks of <= 128 values are summed in eight interleaved accumulators
@@ -151,37 +151,7 @@ __global__ void __launch_bounds__(kPgThreads) pg_episode_window_kernel(const Win
     if (t == 0) mean_std(staged ? stage : a.rescaled, T, &a.stats[0], &a.stats[1]);
 }
 
-// The row arithmetic of the discrete PolicyHead: p = softmax(z) as csrc/c51.hip defines it, q = p + eps, S = sum q (index
-// order), log pi = log q - log S with log x = (float)log((double)x), H = -sum (q / S) * log pi.  All fp32.
-struct PgRow {
-    float p[kPgMaxActions], q[kPgMaxActions], lp[kPgMaxActions];
-    float S, H;
-};
-
-__device__ __forceinline__ void pg_row(const float *x, int A, PgRow &r) {
-    float mx = x[0];
-    for (int j = 1; j < A; ++j) mx = fmaxf(mx, x[j]);
-    float s = 0.f;
-    for (int j = 0; j < A; ++j) {
-        r.p[j] = (float)exp((double)(x[j] - mx));
-        s += r.p[j];
-    }
-    float S = 0.f;
-    for (int j = 0; j < A; ++j) {
-        r.p[j] = r.p[j] / s;
-        r.q[j] = r.p[j] + kEps;
-        S += r.q[j];
-    }
-    const float logS = (float)log((double)S);
-    float h = 0.f;
-    for (int j = 0; j < A; ++j) {
-        r.lp[j] = (float)log((double)r.q[j]) - logS;
-        h += (r.q[j] / S) * r.lp[j];
-    }
-    r.S = S;
-    r.H = -h;
-}
-
+// The row arithmetic of the discrete PolicyHead is policy_head.hpp's (shared with a3c.hip).
 struct HeadLossArgs {
     const float *logits;
     long long ld;
@@ -210,22 +180,7 @@ __global__ void __launch_bounds__(kPgThreads) pg_head_loss_kernel(const HeadLoss
             for (int j = 0; j < A; ++j) d[j] = 0.f;
             continue;
         }
-        PgRow r;
-        pg_row(a.logits + (size_t)b * a.ld, A, r);
-        const float adv = a.advantages[b];
-        pol += r.lp[act] * adv;
-        ent += r.H;
-        // g_k = dL/dp_k of this row's terms -(1/T) log pi_a adv - beta (1/T) H:
-        //   dlog pi_a/dp_k = [k == a]/q_a - 1/S,   dH/dp_k = -(log pi_k + H)/S;   dz_j = p_j (g_j - sum_k g_k p_k)
-        const float cp = adv / fT, ce = a.beta / fT;
-        float g[kPgMaxActions];
-        float dot = 0.f;
-        for (int k = 0; k < A; ++k) {
-            const float dlog = (k == act ? 1.f / r.q[k] : 0.f) - 1.f / r.S;
-            g[k] = ce * ((r.lp[k] + r.H) / r.S) - cp * dlog;
-            dot += g[k] * r.p[k];
-        }
-        for (int j = 0; j < A; ++j) d[j] = r.p[j] * (g[j] - dot);
+        rlx::pg_row_loss_grad(a.logits + (size_t)b * a.ld, A, act, a.advantages[b], a.beta, fT, d, pol, ent);
     }
     pol_s[t] = pol;
     ent_s[t] = ent;

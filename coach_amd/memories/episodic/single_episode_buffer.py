@@ -1,5 +1,5 @@
 """`SingleEpisodeBuffer` (rl_coach/memories/episodic/single_episode_buffer.py:21-33) for N lockstep envs: the memory
-of the on-policy agents that learn from the running episode (Policy Gradients; Actor-Critic and ACER later).
+of the on-policy agents that learn from the running episode (Policy Gradients, Actor-Critic; ACER later).
 
 In the reference the memory holds ONE finished episode and the agent trains from its `current_episode_buffer`, a list
 of Transition objects.  Here both are one staging buffer per env: row (e, t) of `obs` / `action` / `reward` is step t
@@ -10,7 +10,11 @@ place.  An episode that outgrows L raises (the environment's limit was wrong), b
 
 WHEN a transition is visible to train() is the agent's bookkeeping (the response of a non-terminal step is observed at
 the start of the next step, level_manager.py:236-264): the rows are written at once, the agent counts them one step
-late.  Evaluation never writes: `begin_evaluation` only redirects the acting state, as the device replays do.
+late.  A bootstrapping agent (Actor-Critic) also reads the stored `game_over` byte of a window's last row and the state
+behind the window: for a running episode that is row `end` of the env's rows, already written (the state the step whose
+response is not yet counted started from), so the window's T + 1 states are `obs[start : end + 1]` in place; for a
+finished episode it is `next_obs[end - 1]`, the observation BEFORE the reset (`last_next_state`).
+Evaluation never writes: `begin_evaluation` only redirects the acting state, as the device replays do.
 """
 import numpy as np
 import torch
@@ -39,6 +43,8 @@ class SingleEpisodeBuffer(Memory):
         self.obs = torch.zeros(rows, self.obs_dim, dtype=torch.float32, device=device)
         self.action = torch.zeros(rows, dtype=torch.int32, device=device)
         self.reward = torch.zeros(rows, dtype=torch.float32, device=device)
+        self.game_over = torch.zeros(rows, dtype=torch.uint8, device=device)
+        self.next_obs = torch.zeros(rows, self.obs_dim, dtype=torch.float32, device=device)     # before the reset
         self.cur_state = torch.empty(self.n_env, self.obs_dim, dtype=torch.float32, device=device)
         self._eval_state = torch.empty_like(self.cur_state)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
@@ -64,6 +70,15 @@ class SingleEpisodeBuffer(Memory):
         """(obs, action, reward) of steps [start, end) of env's running episode: views, no copy"""
         r0 = env * self.L
         return (self.obs[r0 + start:r0 + end], self.action[r0 + start:r0 + end], self.reward[r0:r0 + end])
+
+    def bootstrap_rows(self, env, start, end, complete):
+        """what a bootstrapping window [start, end) reads beside episode_rows: (the T + 1 states in place, or None when
+        the episode is complete and the state behind the window is `last_next_state`; that state [obs_dim]; the window's
+        last game-over byte [1]) — views, no copy"""
+        r0 = env * self.L
+        in_place = None if complete else self.obs[r0 + start:r0 + end + 1]
+        last_next_state = self.next_obs[r0 + end - 1] if complete else self.obs[r0 + end]
+        return in_place, last_next_state, self.game_over[r0 + end - 1:r0 + end]
 
     # ---------------------------------------------------------------- rollout side (the replays' calls)
     def _state(self):
@@ -95,6 +110,7 @@ class SingleEpisodeBuffer(Memory):
         """one transition per env at its own position, then the envs' next current state (the post-reset observation
         where the episode ended).  record=False (evaluation) only advances the state."""
         s = _rlx.current_stream()
+        stored_game_overs = game_overs
         if dones is not None:
             game_overs = dones
         state = self._state()
@@ -106,7 +122,8 @@ class SingleEpisodeBuffer(Memory):
             if (self.steps >= self.L).any():
                 raise IndexError("an episode outgrew the environment's episode limit of %d steps" % self.L)
             dst = self._dst.push((np.arange(self.n_env) * self.L + self.steps).astype(np.int32))
-            pairs = [(actions, self.action), (rewards, self.reward), (state, self.obs)]
+            pairs = [(actions, self.action), (rewards, self.reward), (state, self.obs),
+                     (stored_game_overs, self.game_over), (next_obs, self.next_obs)]
             self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, dst, 0, 0, self.n_env, self.rows,
                                   self.n_env, self.status, s)
             self.steps += 1

@@ -1053,7 +1053,29 @@ def policy_gradient_net_kwargs(np_, alg, seed):
                 seed=seed)
 
 
-class PolicyGradientNet(_NetBase):
+class _WindowAccumulatingNet(_NetBase):
+    """the on-policy networks' gradient accumulation (Architecture.accumulate_gradients / apply_and_reset_gradients): a
+    subclass gives `window_gradients(...)`, which leaves one update window's gradients in params.grads and returns the
+    loss; an update window's gradient is ADDED onto `accumulated`, which one Adam step consumes and clears."""
+
+    def _finish_accumulating(self, n_scalars):
+        self.scalars = torch.zeros(n_scalars, dtype=torch.float32, device=self.device)
+        self.accumulated = torch.zeros_like(self.params.grads)
+
+    def accumulate_window(self, *args, **kw):
+        """accumulate_gradients (architecture.py:312-385): window_gradients, then accumulated += gradients"""
+        loss = self.window_gradients(*args, **kw)
+        self.lib.axpby(self.accumulated, 1.0, self.accumulated, 1.0, self.params.grads, self.params.size, self.ctx.stream)
+        return loss
+
+    def apply_accumulated(self, grad_scale=1.0):
+        """apply_and_reset_gradients (architecture.py:469-521): one Adam step on the accumulated gradients, which are
+        then cleared"""
+        self.adam.step(float(grad_scale), grads=self.accumulated)
+        self.accumulated.zero_()
+
+
+class PolicyGradientNet(_WindowAccumulatingNet):
     """PolicyGradientNetworkParameters (agents/policy_gradients_agent.py:35-41): one embedder + FC middleware tower under
     a discrete PolicyHead (heads/policy_head.py:89-100): Dense(feat, A) named 'fc', default initialisation, whose outputs
     are the policy values (logits).  No target copy.  The head's loss and its gradient come from rlx_pg_head_loss
@@ -1073,9 +1095,8 @@ class PolicyGradientNet(_NetBase):
         self.head = G.Dense(self.params, "main/policy_values_head/fc", feat, self.A, None, 1)
         self.modules = [self.torso, self.head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
-        self.scalars = torch.zeros(2, dtype=torch.float32, device=device)       # loss, mean entropy of the last window
+        self._finish_accumulating(2)                                 # loss, mean entropy of the last window
         self.loss, self.entropy = self.scalars[0:1], self.scalars[1:2]
-        self.accumulated = torch.zeros_like(self.params.grads)
 
     def policy_values(self, obs, B, tag="act"):
         """the head's Dense output [B, A] (a Tensor; .data is the buffer): logits of the action probabilities"""
@@ -1098,14 +1119,98 @@ class PolicyGradientNet(_NetBase):
             self.grad_norm()
         return self.loss
 
-    def accumulate_window(self, obs, T, actions, advantages):
-        """accumulate_gradients (architecture.py:312-385): window_gradients, then accumulated += gradients"""
-        loss = self.window_gradients(obs, T, actions, advantages)
-        self.lib.axpby(self.accumulated, 1.0, self.accumulated, 1.0, self.params.grads, self.params.size, self.ctx.stream)
-        return loss
 
-    def apply_accumulated(self, grad_scale=1.0):
-        """apply_and_reset_gradients (architecture.py:469-521): one Adam step on the accumulated gradients, which are
-        then cleared"""
-        self.adam.step(float(grad_scale), grads=self.accumulated)
-        self.accumulated.zero_()
+def actor_critic_net_kwargs(np_, alg, seed):
+    """ActorCriticNetworkParameters + the algorithm's beta_entropy -> the keywords of ActorCriticNet's constructor"""
+    heads = {h.head_type: h for h in np_.heads_parameters}
+    return dict(policy_gradient_net_kwargs(np_, alg, seed), v_loss_weight=heads["VHead"].loss_weight)
+
+
+class ActorCriticNet(_WindowAccumulatingNet):
+    """ActorCriticNetworkParameters (agents/actor_critic_agent.py:69-77): one embedder + FC middleware tower under two
+    heads — head 0 = VHead (heads/v_head.py:43-48: Dense(feat, 1), normalized-columns init std 1.0, MSE under
+    loss_weight 0.5), head 1 = the discrete PolicyHead (Dense(feat, A) named 'fc', default initialisation).  No target
+    copy; gradients clipped by global norm at 40.  Everything between the forward and the backward pass of an update
+    window — the bootstrapped targets, the advantages, both heads' losses and gradients — is ONE launch,
+    rlx_a3c_window_loss (csrc/a3c.hip)."""
+
+    def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
+                 learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=40.0,
+                 beta_entropy=0.0, v_loss_weight=0.5, seed=0):
+        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        if not 1 <= self.A <= 18:
+            raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % self.A)
+        self.clip_gradients = clip_gradients
+        self.beta_entropy, self.v_loss_weight = float(beta_entropy), float(v_loss_weight)
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        self.v_head = G.Dense(self.params, "main/v_values_head/output", feat, 1, None, 1, init=G.normalized_columns(1.0))
+        self.pi_head = G.Dense(self.params, "main/policy_values_head/fc", feat, self.A, None, 1)
+        self.heads = [self.v_head, self.pi_head]
+        self.modules = [self.torso] + self.heads
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self._finish_accumulating(4)                 # total loss, value loss, policy loss, mean entropy of the last window
+        sc = self.scalars
+        self.loss, self.value_loss, self.policy_loss, self.entropy = sc[0:1], sc[1:2], sc[2:3], sc[3:4]
+        self._stage = {}
+
+    def policy_values(self, obs, B, tag="act"):
+        """the policy head's Dense output [B, A] (logits of the action probabilities); the V head is not run"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
+        return self.pi_head.forward(self.ctx, acts[-1], tag=tag)
+
+    def predict(self, obs, B, tag="predict"):
+        """both heads -> (V [B], logits [B, A]) as buffers"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
+        v, z = self._heads_forward(acts[-1], acts[-1], tag)
+        return v.data.view(B), z.data.view(B, self.A)
+
+    def _heads_forward(self, x_v, x_pi, tag):
+        """both heads in one launch where the narrow-dense kernels serve the policy head's width"""
+        if self.A <= G.SMALL_N:
+            return G.small_dense_forward_multi(self.ctx, [(self.v_head, x_v), (self.pi_head, x_pi)], tag=tag)
+        return self.v_head.forward(self.ctx, x_v, tag=tag), self.pi_head.forward(self.ctx, x_pi, tag=tag)
+
+    def stage_rows(self, obs, last_next_obs):
+        """the window's T states and a bootstrap state that does not follow them in memory -> one [T + 1, D] buffer"""
+        T = obs.shape[0]
+        buf = self._stage.get(T)
+        if buf is None:
+            buf = self._stage[T] = torch.empty(T + 1, obs.shape[1], dtype=obs.dtype, device=self.device)
+        buf[:T].copy_(obs)
+        buf[T].copy_(last_next_obs.view(-1))
+        return buf
+
+    def window_gradients(self, obs_rows, T, bootstrap, actions, targets, advantages, rewards=None, game_over=None,
+                         discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False):
+        """forward on the T states of one update window and, with bootstrap, on the last next state behind them (obs_rows
+        has T + bootstrap rows); rlx_a3c_window_loss against (actions, rewards, the device's game-over flag), which
+        leaves the fp64 value targets and advantages in targets / advantages [T] — or, with the default rescaler, reads
+        them from there; both heads backward, their input gradients summed; the torso backward: the gradients in
+        params.grads (clipped when clip_gradients is set), the four scalars in self.scalars, tf.global_norm of the raw
+        gradients in self.norm.  The context's buffers are keyed by shape; the means divide by T."""
+        ctx, A = self.ctx, self.A
+        rows = T + int(bool(bootstrap))
+        acts = self.torso.forward(ctx, self.obs_tensor(obs_rows, rows), tag="train")
+        feat = acts[-1]
+        feat.ensure_grad()
+        # each head writes its input gradient into a buffer of its own; they are added into feat.grad below
+        side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
+        side.grad = ctx.buffer(self.pi_head.name + "/input:grad", tuple(feat.data.shape), tag="train")
+        v, z = self._heads_forward(feat, side, "train")
+        self.values = v.data.view(rows)                  # the 'Values' samples are its first T entries
+        self.lib.a3c_window_loss(v.data, 1, z.data, A, actions, rewards, game_over, T, rows, A, float(discount),
+                                 float(gae_lambda), int(rescaler), int(bool(estimate_with_gae)), self.beta_entropy,
+                                 self.v_loss_weight, targets, advantages, v.ensure_grad(), 1, z.ensure_grad(), A,
+                                 self.scalars, self.status, ctx.stream)
+        if A <= G.SMALL_N and rows * A <= 1024:
+            G.small_dense_backward_multi(ctx, [(self.v_head, feat, v), (self.pi_head, side, z)])
+        else:
+            self.v_head.backward(ctx, feat, v)
+            self.pi_head.backward(ctx, side, z)
+        self.lib.axpby(feat.grad, 1.0, feat.grad, 1.0, side.grad, feat.grad.numel(), ctx.stream)
+        feat.grad_is_dz = feat.grad_is_dz and side.grad_is_dz
+        self.torso.backward(ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss

@@ -1376,6 +1376,40 @@ int rlx_pg_head_loss(const float *logits, long long ld, const int *actions, cons
  * -sum_j p_j * log(p_j + eps) on action probabilities [n_env][ld]. */
 int rlx_action_entropy(const float *probs, long long ld, int n_env, int n_actions, float *entropy_out, void *stream);
 
+/* ------------------------------------------------------- Actor-Critic / A3C (added entry point) -- */
+/* ActorCriticAgent.learn_from_batch (agents/actor_critic_agent.py:127-186) between the forward and the backward pass of
+ * one update window of T transitions, one launch of one workgroup.  The forward pass ran on `rows` states: rows = T + 1
+ * when the window bootstraps (the last row is the last next state), rows = T is allowed when the last transition is a
+ * game over.  *game_over is that transition's flag, read on the device.
+ *   targets_out / advantages_out [T], fp64, the reference's operation order (a sequential reverse recurrence):
+ *     RLX_A3C_A_VALUE  R = 0 on a game over, else V[T];  R = r_i + discount * R;  target_i = R, adv_i = R - V_i (:145-154);
+ *     RLX_A3C_GAE      values = V[0 .. T] with values[T] = 0 on a game over; deltas = r + discount * values[1:] -
+ *                      values[:-1]; adv = the lfilter recurrence y_i = x_i + discount * gae_lambda * y_{i+1} over the
+ *                      deltas; targets = adv + V when estimate_state_value_using_gae, else the same recurrence with
+ *                      `discount` over the rewards extended by values[T], without its last element (:108-125, :156-165).
+ *     `discount * <fp32 V>` is an fp32 product where the reference's is (tests/a3c_ref.py names the lines).
+ *     RLX_A3C_TARGETS_GIVEN  both arrays are INPUTS (what Architecture.accumulate_gradients is handed, :175-177);
+ *                      rewards and game_over are not read (they may be null) and nothing is bootstrapped.
+ *   The heads read both rounded to fp32 once.  Every mean divides by T; the bootstrap row has no term, dV = 0, dlogits = 0.
+ *   V head (VHead, heads/head.py:170-181): scalars[1] = value loss = (1/T) sum_b v_loss_weight * (V_b - target_b)^2,
+ *     dV_b = v_loss_weight * 2 (V_b - target_b) / T.
+ *   Policy head: the row arithmetic, status bit 0 and dlogits of rlx_pg_head_loss with these advantages (one shared
+ *     definition, csrc/policy_head.hpp).  scalars[2] = policy loss = -(1/T) sum_b log pi_b(a_b) adv_b,
+ *     scalars[3] = mean entropy, scalars[0] = total = scalars[1] + (scalars[2] - beta_entropy * scalars[3]).
+ *   Batch sums: thread partials in row order, then a fixed tree (no atomics).
+ * A window that is not a game over with rows = T raises RLX_A3C_STATUS_NO_BOOTSTRAP_ROW and nothing else is read or
+ * written.  V / dV are read and written at strides ld_v / ld_dv.  1 <= n_actions <= 18. */
+#define RLX_A3C_A_VALUE 5             /* PolicyGradientRescaler.A_VALUE */
+#define RLX_A3C_GAE 8                 /* PolicyGradientRescaler.GAE */
+#define RLX_A3C_TARGETS_GIVEN -1
+#define RLX_A3C_STATUS_NO_BOOTSTRAP_ROW 2
+int rlx_a3c_window_loss(const float *V, long long ld_v, const float *logits, long long ld, const int *actions,
+                        const float *rewards, const unsigned char *game_over, int T, int rows, int n_actions,
+                        double discount, double gae_lambda, int rescaler, int estimate_state_value_using_gae,
+                        float beta_entropy, float v_loss_weight, double *targets_out, double *advantages_out, float *dV,
+                        long long ld_dv, float *dlogits, long long ld_dlogits, float *scalars, int *status,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
