@@ -317,6 +317,9 @@ ADAM_TICKET_WORDS = CONSTANTS["RLX_ADAM_TICKET_WORDS"]
 MAX_SPLITK_JOBS = CONSTANTS["RLX_MAX_SPLITK_JOBS"]
 MAX_COLUMNS = CONSTANTS["RLX_MAX_COLUMNS"]
 A3C_TARGETS_GIVEN = CONSTANTS["RLX_A3C_TARGETS_GIVEN"]     # rlx_a3c_window_loss reads the targets it is handed
+# rlx_nstep_q_window_loss: the targets horizon by the reference's name; TARGETS_GIVEN reads the targets it is handed
+NSTEPQ_HORIZON = {"N-Step": CONSTANTS["RLX_NSTEPQ_N_STEP"], "1-Step": CONSTANTS["RLX_NSTEPQ_ONE_STEP"]}
+NSTEPQ_TARGETS_GIVEN = CONSTANTS["RLX_NSTEPQ_TARGETS_GIVEN"]
 ACT = {None: CONSTANTS["RLX_ACT_NONE"]}         # activation codes by name: {None: 0, "none": 0, "relu": 1, "tanh": 2}
 ACT.update((k[len("RLX_ACT_"):].lower(), v) for k, v in CONSTANTS.items() if k.startswith("RLX_ACT_"))
 

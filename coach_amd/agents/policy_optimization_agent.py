@@ -1,8 +1,9 @@
 """The on-policy base of the policy-optimisation family on one MI355X — host-side mirror of
 rl_coach/agents/policy_optimization_agent.py (PolicyGradientRescaler :30-39, PolicyOptimizationAgent :45-162) for N
 lockstep envs.  Its simplest member is PolicyGradientsAgent (agents/policy_gradients_agent.py); ActorCriticAgent
-(agents/actor_critic_agent.py) bootstraps; an ACER agent would be a subclass with its own network, its own
-`_window_device` and its own head.
+(agents/actor_critic_agent.py) bootstraps; NStepQAgent (agents/n_step_q_agent.py) trains a Q head with a target network
+from the same windows and acts epsilon-greedily (`_make_exploration_policy`); an ACER agent would be a subclass with
+its own network, its own `_window_device` and its own head.
 
 Every env is ONE reference agent's episode buffer (memories/episodic/single_episode_buffer.py: a staging buffer
 [n_env, L]) with its own `last_gradient_update_step_idx`; the envs share the network, the per-timestep statistics and
@@ -73,7 +74,7 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
         self.policy_gradient_rescaler = getattr(alg, "policy_gradient_rescaler", None)      # :49-51
         self.networks = {"main": self._make_network(tuple(ep.observation_shape), self.ap.network_wrappers["main"])}
         self.memory = SingleEpisodeBuffer(self.device, self.n_env, tuple(ep.observation_shape), self.L)
-        self.exploration_policy = Categorical(self.A, self.n_env, self.device, self.ap.exploration)
+        self.exploration_policy = self._make_exploration_policy()
         dev, n, L = self.device, self.n_env, self.L
         self.actions = torch.zeros(n, dtype=torch.int32, device=dev)
         self.action_probabilities = torch.zeros(n, self.A, dtype=torch.float32, device=dev)
@@ -94,6 +95,10 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
 
     def _make_network(self, obs_shape, wrapper):
         raise NotImplementedError
+
+    def _make_exploration_policy(self):
+        """the family acts by a categorical draw on the policy head; a value-based member (N-step Q) gives its own"""
+        return Categorical(self.A, self.n_env, self.device, self.ap.exploration)
 
     def _window_device(self, env, start, end, complete):
         """learn_from_batch on steps [start, end) of env's episode: the gradients are accumulated -> the loss"""

@@ -28,7 +28,9 @@ the calls of architecture.py:26-237 and tensorflow_components/architecture.py:31
     'output_0_0' = actions, targets = the rescaled returns; predict -> the action probabilities;
   * Actor-Critic (`ActorCriticNetworkParameters`): embedder -> FC middleware -> VHead + discrete PolicyHead, fed the way
     ActorCriticAgent.learn_from_batch feeds it (actor_critic_agent.py:175-177): inputs 'observation' and 'output_1_0' =
-    actions, targets = [value targets, advantages]; predict -> [V, the action probabilities].
+    actions, targets = [value targets, advantages]; predict -> [V, the action probabilities];
+  * N-step Q (`NStepQNetworkParameters`): embedder -> FC middleware -> QHead with a target copy, fed the way
+    NStepQAgent.learn_from_batch feeds it (n_step_q_agent.py:134): targets = [the full target matrix]; predict -> Q.
 
 One device network (`coach_amd.nn.networks.DQNNet`) holds the online and the target weights in one
 allocation; the `…/online` and `…/target` HipArchitecture objects of a NetworkWrapper are two views of
@@ -42,8 +44,8 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import (ActorCriticNet, ClippedPPONet, DQNNet, PolicyGradientNet, actor_critic_net_kwargs,
-                           dqn_net_kwargs, policy_gradient_net_kwargs)
+from ..nn.networks import (ActorCriticNet, ClippedPPONet, DQNNet, NStepQNet, PolicyGradientNet,
+                           actor_critic_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs, policy_gradient_net_kwargs)
 from .architecture import Architecture
 
 
@@ -695,8 +697,45 @@ class ActorCriticArchitecture(HipArchitecture):
         return float(sc[0]), losses, float(net.norm.item()), [table[f]() for f in additional_fetches]
 
 
+# =============================================================================== N-step Q
+class NStepQArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> QHead with a target copy, fed the way NStepQAgent.learn_from_batch feeds it
+    (n_step_q_agent.py:134): input 'observation', targets = [state_value_head_targets (B, A)], the online prediction with
+    the taken actions' columns replaced.  A full target matrix is the head's regression against every column
+    (rlx_regression_loss; the untouched columns give exactly zero).  predict -> Q (B, A), of the online or the target
+    view; accumulate_gradients -> total loss, [the Q head's loss], the gradients' norm."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        if not hasattr(spaces.action, "actions"):
+            raise ValueError("a Box action space is not served: the N-step Q network has the discrete QHead only")
+        return NStepQNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
+                         len(spaces.action.actions), **n_step_q_net_kwargs(np_, seed))
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        net, tag = self.net, "%s_%d" % (tag, B)
+        q = net.target_q_values(obs, B, tag=tag + "_t") if self.is_target else net.q_values(obs, B, tag=tag)
+        return [q.data.view(B, net.A)]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        obs, B = self._observation(inputs)
+        target = targets[0] if isinstance(targets, (list, tuple)) else targets
+        target = self._to_device(target, torch.float32).contiguous()
+        if tuple(target.shape) != (B, net.A):
+            raise ValueError("targets shape {} does not match the head output {}".format(tuple(target.shape), (B, net.A)))
+        if importance_weights is not None:
+            raise ValueError("the N-step Q head takes no importance weights")
+        if additional_fetches:
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        net.window_gradients(obs, B, None, None, target_matrix=target)
+        total_loss = float(net.loss.item())
+        return total_loss, [total_loss], float(net.norm.item()), []
+
+
 _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
                        "ActorCriticNetworkParameters": ActorCriticArchitecture,
+                       "NStepQNetworkParameters": NStepQArchitecture,
                        "SACPolicyNetworkParameters": SACPolicyArchitecture,
                        "SACCriticNetworkParameters": SACQArchitecture,
                        "SACValueNetworkParameters": SACValueArchitecture,

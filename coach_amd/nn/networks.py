@@ -1061,6 +1061,18 @@ class _WindowAccumulatingNet(_NetBase):
     def _finish_accumulating(self, n_scalars):
         self.scalars = torch.zeros(n_scalars, dtype=torch.float32, device=self.device)
         self.accumulated = torch.zeros_like(self.params.grads)
+        self._stage = {}
+
+    def stage_rows(self, obs, last_next_obs):
+        """a window's n states and a state that does not follow them in memory (the observation before the reset behind
+        a finished episode) -> one [n + 1, D] buffer"""
+        T = obs.shape[0]
+        buf = self._stage.get(T)
+        if buf is None:
+            buf = self._stage[T] = torch.empty(T + 1, obs.shape[1], dtype=obs.dtype, device=self.device)
+        buf[:T].copy_(obs)
+        buf[T].copy_(last_next_obs.view(-1))
+        return buf
 
     def accumulate_window(self, *args, **kw):
         """accumulate_gradients (architecture.py:312-385): window_gradients, then accumulated += gradients"""
@@ -1152,7 +1164,6 @@ class ActorCriticNet(_WindowAccumulatingNet):
         self._finish_accumulating(4)                 # total loss, value loss, policy loss, mean entropy of the last window
         sc = self.scalars
         self.loss, self.value_loss, self.policy_loss, self.entropy = sc[0:1], sc[1:2], sc[2:3], sc[3:4]
-        self._stage = {}
 
     def policy_values(self, obs, B, tag="act"):
         """the policy head's Dense output [B, A] (logits of the action probabilities); the V head is not run"""
@@ -1170,16 +1181,6 @@ class ActorCriticNet(_WindowAccumulatingNet):
         if self.A <= G.SMALL_N:
             return G.small_dense_forward_multi(self.ctx, [(self.v_head, x_v), (self.pi_head, x_pi)], tag=tag)
         return self.v_head.forward(self.ctx, x_v, tag=tag), self.pi_head.forward(self.ctx, x_pi, tag=tag)
-
-    def stage_rows(self, obs, last_next_obs):
-        """the window's T states and a bootstrap state that does not follow them in memory -> one [T + 1, D] buffer"""
-        T = obs.shape[0]
-        buf = self._stage.get(T)
-        if buf is None:
-            buf = self._stage[T] = torch.empty(T + 1, obs.shape[1], dtype=obs.dtype, device=self.device)
-        buf[:T].copy_(obs)
-        buf[T].copy_(last_next_obs.view(-1))
-        return buf
 
     def window_gradients(self, obs_rows, T, bootstrap, actions, targets, advantages, rewards=None, game_over=None,
                          discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False):
@@ -1210,6 +1211,79 @@ class ActorCriticNet(_WindowAccumulatingNet):
             self.pi_head.backward(ctx, side, z)
         self.lib.axpby(feat.grad, 1.0, feat.grad, 1.0, side.grad, feat.grad.numel(), ctx.stream)
         feat.grad_is_dz = feat.grad_is_dz and side.grad_is_dz
+        self.torso.backward(ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss
+
+
+def n_step_q_net_kwargs(np_, seed):
+    """NStepQNetworkParameters -> the keywords of NStepQNet's constructor"""
+    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
+                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
+                adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
+                clip_gradients=getattr(np_, "clip_gradients", None),
+                replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss, seed=seed)
+
+
+class NStepQNet(_WindowAccumulatingNet):
+    """NStepQNetworkParameters (agents/n_step_q_agent.py:34-43): one embedder + FC middleware tower under the plain QHead
+    (Dense(feat, A), the layer and initialisation of DQNNet._q_head_layer), with a target copy; MSE unless
+    replace_mse_with_huber_loss.  Everything between the forward and the backward pass of an update window — the
+    bootstrapped N-step or 1-step targets from the target network, the Q head's loss on the taken action and its
+    gradient — is ONE launch, rlx_nstep_q_window_loss (csrc/n_step_q.hip)."""
+
+    def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
+                 learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None,
+                 replace_mse_with_huber_loss=False, seed=0):
+        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        self.clip_gradients = clip_gradients
+        self.huber = bool(replace_mse_with_huber_loss)
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        self.q_head = G.Dense(self.params, "main/q_head/dense", feat, self.A, None, 1)
+        self.modules = [self.torso, self.q_head]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=True)
+        self._finish_accumulating(1)                                 # the loss of the last window
+        self.loss = self.scalars[0:1]
+        self.td_targets = None           # [T, A] of the last window: state_value_head_targets, the 'Q Values' samples
+
+    def _q(self, obs, B, tag, weights=None):
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=weights)
+        return acts, self.q_head.forward(self.ctx, acts[-1], tag=tag, weights=weights)
+
+    def q_values(self, obs, B, tag="act"):
+        """the ONLINE network's Q values [B, A] (a Tensor; .data is the buffer), for acting"""
+        return self._q(obs, B, tag)[1]
+
+    def target_q_values(self, obs, rows, tag="target"):
+        """the TARGET network's Q values [rows, A]"""
+        return self._q(obs, rows, tag, self.target)[1]
+
+    def window_gradients(self, obs, T, actions, targets, target_obs=None, rows_t=0, rewards=None, game_over=None,
+                         discount=0.0, horizon=_rlx.NSTEPQ_TARGETS_GIVEN, target_matrix=None):
+        """the online network forward on the T states of one update window and the target network on rows_t states
+        behind them (one for 'N-Step', the T next states for '1-Step'); rlx_nstep_q_window_loss against (actions,
+        rewards, the device's game-over flag), which leaves the fp32 targets in targets [T] — or, with the default
+        horizon, reads them from there — and the whole target matrix in self.td_targets; the head and the torso
+        backward: the gradients in params.grads (clipped when clip_gradients is set), the loss in self.loss,
+        tf.global_norm of the raw gradients in self.norm.  target_matrix [T, A] (what Architecture.accumulate_gradients
+        is handed): the head's loss against every column, which is rlx_regression_loss."""
+        ctx, A = self.ctx, self.A
+        q_t = self.target_q_values(target_obs, rows_t, tag="train_target").data if rows_t else None
+        acts, q = self._q(obs, T, "train")
+        # what the launch reads, kept for the tests: the two networks' outputs of the last window
+        self.q_online, self.q_target = q.data.view(T, A), (q_t.view(rows_t, A) if rows_t else None)
+        if target_matrix is not None:
+            self.td_targets = target_matrix
+            self.lib.regression_loss(q.data, A, target_matrix, A, None, T, A, int(self.huber), 1.0, 1.0,
+                                     q.ensure_grad(), A, self.scalars, ctx.stream)
+        else:
+            self.td_targets = ctx.buffer(self.q_head.name + "/td_targets", (T, A), tag="train")
+            self.lib.nstep_q_window_loss(q.data, A, q_t, A, rows_t, actions, rewards, game_over, T, A, float(discount),
+                                         int(horizon), int(self.huber), targets, self.td_targets, A, q.ensure_grad(), A,
+                                         self.scalars, self.status, ctx.stream)
+        self.q_head.backward(ctx, acts[-1], q)
         self.torso.backward(ctx, acts)
         if not self.clip_by_global_norm():
             self.grad_norm()

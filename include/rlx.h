@@ -1410,6 +1410,41 @@ int rlx_a3c_window_loss(const float *V, long long ld_v, const float *logits, lon
                         long long ld_dv, float *dlogits, long long ld_dlogits, float *scalars, int *status,
                         void *stream);
 
+/* ------------------------------------------------------------- N-step Q (added entry point) -- */
+/* NStepQAgent.learn_from_batch (agents/n_step_q_agent.py:99-140) between the forward and the backward pass of one update
+ * window of T transitions, one launch of one workgroup.  q_online [T][ld_q] is the online network on the window's
+ * states; q_target [rows_t][ld_t] the TARGET network on the state behind the window (RLX_NSTEPQ_N_STEP: one row) or on
+ * the T next states (RLX_NSTEPQ_ONE_STEP: T rows).  *game_over is the last transition's flag, read on the device (a
+ * window never spans episodes, so only its last row can be terminal).
+ *   targets [T], fp32: the value written into column actions[i] of row i of the online prediction:
+ *     RLX_NSTEPQ_N_STEP    R = 0 on a game over, else max_a q_target[0][a];  R = r_i + discount * R backwards (a
+ *                          sequential fp64 recurrence whose FIRST product is fp32, as the reference's is);
+ *                          target_i = R rounded to fp32 once (:116-125).  A game over reads no target row.
+ *     RLX_NSTEPQ_ONE_STEP  target_i = r_i + ((1 - game_over_i) * discount) * max_a q_target[i][a], fp64 on the widened
+ *                          maximum, rounded to fp32 once (:107-114).
+ *     RLX_NSTEPQ_TARGETS_GIVEN  targets is an INPUT (the taken column of what Architecture.accumulate_gradients is
+ *                          handed, :134); no target row, reward or game-over flag is read (they may be null).
+ *     tests/n_step_q_ref.py names the reference's line of every rounding point.
+ *   td_targets [T][ld_tt], optional (may be null): the full state_value_head_targets matrix — q_online with that column
+ *     replaced — the 'Q Values' signal.
+ *   Q head (csrc/losses_body.hpp, the convention of rlx_regression_loss): e_b = q_online[b][a_b] - target_b, MSE or
+ *     (huber != 0) Huber with delta 1; scalars[0] = loss = (1/T) sum_b l_b; dq[b][a_b] = g_b / T and every other entry of
+ *     dq is exactly 0: the target matrix equals the online prediction there (as for rlx_dqn_head_loss).
+ *   Batch sum: thread partials in row order, then a fixed tree (no atomics).
+ * An action outside [0, n_actions) raises RLX_NSTEPQ_STATUS_BAD_ACTION: the row has no term, a zero dq row, its
+ * td_targets row is the online row and its targets entry is untouched; the mean still divides by T.  A window that is
+ * not a game over with rows_t < 1 (N_STEP), or any window with rows_t < T (ONE_STEP), raises
+ * RLX_NSTEPQ_STATUS_NO_TARGET_ROWS and nothing else is read or written. */
+#define RLX_NSTEPQ_N_STEP 0           /* targets_horizon = 'N-Step' */
+#define RLX_NSTEPQ_ONE_STEP 1         /* targets_horizon = '1-Step' */
+#define RLX_NSTEPQ_TARGETS_GIVEN -1
+#define RLX_NSTEPQ_STATUS_BAD_ACTION 1
+#define RLX_NSTEPQ_STATUS_NO_TARGET_ROWS 2
+int rlx_nstep_q_window_loss(const float *q_online, long long ld_q, const float *q_target, long long ld_t, int rows_t,
+                            const int *actions, const float *rewards, const unsigned char *game_over, int T,
+                            int n_actions, double discount, int horizon, int huber, float *targets, float *td_targets,
+                            long long ld_tt, float *dq, long long ld_dq, float *scalars, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
