@@ -320,6 +320,8 @@ A3C_TARGETS_GIVEN = CONSTANTS["RLX_A3C_TARGETS_GIVEN"]     # rlx_a3c_window_loss
 # rlx_nstep_q_window_loss: the targets horizon by the reference's name; TARGETS_GIVEN reads the targets it is handed
 NSTEPQ_HORIZON = {"N-Step": CONSTANTS["RLX_NSTEPQ_N_STEP"], "1-Step": CONSTANTS["RLX_NSTEPQ_ONE_STEP"]}
 NSTEPQ_TARGETS_GIVEN = CONSTANTS["RLX_NSTEPQ_TARGETS_GIVEN"]
+# rlx_acer_window_loss's mode bits: the trust-region step on the gradient; the window's arrays are handed in, not computed
+ACER_TRUST_REGION, ACER_TARGETS_GIVEN = CONSTANTS["RLX_ACER_TRUST_REGION"], CONSTANTS["RLX_ACER_TARGETS_GIVEN"]
 ACT = {None: CONSTANTS["RLX_ACT_NONE"]}         # activation codes by name: {None: 0, "none": 0, "relu": 1, "tanh": 2}
 ACT.update((k[len("RLX_ACT_"):].lower(), v) for k, v in CONSTANTS.items() if k.startswith("RLX_ACT_"))
 

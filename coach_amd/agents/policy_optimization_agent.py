@@ -2,8 +2,8 @@
 rl_coach/agents/policy_optimization_agent.py (PolicyGradientRescaler :30-39, PolicyOptimizationAgent :45-162) for N
 lockstep envs.  Its simplest member is PolicyGradientsAgent (agents/policy_gradients_agent.py); ActorCriticAgent
 (agents/actor_critic_agent.py) bootstraps; NStepQAgent (agents/n_step_q_agent.py) trains a Q head with a target network
-from the same windows and acts epsilon-greedily (`_make_exploration_policy`); an ACER agent would be a subclass with
-its own network, its own `_window_device` and its own head.
+from the same windows and acts epsilon-greedily (`_make_exploration_policy`); ACERAgent (agents/acer_agent.py) trains
+every window at once and adds replayed windows of complete episodes (`_make_episode_buffer`).
 
 Every env is ONE reference agent's episode buffer (memories/episodic/single_episode_buffer.py: a staging buffer
 [n_env, L]) with its own `last_gradient_update_step_idx`; the envs share the network, the per-timestep statistics and
@@ -73,7 +73,7 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
         self.A = int(ep.num_actions)
         self.policy_gradient_rescaler = getattr(alg, "policy_gradient_rescaler", None)      # :49-51
         self.networks = {"main": self._make_network(tuple(ep.observation_shape), self.ap.network_wrappers["main"])}
-        self.memory = SingleEpisodeBuffer(self.device, self.n_env, tuple(ep.observation_shape), self.L)
+        self.memory = self._make_episode_buffer(tuple(ep.observation_shape))
         self.exploration_policy = self._make_exploration_policy()
         dev, n, L = self.device, self.n_env, self.L
         self.actions = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -95,6 +95,10 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
 
     def _make_network(self, obs_shape, wrapper):
         raise NotImplementedError
+
+    def _make_episode_buffer(self, obs_shape):
+        """the staging buffer of the running episodes; ACER's also keeps the acting probabilities and feeds a replay"""
+        return SingleEpisodeBuffer(self.device, self.n_env, obs_shape, self.L)
 
     def _make_exploration_policy(self):
         """the family acts by a categorical draw on the policy head; a value-based member (N-step Q) gives its own"""

@@ -88,3 +88,14 @@ class VHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='v_head_params', rescale_gradient_from_head_by_factor=1.0,
                  loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class ACERPolicyHeadParameters(HeadParameters):
+    """ACERPolicyHeadParameters (head_parameters.py:225-232): for a discrete action space one Dense layer of A policy
+    values ('fc') under a softmax (heads/acer_policy_head.py:115-125).  The truncated importance-weighted loss, the bias
+    correction, the KL to the average policy and the optional trust-region step come from rlx_acer_window_loss."""
+    head_type = "ACERPolicyHead"
+
+    def __init__(self, activation_function='relu', name='acer_policy_head_params',
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

@@ -30,7 +30,10 @@ the calls of architecture.py:26-237 and tensorflow_components/architecture.py:31
     ActorCriticAgent.learn_from_batch feeds it (actor_critic_agent.py:175-177): inputs 'observation' and 'output_1_0' =
     actions, targets = [value targets, advantages]; predict -> [V, the action probabilities];
   * N-step Q (`NStepQNetworkParameters`): embedder -> FC middleware -> QHead with a target copy, fed the way
-    NStepQAgent.learn_from_batch feeds it (n_step_q_agent.py:134): targets = [the full target matrix]; predict -> Q.
+    NStepQAgent.learn_from_batch feeds it (n_step_q_agent.py:134): targets = [the full target matrix]; predict -> Q;
+  * ACER (`ACERNetworkParameters`): embedder -> FC middleware -> QHead + ACERPolicyHead with a target copy (the average
+    policy network), fed the way ACERAgent._learn_from_batch feeds it (acer_agent.py:157-165): 'output_1_0' ...
+    'output_1_5' and targets = [the aliased Q matrix, the state values]; predict -> [Q, the action probabilities].
 
 One device network (`coach_amd.nn.networks.DQNNet`) holds the online and the target weights in one
 allocation; the `…/online` and `…/target` HipArchitecture objects of a NetworkWrapper are two views of
@@ -44,8 +47,9 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import (ActorCriticNet, ClippedPPONet, DQNNet, NStepQNet, PolicyGradientNet,
-                           actor_critic_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs, policy_gradient_net_kwargs)
+from ..nn.networks import (ACERNet, ActorCriticNet, ClippedPPONet, DQNNet, NStepQNet, PolicyGradientNet,
+                           acer_net_kwargs, actor_critic_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs,
+                           policy_gradient_net_kwargs)
 from .architecture import Architecture
 
 
@@ -733,7 +737,80 @@ class NStepQArchitecture(HipArchitecture):
         return total_loss, [total_loss], float(net.norm.item()), []
 
 
+# =================================================================================== ACER
+class ACERArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> QHead (head 0) + ACERPolicyHead (head 1) with a target copy (the average policy
+    network), fed the way ACERAgent._learn_from_batch feeds it (acer_agent.py:157-165): inputs 'observation',
+    'output_1_0' = actions, 'output_1_1' = rho (B, A), 'output_1_2' = rho_i (B,), 'output_1_3' = the aliased Q values
+    (B, A), 'output_1_4' = Q_retrace (B,), 'output_1_5' = the average policy (B, A); targets = [the Q head's target
+    matrix (B, A), the state values (B,)] (rlx_acer_window_loss with RLX_ACER_TARGETS_GIVEN).  predict -> [Q (B, A),
+    action probabilities (B, A)], of the online or the target view; accumulate_gradients -> total loss, [Q loss, policy
+    loss (, the entropy regulariser)], the gradients' norm; fetches: probability_loss, bias_correction_loss,
+    kl_divergence of head 1."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        if not hasattr(spaces.action, "actions"):
+            raise ValueError("only discrete action spaces are supported for ACER")
+        return ACERNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
+                       len(spaces.action.actions), **acer_net_kwargs(np_, agent_parameters.algorithm, seed))
+
+    def _handles(self):
+        self.inputs = ['observation'] + ['output_1_%d' % i for i in range(6)]
+        self.output_heads = [_HeadFetches(0, ['output']),
+                             _HeadFetches(1, ['probability_loss', 'bias_correction_loss', 'kl_divergence', 'output'])]
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        net, tag = self.net, "%s_%d" % (tag, B)
+        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
+        if self.is_target:
+            acts = net.torso.forward(net.ctx, net.obs_tensor(obs, B), tag=tag + "_t", weights=net.target)
+            q = net.q_head.forward(net.ctx, acts[-1], tag=tag + "_t", weights=net.target).data.view(B, net.A)
+            z = net.pi_head.forward(net.ctx, acts[-1], tag=tag + "_t", weights=net.target).data.view(B, net.A)
+        else:
+            q, z = net.predict(obs, B, tag=tag)
+        net.lib.softmax(z, net.A, B, net.A, probs, net.A, _rlx.current_stream())
+        return [q, probs]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        obs, B = self._observation(inputs)
+        missing = [n for n in self.inputs[1:] if n not in inputs]
+        if missing:
+            raise ValueError("the ACER policy head needs the inputs {}".format(missing))
+        if not isinstance(targets, (list, tuple)) or len(targets) != 2:
+            raise ValueError("targets must be [the Q head's target matrix, the state values]")
+        f32 = lambda v, shape: self._to_device(v, torch.float32).reshape(shape).contiguous()
+        actions = self._to_device(inputs['output_1_0'], torch.int32).reshape(-1).contiguous()
+        if actions.numel() != B:
+            raise ValueError("output_1_0 must hold one action per sample")
+        A = net.A
+        try:
+            given = dict(rho=f32(inputs['output_1_1'], (B, A)), rho_i=f32(inputs['output_1_2'], (B,)),
+                         td_targets=f32(inputs['output_1_3'], (B, A)), q_retrace=f32(inputs['output_1_4'], (B,)),
+                         avg_policy=f32(inputs['output_1_5'], (B, A)), V=f32(targets[1], (B,)))
+            q_targets = f32(targets[0], (B, A))
+        except RuntimeError as e:
+            raise ValueError("an ACER input does not have its shape for a batch of {}: {}".format(B, e))
+        # the reference hands ONE array as 'output_1_3' and as the Q head's target; the launch reads it once
+        if not torch.equal(q_targets, given["td_targets"]):
+            raise ValueError("the Q head's targets must be the matrix handed in as output_1_3 (the reference aliases them)")
+        net.window_gradients(obs, B, False, actions, given=given)
+        sc = net.scalars.cpu().numpy()
+        net.check_status()
+        head = self.output_heads[1]
+        table = {head.probability_loss: lambda: sc[3], head.bias_correction_loss: lambda: sc[4],
+                 head.kl_divergence: lambda: sc[5]}
+        if any(f not in table for f in additional_fetches):
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        losses = [float(sc[1]), float(sc[2])]
+        if net.beta_entropy:                             # the regulariser is a loss of its own (acer_policy_head.py:56-58)
+            losses.append(float(-np.float32(net.beta_entropy) * sc[6]))
+        return float(sc[0]), losses, float(net.norm.item()), [table[f]() for f in additional_fetches]
+
+
 _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
+                       "ACERNetworkParameters": ACERArchitecture,
                        "ActorCriticNetworkParameters": ActorCriticArchitecture,
                        "NStepQNetworkParameters": NStepQArchitecture,
                        "SACPolicyNetworkParameters": SACPolicyArchitecture,

@@ -1,5 +1,5 @@
 """`SingleEpisodeBuffer` (rl_coach/memories/episodic/single_episode_buffer.py:21-33) for N lockstep envs: the memory
-of the on-policy agents that learn from the running episode (Policy Gradients, Actor-Critic; ACER later).
+of the on-policy agents that learn from the running episode (Policy Gradients, Actor-Critic, N-step Q, ACER).
 
 In the reference the memory holds ONE finished episode and the agent trains from its `current_episode_buffer`, a list
 of Transition objects.  Here both are one staging buffer per env: row (e, t) of `obs` / `action` / `reward` is step t
@@ -14,6 +14,8 @@ late.  A bootstrapping agent (Actor-Critic) also reads the stored `game_over` by
 behind the window: for a running episode that is row `end` of the env's rows, already written (the state the step whose
 response is not yet counted started from), so the window's T + 1 states are `obs[start : end + 1]` in place; for a
 finished episode it is `next_obs[end - 1]`, the observation BEFORE the reset (`last_next_state`).
+ACER adds two things, both optional: a per-row column `mu` for the behaviour policy's probabilities of the acting step,
+and a replay of complete episodes (memories/episodic/episode_store.py) that receives an env's rows when its episode ends.
 Evaluation never writes: `begin_evaluation` only redirects the acting state, as the device replays do.
 """
 import numpy as np
@@ -30,7 +32,12 @@ class SingleEpisodeBufferParameters(MemoryParameters):                  # single
 
 
 class SingleEpisodeBuffer(Memory):
-    def __init__(self, device=None, n_env=1, observation_shape=None, max_episode_length=None):
+    def __init__(self, device=None, n_env=1, observation_shape=None, max_episode_length=None,
+                 action_probabilities=0, replay=None):
+        """action_probabilities: A > 0 adds a per-row column [rows, A] for the behaviour policy's probabilities of the
+        acting step (ACER's info['all_action_probabilities']), written by the step's one copy launch; replay: an
+        EpisodeStore that receives every finished episode's rows (ACER).  Without them the rows and launches are the
+        on-policy agents'."""
         super().__init__((MemoryGranularity.Episodes, 1))                   # single_episode_buffer.py:33
         if device is None or observation_shape is None or not max_episode_length:
             raise ValueError("the device episode buffer needs a device, an observation shape and the episode limit")
@@ -45,6 +52,9 @@ class SingleEpisodeBuffer(Memory):
         self.reward = torch.zeros(rows, dtype=torch.float32, device=device)
         self.game_over = torch.zeros(rows, dtype=torch.uint8, device=device)
         self.next_obs = torch.zeros(rows, self.obs_dim, dtype=torch.float32, device=device)     # before the reset
+        self.mu = torch.zeros(rows, int(action_probabilities), dtype=torch.float32, device=device) \
+            if action_probabilities else None
+        self.replay = replay
         self.cur_state = torch.empty(self.n_env, self.obs_dim, dtype=torch.float32, device=device)
         self._eval_state = torch.empty_like(self.cur_state)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
@@ -106,9 +116,10 @@ class SingleEpisodeBuffer(Memory):
         self.reset(first_obs)
 
     def store(self, actions, rewards, game_overs, next_obs, reset_obs, record=True, dones=None, defer=False,
-              episode_end=False, dones_host=None):
+              episode_end=False, dones_host=None, action_probabilities=None):
         """one transition per env at its own position, then the envs' next current state (the post-reset observation
-        where the episode ended).  record=False (evaluation) only advances the state."""
+        where the episode ended).  record=False (evaluation) only advances the state.  action_probabilities [n_env, A]:
+        the acting step's probabilities, one more pair of the copy launch when the buffer has the column."""
         s = _rlx.current_stream()
         stored_game_overs = game_overs
         if dones is not None:
@@ -124,10 +135,17 @@ class SingleEpisodeBuffer(Memory):
             dst = self._dst.push((np.arange(self.n_env) * self.L + self.steps).astype(np.int32))
             pairs = [(actions, self.action), (rewards, self.reward), (state, self.obs),
                      (stored_game_overs, self.game_over), (next_obs, self.next_obs)]
+            if self.mu is not None:
+                if action_probabilities is None:
+                    raise ValueError("the episode buffer has a column for the acting step's action probabilities")
+                pairs.append((action_probabilities, self.mu))
             self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, dst, 0, 0, self.n_env, self.rows,
                                   self.n_env, self.status, s)
             self.steps += 1
             ended = np.asarray(dones_host, dtype=bool)
+            if self.replay is not None:                  # store_episode (agent.py:576-580), in env order
+                for e in np.nonzero(ended)[0].tolist():
+                    self.replay.append_episode(self, e, int(self.steps[e]))
             self.last_episode_lengths[ended] = self.steps[ended]
             self.steps[ended] = 0
         self.lib.select_rows(game_overs, reset_obs, next_obs, state, self.n_env, self.obs_dim * 4, s)

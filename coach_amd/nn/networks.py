@@ -1288,3 +1288,139 @@ class NStepQNet(_WindowAccumulatingNet):
         if not self.clip_by_global_norm():
             self.grad_norm()
         return self.loss
+
+
+def acer_net_kwargs(np_, alg, seed):
+    """ACERNetworkParameters + the algorithm's head constants -> the keywords of ACERNet's constructor"""
+    heads = {h.head_type: h for h in np_.heads_parameters}
+    return dict(policy_gradient_net_kwargs(np_, alg, seed), q_loss_weight=heads["QHead"].loss_weight,
+                importance_weight_truncation=alg.importance_weight_truncation, max_kl_divergence=alg.max_KL_divergence,
+                trust_region=bool(getattr(alg, "apply_trust_region_to_gradients", False)))
+
+
+class ACERNet(_WindowAccumulatingNet):
+    """ACERNetworkParameters (agents/acer_agent.py:78-87): one embedder + FC middleware tower under two heads — head 0 =
+    the plain QHead (Dense(feat, A), the layer and initialisation of NStepQNet's; MSE under loss_weight 0.5), head 1 =
+    ACERPolicyHead (Dense(feat, A) named 'fc', default initialisation) — with a target copy, which is the AVERAGE policy
+    network; gradients clipped by global norm at 40.  Everything between the forward and the backward pass of an update
+    window — state values, importance weights, the Q-retrace targets, both heads' losses and gradients — is ONE launch,
+    rlx_acer_window_loss (csrc/acer.hip).  A window's gradients REPLACE the accumulation buffer and are applied at
+    once (NetworkWrapper.train_and_sync_networks, network_wrapper.py:156-177: accumulate_gradients(no_accumulation=True),
+    then apply_gradients without a reset); the buffer keeps them, so the base's apply step applies the last window's
+    gradients once more and then clears them (:179-203).  `adam_steps` counts the Adam steps."""
+
+    def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
+                 learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=40.0,
+                 beta_entropy=0.0, q_loss_weight=0.5, importance_weight_truncation=10.0, max_kl_divergence=1.0,
+                 trust_region=False, seed=0):
+        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        if not 1 <= self.A <= 18:
+            raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % self.A)
+        self.clip_gradients = clip_gradients
+        self.beta_entropy, self.q_loss_weight = float(beta_entropy), float(q_loss_weight)
+        self.truncation, self.max_kl = float(importance_weight_truncation), float(max_kl_divergence)
+        self.trust_region = bool(trust_region)
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        self.q_head = G.Dense(self.params, "main/q_head/dense", feat, self.A, None, 1)
+        self.pi_head = G.Dense(self.params, "main/acer_policy_head/fc", feat, self.A, None, 1)
+        self.heads = [self.q_head, self.pi_head]
+        self.modules = [self.torso] + self.heads
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=True)
+        self._finish_accumulating(7)
+        sc = self.scalars
+        self.loss, self.q_loss, self.policy_loss, self.probability_loss = sc[0:1], sc[1:2], sc[2:3], sc[3:4]
+        self.bias_correction_loss, self.kl_divergence, self.entropy = sc[4:5], sc[5:6], sc[6:7]
+        self.bootstrap_value = torch.zeros(1, dtype=torch.float32, device=device)
+        self.adam_steps = 0
+        self._window = {}
+
+    def policy_values(self, obs, B, tag="act"):
+        """the policy head's Dense output [B, A] (logits of the action probabilities); the Q head is not run"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
+        return self.pi_head.forward(self.ctx, acts[-1], tag=tag)
+
+    def _heads_forward(self, x_q, x_pi, tag):
+        """both heads in one launch where the narrow-dense kernels serve the heads' width"""
+        if self.A <= G.SMALL_N:
+            return G.small_dense_forward_multi(self.ctx, [(self.q_head, x_q), (self.pi_head, x_pi)], tag=tag)
+        return self.q_head.forward(self.ctx, x_q, tag=tag), self.pi_head.forward(self.ctx, x_pi, tag=tag)
+
+    def predict(self, obs, B, tag="predict"):
+        """both heads of the ONLINE network -> (Q [B, A], logits [B, A]) as buffers"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
+        q, z = self._heads_forward(acts[-1], acts[-1], tag)
+        return q.data.view(B, self.A), z.data.view(B, self.A)
+
+    def average_policy_values(self, obs, B, tag="avg"):
+        """the AVERAGE (target) network's policy logits [B, A]"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=self.target)
+        return self.pi_head.forward(self.ctx, acts[-1], tag=tag, weights=self.target).data.view(B, self.A)
+
+    def window_buffers(self, T):
+        """the window's arrays the launch writes (or, given, reads): V, rho, rho_i, avg_policy, q_retrace, td_targets"""
+        w = self._window.get(T)
+        if w is None:
+            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)
+            w = self._window[T] = dict(V=z(T), rho=z(T, self.A), rho_i=z(T), avg_policy=z(T, self.A), q_retrace=z(T),
+                                       td_targets=z(T, self.A))
+        return w
+
+    def window_gradients(self, obs_rows, T, bootstrap, actions, mu=None, rewards=None, game_over=None, discount=0.0,
+                         given=None):
+        """the online network forward on the T states of one update window and, with bootstrap, on the state behind them
+        (obs_rows has T + bootstrap rows), the average network's policy head on the T states; rlx_acer_window_loss
+        against (mu, actions, rewards, the device's game-over flag), which leaves the window's arrays in
+        self.window — or, with `given` (a dict of them: what Architecture.accumulate_gradients is handed), reads them;
+        both heads backward, their input gradients summed; the torso backward: the gradients in params.grads (clipped
+        when clip_gradients is set), the seven scalars in self.scalars, tf.global_norm of the raw gradients in
+        self.norm.  The context's buffers are keyed by shape; the means divide by T."""
+        ctx, A = self.ctx, self.A
+        rows = T + int(bool(bootstrap))
+        mode = _rlx.ACER_TRUST_REGION if self.trust_region else 0
+        if given is None:
+            w = self.window_buffers(T)
+            avg_z = self.average_policy_values(obs_rows, T, tag="train_avg")
+        else:
+            w, avg_z, mode = given, None, mode | _rlx.ACER_TARGETS_GIVEN
+        self.window = w
+        acts = self.torso.forward(ctx, self.obs_tensor(obs_rows, rows), tag="train")
+        feat = acts[-1]
+        feat.ensure_grad()
+        # each head writes its input gradient into a buffer of its own; they are added into feat.grad below
+        side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
+        side.grad = ctx.buffer(self.pi_head.name + "/input:grad", tuple(feat.data.shape), tag="train")
+        q, z = self._heads_forward(feat, side, "train")
+        self.q_online, self.logits = q.data.view(rows, A), z.data.view(rows, A)    # what the launch reads (for the tests)
+        self.lib.acer_window_loss(q.data, A, z.data, A, rows, avg_z, A, mu, A, actions, rewards, game_over, T, A,
+                                  float(discount), self.truncation, self.max_kl, self.beta_entropy, self.q_loss_weight,
+                                  mode, w["V"], w["rho"], A, w["rho_i"], w["avg_policy"], A, w["q_retrace"],
+                                  self.bootstrap_value, w["td_targets"], A, q.ensure_grad(), A, z.ensure_grad(), A,
+                                  self.scalars, self.status, ctx.stream)
+        if A <= G.SMALL_N and rows * A <= 1024:
+            G.small_dense_backward_multi(ctx, [(self.q_head, feat, q), (self.pi_head, side, z)])
+        else:
+            self.q_head.backward(ctx, feat, q)
+            self.pi_head.backward(ctx, side, z)
+        self.lib.axpby(feat.grad, 1.0, feat.grad, 1.0, side.grad, feat.grad.numel(), ctx.stream)
+        feat.grad_is_dz = feat.grad_is_dz and side.grad_is_dz
+        self.torso.backward(ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss
+
+    def train_window(self, *args, rate=None, **kw):
+        """train_and_sync_networks (network_wrapper.py:156-177): the window's gradients replace the accumulation buffer
+        and are applied at once, the buffer is NOT cleared; then the average network moves by `rate`
+        (acer_agent.py:167-168)"""
+        loss = self.window_gradients(*args, **kw)
+        self.accumulated.copy_(self.params.grads)
+        self.adam.step(1.0, grads=self.accumulated)
+        self.adam_steps += 1
+        if rate is not None:
+            self.update_target(rate)
+        return loss
+
+    def apply_accumulated(self, grad_scale=1.0):
+        super().apply_accumulated(grad_scale)
+        self.adam_steps += 1

@@ -1445,6 +1445,60 @@ int rlx_nstep_q_window_loss(const float *q_online, long long ld_q, const float *
                             int n_actions, double discount, int horizon, int huber, float *targets, float *td_targets,
                             long long ld_tt, float *dq, long long ld_dq, float *scalars, int *status, void *stream);
 
+/* ------------------------------------------------------------------ ACER (added entry point) -- */
+/* ACERAgent._learn_from_batch (agents/acer_agent.py:118-165) between the forward and the backward pass of one update
+ * window of T transitions, one launch of one workgroup.  q / logits [rows][ld] are the online network's Q head and policy
+ * head: rows = T + 1 when the window bootstraps (the last row is the state behind the window), rows = T is allowed when
+ * the last transition is a game over.  avg_logits [T][ld] is the average (target) network's policy head on the T
+ * states, mu [T][ld_mu] the behaviour policy's stored probabilities.  *game_over is the last transition's flag, read on
+ * the device.
+ *   Phase 1, per row (arrays that are outputs; the 'Values' signal reads V):
+ *     p = softmax(logits) and avg_policy = softmax(avg_logits) as csrc/policy_head.hpp defines it;
+ *     V_b = np.sum(p * Q) in numpy's own order (a plain loop below 8 actions, eight accumulators from 8 on);
+ *     rho = p / (mu + eps);  rho_i = rho[b][a_b];  *bootstrap_value = np.sum(Q * p) of row T (0 on a game over).
+ *   Phase 2, q_retrace [T], fp32: Qret = 0 on a game over, else *bootstrap_value; backwards, sequentially,
+ *     Qret = r_i + discount * Qret (fp64, but the FIRST product is fp32, as the reference's is); q_retrace_i = Qret
+ *     rounded to fp32 once; Qret = min(1, rho_i) * (Qret - Q[i][a_i]) + V_i in fp64.  tests/acer_ref.py names the
+ *     reference's line of every rounding point.
+ *   td_targets [T][ld_tt], optional (may be null): q with the taken entries replaced by q_retrace — the Q head's target
+ *     AND, because the reference aliases the two arrays, the Q values the policy head is fed (Q').
+ *   Phase 3, per row.  Q head (csrc/losses_body.hpp, the convention of rlx_regression_loss): e_b = q[b][a_b] -
+ *     q_retrace_b, MSE; scalars[1] = (1/T) sum_b q_loss_weight * e_b^2; dq[b][a_b] = q_loss_weight * 2 e_b / T and every
+ *     other entry of dq exactly 0.  ACER policy head (csrc/acer_head.hpp; acer_policy_head.py:47-113), with log pi, H of
+ *     the discrete policy row:
+ *       scalars[3] = probability loss     = -(1/T) sum_b log pi_b(a_b) (q_retrace_b - V_b) min(truncation, rho_i_b)
+ *       scalars[4] = bias-correction loss = -(1/T) sum_b sum_k log(p_k + eps) (Q'_k - V_b) relu(1 - truncation /
+ *                                            (rho_k + eps)) p_k   (the trailing p_k under stop_gradient)
+ *       scalars[2] = policy loss = scalars[3] + scalars[4];   scalars[6] = mean entropy;
+ *       scalars[5] = (1/T) sum_b KL(Categorical(avg_policy + eps) || Categorical(p + eps)), logged only;
+ *       scalars[0] = total = scalars[1] + (scalars[2] - beta_entropy * scalars[6]).
+ *     dlogits = dz_j = p_j (g_j - sum_k g_k p_k) with g = dL/dp of the row.  With RLX_ACER_TRUST_REGION in `mode`, g first
+ *     goes through the reference's trust_region_layer gradient (g' = -g T; k = -avg_policy / (p + eps); adj = relu((sum
+ *     k g' - max_kl) / (sum k^2 + eps)); g' -= adj k; g = -g' / T).  The reference's own graph never routes a gradient
+ *     through that layer, so the faithful mode is without the bit.
+ *   Every mean divides by T; the bootstrap row has no term and exactly zero dq and dlogits rows.  Batch sums: thread
+ *   partials in row order, then a fixed tree (no atomics).
+ * RLX_ACER_TARGETS_GIVEN in `mode`: phases 1 and 2 are skipped; V, rho, rho_i, avg_policy and q_retrace are INPUTS (what
+ *   Architecture.accumulate_gradients is handed: target 1, output_1_1, output_1_2, output_1_5, output_1_4), td_targets,
+ *   when not null, is read as Q' (output_1_3), else Q' is q with the taken entry replaced; avg_logits, mu, rewards,
+ *   game_over and bootstrap_value are not touched (they may be null) and nothing is bootstrapped.
+ * An action outside [0, n_actions) raises RLX_ACER_STATUS_BAD_ACTION: the row has no term and zero gradient rows, its
+ * td_targets row is the online row, and the recurrence passes V_i on (rho_i = 0); the means still divide by T.  A window
+ * that is not a game over with rows = T raises RLX_ACER_STATUS_NO_BOOTSTRAP_ROW and nothing else is read or written.
+ * 1 <= n_actions <= 18, any T >= 1. */
+#define RLX_ACER_TRUST_REGION 1
+#define RLX_ACER_TARGETS_GIVEN 2
+#define RLX_ACER_STATUS_BAD_ACTION 1
+#define RLX_ACER_STATUS_NO_BOOTSTRAP_ROW 2
+int rlx_acer_window_loss(const float *q, long long ld_q, const float *logits, long long ld_logits, int rows,
+                         const float *avg_logits, long long ld_avg_logits, const float *mu, long long ld_mu,
+                         const int *actions, const float *rewards, const unsigned char *game_over, int T, int n_actions,
+                         double discount, float truncation, float max_kl, float beta_entropy, float q_loss_weight,
+                         int mode, float *V, float *rho, long long ld_rho, float *rho_i, float *avg_policy,
+                         long long ld_avg_policy, float *q_retrace, float *bootstrap_value, float *td_targets,
+                         long long ld_tt, float *dq, long long ld_dq, float *dlogits, long long ld_dlogits,
+                         float *scalars, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
