@@ -285,7 +285,7 @@ STRUCT_NAMES = {          # rlx.h structure -> its class in this module (bound b
     "rlx_small_dense_problem": "SmallDenseProblem", "rlx_mlp_dqn_desc": "MlpDqnDesc", "rlx_mlp3": "Mlp3",
     "rlx_fused_net": "FusedNet", "rlx_td3_fused_desc": "Td3FusedDesc", "rlx_sac_fused_desc": "SacFusedDesc",
     "rlx_ppo_fc_heads_desc": "PpoFcHeadsDesc", "rlx_ppo_rows_desc": "PpoRowsDesc", "rlx_observe_desc": "ObserveDesc",
-    "rlx_signal_source": "SignalSource",
+    "rlx_signal_source": "SignalSource", "rlx_adam_split_desc": "AdamSplitDesc",
 }
 _TEXT = header_text()
 STRUCTS = parse_structs(_TEXT, STRUCT_NAMES)
@@ -298,6 +298,7 @@ Mlp3, FusedNet = STRUCTS["rlx_mlp3"], STRUCTS["rlx_fused_net"]
 Td3FusedDesc, SacFusedDesc = STRUCTS["rlx_td3_fused_desc"], STRUCTS["rlx_sac_fused_desc"]
 PpoFcHeadsDesc, PpoRowsDesc = STRUCTS["rlx_ppo_fc_heads_desc"], STRUCTS["rlx_ppo_rows_desc"]
 ObserveDesc, SignalSource = STRUCTS["rlx_observe_desc"], STRUCTS["rlx_signal_source"]
+AdamSplitDesc = STRUCTS["rlx_adam_split_desc"]
 
 
 class SplitkJob(STRUCTS["rlx_splitk_job"]):
@@ -396,9 +397,11 @@ def conv_dw_item(x, x_tower_stride, x_is_u8, a_div, dz, dz_tower_stride, B, H, W
     return it
 
 
-def conv_dw_multi(items, jobs, stream=None):
+def conv_dw_multi(items, jobs, stream=None, adam=None):
     """rlx_conv_dw_multi: the convolution layers' weight gradients of one backward pass as ONE launch; jobs[i] receives
-    item i's outstanding reduction (the SAME SplitkJob objects the caller commits)."""
+    item i's outstanding reduction (the SAME SplitkJob objects the caller commits).
+    adam = (AdamSplitDesc, riders, riders_first): rlx_conv_dw_multi_adam — the same launch also steps the early Adam blocks.
+    Such a call changes weights, so it is never recorded for replay: not allowed while GEMM_HOOK is set."""
     s = current_stream() if stream is None else stream
     n = len(items)
     arr = (ConvDwItem * n)(*items)
@@ -406,6 +409,12 @@ def conv_dw_multi(items, jobs, stream=None):
 
     def run():
         lib().conv_dw_multi(arr, jarr, n, s)
+    if adam is not None:
+        if GEMM_HOOK is not None:
+            raise RuntimeError("rlx_conv_dw_multi_adam applies an Adam step: it cannot be recorded for replay")
+        desc, riders, first = adam
+        lib().conv_dw_multi_adam(arr, jarr, n, ctypes.byref(desc), int(riders), int(bool(first)), s)
+        run = lambda: None
     if GEMM_HOOK is not None:
         descs = []
         for it in items:

@@ -106,6 +106,11 @@ class ClippedPPOAgent(object):
     # tower rides in the same launches as the policy tower (the fused convolution launch has a workgroup per half image
     # and tower: 128 -> 256 of the chip's 256 CUs).  The flag is for same-process A/Bs and the equivalence test
     RECORD_WHILE_ACTING = True
+    # the Adam step of the parameters whose gradients are final before the convolution weight-gradient launch (the FC layer:
+    # 95 % of the bytes) as rider workgroups of that launch, and only the rest in the launch at the end of the update
+    # (rlx_conv_dw_multi_adam / rlx_adam_tf1_step_late).  Bit-identical to the one-launch step; the flag is
+    # for same-process A/Bs and the equivalence test
+    ADAM_UNDER_CONV_DW = True
     DATASET_CHUNK = 2048    # rows per forward pass of the whole-dataset passes (V(s) for GAE, the old policy): 256 -> 2048 is -1.0 ms per C2 iteration (profiles/r04_ab_ppo_chunk.txt)
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
@@ -637,6 +642,7 @@ class ClippedPPOAgent(object):
 
     def _minibatch_fb(self, m, clip_rescaler, stop_after_dense=False, i=0, epoch=None):
         """epoch: the buffers of _gather_epoch — minibatch i's rows are already in training order."""
+        self._arm_early_adam(stop_after_dense)
         if epoch is not None:
             B = self.ap.network_wrappers["main"].batch_size
             sl = slice(i * B, i * B + m)
@@ -651,7 +657,20 @@ class ClippedPPOAgent(object):
                                                old, clip_rescaler, self.mb_ratio, self.mb_clipped,
                                                stop_after_dense=stop_after_dense)
 
+    EARLY_ADAM_SCALE = 1.0      # the gradient scale of a single-worker update (train_network), fixed when the step is armed
+
+    def _arm_early_adam(self, stop_after_dense=False):
+        """Arms (or disarms) ADAM_UNDER_CONV_DW for the forward / backward pass that follows.  Not with data parallelism
+        (the gradient is not final before its all-reduce), not for a pass that stops after the dense layers, not while
+        bench.py's recorder replays the launches (a replayed launch must never apply Adam); a soft target mix is never
+        part of this network's finish.  Inside a stream capture only with the split built before (train_network)."""
+        net = self.networks["main"]
+        net.disarm_early_adam()
+        if self.ADAM_UNDER_CONV_DW and self.dist is None and not stop_after_dense and _rlx.GEMM_HOOK is None:
+            net.arm_early_adam(self.EARLY_ADAM_SCALE, prepare=not torch.cuda.is_current_stream_capturing())
+
     def _minibatch_finish(self, scale):
+        """the late launch of an armed step (ValueError if `scale` is not the armed one), else the whole step"""
         net = self.networks["main"]
         net.finish_update(scale, signal_acc=self.scalar_acc)
 
@@ -708,6 +727,9 @@ class ClippedPPOAgent(object):
         # (a decaying clipping_decay_schedule, presets/Mujoco_ClippedPPO.py, would otherwise re-capture every phase)
         self.networks["main"].set_clip_rescaler(float(alg.clipping_decay_schedule.current_value))
         clip = None
+        early = bool(self.ADAM_UNDER_CONV_DW and self.dist is None)     # (part of the graph keys: the captured launches differ)
+        if early:
+            self.networks["main"].prepare_early_adam()                  # device lists of the split: built outside any capture
         scale = self.dist.grad_scale(netp.scale_down_gradients_by_number_of_workers_for_sync_training) \
             if self.dist else 1.0
         results = []
@@ -753,13 +775,13 @@ class ClippedPPOAgent(object):
                         else:
                             reduced_fb(min(B, n - i * B), i, e)
                         self._minibatch_finish(scale)
-                self._run(("epoch", n, clip, scale, self.dist is not None and self.overlap_allreduce), epoch)
+                self._run(("epoch", n, clip, scale, self.dist is not None and self.overlap_allreduce, early), epoch)
                 results.append(self.scalar_acc / nmb)
                 continue
             for i in range(nmb):
                 m = min(B, n - i * B)
                 if self.dist is None:
-                    self._run(("mb", m, clip, scale, i), lambda: (self._minibatch_fb(m, clip, i=i),
+                    self._run(("mb", m, clip, scale, i, early), lambda: (self._minibatch_fb(m, clip, i=i),
                                                                   self._minibatch_finish(scale)))
                 elif in_graph:
                     self._run(("mb_dp", m, clip, scale, i, self.overlap_allreduce),

@@ -8,6 +8,11 @@
 // start the next workgroup the moment one finishes: no launch ramp and no tail between the layers (14.7 + 12.9 + 11.6 us
 // as three launches in the Clipped-PPO update).  Same device code (conv_dw_body.hpp), same sums, same partials.
 #include "conv_dw_body.hpp"
+// the Adam riders of rlx_conv_dw_multi_adam: optim.hip's arithmetic, which must not be contracted (this file is not
+// compiled with -ffp-contract=off)
+#pragma clang fp contract(off)
+#include "adam_block_body.hpp"
+#pragma clang fp contract(fast)
 
 namespace {
 
@@ -52,23 +57,59 @@ __global__ void __launch_bounds__(kThreads) conv_dw_multi_kernel(const MultiArgs
     }
 }
 
+// rlx_conv_dw_multi_adam: conv_dw_multi_kernel<4>'s grid plus `riders` workgroups that step the EARLY virtual blocks of the
+// Adam update (adam_block_body.hpp) — parameters whose gradients were final before this launch, here the FC layer's 95 %
+// of the Clipped-PPO network.  The convolution workgroups of the four-pass form take <= 50 KB of LDS, three fit a CU, and
+// the grid only ever fills two of those slots (profiles/r06_ab_conv_dw_passes.txt): a rider streams in the third.  It
+// uses the first 1 KB of the launch's LDS, draws no ticket and hands nothing to anybody inside the launch.
+// first: riders are workgroups [0, riders) (a multiple of 8, so that the bodies' bid & 7 stays the workgroup's XCD),
+// else [conv grid, conv grid + riders).
+__global__ void __launch_bounds__(kThreads)
+conv_dw_multi_adam_kernel(const MultiArgs m, const rlx_adam::EarlyDev e, const int riders, const int first) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    static_assert(kThreads == rlx_adam::kBlock, "a rider is one Adam block");
+    int bid = blockIdx.x;
+    if (first) {
+        if (bid < riders) {
+            rlx_adam::early_blocks(e, bid, riders, smem);
+            return;
+        }
+        bid -= riders;
+    }
+    if (bid < m.nb_u8) {
+        if (m.u8_half) conv_dw_u8_body_half(m.u8, bid, smem);
+        else conv_dw_u8_body_passes<4>(m.u8, bid, smem);
+        return;
+    }
+    bid -= m.nb_u8;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if (bid < m.nb_f[i]) {
+            if (m.kind[i] == 1) conv_dw_f32_body_two_pass<64, 3, 1, 9, 7, 4, 7>(m.f[i], bid, smem);
+            else conv_dw_f32_body_two_pass<32, 4, 2, 20, 9, 5, 9>(m.f[i], bid, smem);
+            return;
+        }
+        bid -= m.nb_f[i];
+    }
+    if (!first && bid < riders) rlx_adam::early_blocks(e, bid, riders, smem);
+}
+
 int g_passes = 2;          // rlx_conv_dw_passes
 int g_pairs_per_wg = 0;    // rlx_conv_dw_pairs_per_workgroup (0: by the number of workgroups)
 // image pairs per workgroup of an fp32 item: two where (tower, pair) units are plentiful (the Clipped-PPO minibatch: 2 x 32 —
 // same launch time, half the partial sums: 8.9 MB less written and read back per update, profiles/r06_ab_conv_dw_pairs.txt),
 // one where that would leave CUs without work (the DQN update's 16 pairs: 165.8 against 156.7 ms per C3 step)
-inline int pairs_per_wg(int B, int towers) {
-    if (g_passes <= 1) return 1;
+inline int pairs_per_wg(int B, int towers, int passes) {
+    if (passes <= 1) return 1;
     if (g_pairs_per_wg > 0) return g_pairs_per_wg;
     return towers * ((B + 1) / 2) >= 64 ? 2 : 1;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rlx_conv_dw_multi(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n_items, void *stream) {
+// adam: rlx_conv_dw_multi_adam — the four-pass bodies whatever g_passes says, and `riders` Adam workgroups in the same launch
+int conv_dw_multi_impl(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n_items, void *stream,
+                       const rlx_adam_split_desc *adam, int riders, int riders_first) {
     RLX_REQUIRE(items && jobs && n_items >= 1 && n_items <= 3, "rlx_conv_dw_multi: 1 .. 3 items");
+    const int passes = adam ? 4 : g_passes;
     // the one-launch form: at most one uint8 item of the Atari geometry and up to two fp32 items; anything else goes out item by item
     int n_u8 = 0, n_f = 0;
     bool one = n_items >= 2;
@@ -84,7 +125,7 @@ int rlx_conv_dw_multi(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n
             iu = &it; ju = i; ++n_u8;
         } else {
             one = n_f < 2 && geometry_f32(it.B, it.H, it.W, it.C, it.KH, it.KW, it.S, it.filters, it.towers, &gf[n_f < 2 ? n_f : 1],
-                                          pairs_per_wg(it.B, it.towers));
+                                          pairs_per_wg(it.B, it.towers, passes));
             if (n_f < 2) { fi[n_f] = &it; jf[n_f] = i; }
             ++n_f;
         }
@@ -101,7 +142,7 @@ int rlx_conv_dw_multi(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n
                                   it.db_tower_stride, it.workspace, it.workspace_floats, &jobs[i], stream);
             if (rc != RLX_OK) return rc;
         }
-        return RLX_OK;
+        return adam ? rlx_adam_tf1_step_early(adam, riders, stream) : RLX_OK;
     }
     MultiArgs m;
     m.nb_u8 = m.nb_f[0] = m.nb_f[1] = 0;
@@ -143,7 +184,7 @@ int rlx_conv_dw_multi(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n
         a.x = static_cast<const float *>(it.x); a.x_ts = it.x_tower_stride; a.dz = it.dz; a.dz_ts = it.dz_tower_stride;
         a.part = it.workspace; a.cpart = it.db ? it.workspace + (size_t)it.towers * g.splits * g.K * kN : nullptr;
         a.B = it.B; a.H = it.H; a.OH = g.OH; a.KH = it.KH; a.splits = g.splits; a.units = it.towers * g.splits;
-        a.ppw = pairs_per_wg(it.B, it.towers);
+        a.ppw = pairs_per_wg(it.B, it.towers, passes);
         a.stamps = nullptr;
         m.nb_f[k] = ((a.units + 7) / 8) * 8 * it.KH;
         m.kind[k] = g.kind;
@@ -162,24 +203,50 @@ int rlx_conv_dw_multi(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_multi_kernel<4>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_multi_adam_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         configured = true;
     }
     const unsigned grid = m.nb_u8 + m.nb_f[0] + m.nb_f[1];
-    if (g_passes > 1) {
+    if (passes > 1) {
         // per-body LDS of the multi-pass forms
-        size_t lds2 = iu ? (m.u8_half ? lds_u8_half() : (g_passes == 4 ? lds_u8_passes<4>() : lds_u8_passes<2>())) : 0;
+        size_t lds2 = iu ? (m.u8_half ? lds_u8_half() : (passes == 4 ? lds_u8_passes<4>() : lds_u8_passes<2>())) : 0;
         for (int k = 0; k < 2; ++k) {
             if (!fi[k]) continue;
             const size_t l = m.kind[k] == 2 ? lds_f32_two_pass<32, 20, 9, 5>() : lds_f32_two_pass<64, 9, 7, 4>();
             lds2 = l > lds2 ? l : lds2;
         }
-        if (g_passes == 4) RLX_LAUNCH((conv_dw_multi_kernel<4>), grid, kThreads, lds2, rlx::as_stream(stream), m);
+        if (adam) {
+            rlx_adam::EarlyDev e;
+            const int rc = rlx_adam::early_dev(adam, &e, "rlx_conv_dw_multi_adam");
+            if (rc != RLX_OK) return rc;
+            if (riders > e.n_early) riders = riders_first ? (e.n_early + 7) / 8 * 8 : e.n_early;
+            const size_t red = sizeof(float) * rlx_adam::kBlock;
+            RLX_LAUNCH((conv_dw_multi_adam_kernel), grid + riders, kThreads, lds2 > red ? lds2 : red, rlx::as_stream(stream), m, e,
+                       riders, riders_first);
+        } else if (passes == 4) RLX_LAUNCH((conv_dw_multi_kernel<4>), grid, kThreads, lds2, rlx::as_stream(stream), m);
         else RLX_LAUNCH((conv_dw_multi_kernel<2>), grid, kThreads, lds2, rlx::as_stream(stream), m);
     } else {
         RLX_LAUNCH((conv_dw_multi_kernel<1>), grid, kThreads, lds, rlx::as_stream(stream), m);
     }
     RLX_LAUNCH_CHECK();
     return RLX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rlx_conv_dw_multi(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n_items, void *stream) {
+    return conv_dw_multi_impl(items, jobs, n_items, stream, nullptr, 0, 0);
+}
+
+int rlx_conv_dw_multi_adam(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int n_items, const rlx_adam_split_desc *adam,
+                           int riders, int riders_first, void *stream) {
+    RLX_REQUIRE(adam, "rlx_conv_dw_multi_adam: null Adam descriptor");
+    RLX_REQUIRE(riders >= 1 && riders <= 1024 && (!riders_first || riders % 8 == 0),
+                "rlx_conv_dw_multi_adam: 1 .. 1024 riders, a multiple of 8 when they are dispatched first");
+    return conv_dw_multi_impl(items, jobs, n_items, stream, adam, riders, riders_first ? 1 : 0);
 }
 
 int rlx_conv_dw_pairs_per_workgroup(int pairs) {

@@ -21,10 +21,11 @@
 // float4 accesses, grid-stride, <= 2048 workgroups.  Compiled with -ffp-contract=off so that the
 // mixing rounds like numpy's two products + add.
 #include "rlx_common.hpp"
+#include "adam_block_body.hpp"
 
 namespace {
 
-constexpr int kBlock = 256;
+using rlx_adam::kBlock;
 
 // The fence-free publication below (partial sums stored at agent scope, completed by s_waitcnt / by the return of an
 // exchange before the ticket is drawn) leans on how gfx942 / gfx950 perform agent-scope stores and atomics at the memory
@@ -214,89 +215,33 @@ adam_step_kernel(float *__restrict__ w, const float *__restrict__ g, float *__re
 // BEFORE the first store, and it is published by an agent-scope atomic exchange issued in front of the stores; at the
 // end of the block the exchange has long returned (the ticket draw is made to depend on its return value), and the
 // block that draws the last ticket does adam_finish_norm_kernel's arithmetic in its order: 210.2 us per update.
-constexpr int kNormIt = 4;
-template <bool MIX>
-__global__ void __launch_bounds__(kBlock)
-adam_step_norm_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
-                      long long n, float lr, float beta1, float beta2, float eps, float *state, float grad_scale,
-                      float *sumsq_part, float *__restrict__ target, float rate, float one_minus_rate,
-                      unsigned int *ticket, float *norm_out, const float *acc_src, float *acc_dst, int n_acc) {
-    __shared__ float red[kBlock];
-    __shared__ int last_s;
-    const float b1p = state[0], b2p = state[1];
-    const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
-    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long n4 = n >> 2;
-    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    float4 gw[kNormIt], mw[kNormIt], vw[kNormIt], ww[kNormIt], tw[kNormIt];
-#pragma unroll
-    for (int it = 0; it < kNormIt; ++it) {
-        const long long i = i0 + it * stride;
-        if (i < n4) {
-            gw[it] = reinterpret_cast<const float4 *>(g)[i];
-            mw[it] = reinterpret_cast<float4 *>(m)[i];
-            vw[it] = reinterpret_cast<float4 *>(v)[i];
-            ww[it] = reinterpret_cast<float4 *>(w)[i];
-            if (MIX) tw[it] = reinterpret_cast<float4 *>(target)[i];
-        }
-    }
-    const long long it0 = (n4 << 2) + i0;            // the (at most 3) elements behind the last float4: one thread each
-    const bool has_tail = it0 < n;
-    const float gt = has_tail ? g[it0] : 0.f;
-    float ss = 0.f;                                   // the additions of adam_step_kernel<true>, in its order
-#pragma unroll
-    for (int it = 0; it < kNormIt; ++it)
-        if (i0 + it * stride < n4) {
-            const float *gp = &gw[it].x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) ss += gp[k] * gp[k];
-        }
-    if (has_tail) ss += gt * gt;
-    red[threadIdx.x] = ss;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
-    float old = 0.f;
-    if (threadIdx.x == 0)
-        old = __hip_atomic_exchange(&sumsq_part[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int it = 0; it < kNormIt; ++it) {
-        const long long i = i0 + it * stride;
-        if (i < n4) {
-            float *gp = &gw[it].x, *mp = &mw[it].x, *vp = &vw[it].x, *wp = &ww[it].x, *tp = &tw[it].x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float gr = gp[k] * grad_scale;
-                mp[k] += (gr - mp[k]) * omb1;
-                vp[k] += (gr * gr - vp[k]) * omb2;
-                wp[k] -= (mp[k] * alpha) / (sqrtf(vp[k]) + eps);
-                if (MIX) tp[k] = rate * wp[k] + one_minus_rate * tp[k];
-            }
-            reinterpret_cast<float4 *>(m)[i] = mw[it];
-            reinterpret_cast<float4 *>(v)[i] = vw[it];
-            reinterpret_cast<float4 *>(w)[i] = ww[it];
-            if (MIX) reinterpret_cast<float4 *>(target)[i] = tw[it];
-        }
-    }
-    if (has_tail) {
-        const float gr = gt * grad_scale;
-        m[it0] += (gr - m[it0]) * omb1;
-        v[it0] += (gr * gr - v[it0]) * omb2;
-        w[it0] -= (m[it0] * alpha) / (sqrtf(v[it0]) + eps);
-        if (MIX) target[it0] = rate * w[it0] + one_minus_rate * target[it0];
-    }
+using rlx_adam::kNormIt;
+
+// The end of a register-held Adam block: thread 0 draws the ticket (not before the exchange that published the block's
+// partial sum has returned `old`), and the workgroup that drew the last one sums ALL `nparts` partials in index order.
+__device__ __forceinline__ void adam_norm_finish(const float old, unsigned int *ticket, float *sumsq_part, const int nparts,
+                                                 float *state, const float b1p, const float b2p, const float beta1,
+                                                 const float beta2, float *norm_out, const float *acc_src, float *acc_dst,
+                                                 const int n_acc, float *red, int *last_s) {
     if (threadIdx.x == 0) {
         asm volatile("" ::"v"(old) : "memory");        // the draw is not issued before the exchange has returned
-        last_s = draw_last_ticket(ticket);
+        *last_s = draw_last_ticket(ticket);
     }
     __syncthreads();
-    if (!last_s) return;
+    if (!*last_s) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // pairs the publication of the partial sums (one workgroup only)
-    float s = 0.f;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kBlock)
+    // (a grid has at most 1024 blocks: a thread's <= 4 partials are requested together and added in index order — this
+    // workgroup is the launch's tail, and a loop would make four dependent round trips to the memory side of it)
+    float s = 0.f, part[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + k * kBlock;
+        part[k] = i < nparts ? __hip_atomic_load(&sumsq_part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if ((int)threadIdx.x + k * kBlock < nparts) s += part[k];
+    for (int i = threadIdx.x + 4 * kBlock; i < nparts; i += kBlock)
         s += __hip_atomic_load(&sumsq_part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     red[threadIdx.x] = s;
     __syncthreads();
@@ -310,6 +255,44 @@ adam_step_norm_kernel(float *__restrict__ w, const float *__restrict__ g, float 
         state[1] = b2p * beta2;
         for (int i = 0; i < n_acc; ++i) acc_dst[i] += acc_src[i];
     }
+}
+
+template <bool MIX>
+__global__ void __launch_bounds__(kBlock)
+adam_step_norm_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                      long long n, float lr, float beta1, float beta2, float eps, float *state, float grad_scale,
+                      float *sumsq_part, float *__restrict__ target, float rate, float one_minus_rate,
+                      unsigned int *ticket, float *norm_out, const float *acc_src, float *acc_dst, int n_acc) {
+    __shared__ float red[kBlock];
+    __shared__ int last_s;
+    const float b1p = state[0], b2p = state[1];
+    const rlx_adam::Coef c = rlx_adam::coef(b1p, b2p, lr, beta1, beta2, eps, grad_scale, rate, one_minus_rate);
+    const float old = rlx_adam::block_step<MIX, true>(w, g, m, v, n, c, sumsq_part, target, (int)blockIdx.x, (int)gridDim.x, red);
+    adam_norm_finish(old, ticket, sumsq_part, (int)gridDim.x, state, b1p, b2p, beta1, beta2, norm_out, acc_src, acc_dst, n_acc,
+                     red, &last_s);
+}
+
+// The same step split over two launches (rlx_adam_tf1_step_early / _late; rlx_adam_split_blocks says which virtual block goes
+// where).  EARLY: workgroup r takes the early blocks r, r + gridDim.x, ...; it draws no ticket, its partial sums are in
+// memory when the launch ends.  LATE: one workgroup per late block; the ticket counts the late blocks, and the workgroup
+// that draws the last one sums the partials of ALL `blocks` virtual blocks, the early launch's among them.
+__global__ void __launch_bounds__(kBlock) adam_early_kernel(const rlx_adam::EarlyDev e) {
+    __shared__ float red[kBlock];
+    rlx_adam::early_blocks(e, (int)blockIdx.x, (int)gridDim.x, red);
+}
+
+__global__ void __launch_bounds__(kBlock)
+adam_late_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                 long long n, float lr, float beta1, float beta2, float eps, float *state, float grad_scale,
+                 float *sumsq_part, const int *__restrict__ late, int blocks, unsigned int *ticket, float *norm_out,
+                 const float *acc_src, float *acc_dst, int n_acc) {
+    __shared__ float red[kBlock];
+    __shared__ int last_s;
+    const float b1p = state[0], b2p = state[1];
+    const rlx_adam::Coef c = rlx_adam::coef(b1p, b2p, lr, beta1, beta2, eps, grad_scale, 0.f, 0.f);
+    const float old = rlx_adam::block_step<false, true>(w, g, m, v, n, c, sumsq_part, nullptr, late[blockIdx.x], blocks, red);
+    adam_norm_finish(old, ticket, sumsq_part, blocks, state, b1p, b2p, beta1, beta2, norm_out, acc_src, acc_dst, n_acc, red,
+                     &last_s);
 }
 
 __global__ void adam_advance_kernel(float *state, float beta1, float beta2) {
@@ -520,6 +503,72 @@ int rlx_adam_tf1_step(float *weights, const float *grads, float *m, float *v, lo
     } else if (n_acc > 0) {
         RLX_REQUIRE(false, "rlx_adam_tf1_step: signal sums ride with the norm finish (give norm_out)");
     }
+    return RLX_OK;
+}
+
+int rlx_adam_step_blocks(long long n, long long workspace_floats, int *blocks_host) {
+    RLX_REQUIRE(n > 0 && blocks_host, "rlx_adam_step_blocks: bad arguments");
+    int blocks = rlx::grid_for(n / 4 + 1, kBlock, 1024);
+    if (blocks > workspace_floats) blocks = (int)workspace_floats;
+    // 0: rlx_adam_tf1_step would not take its register-held one-launch form
+    *blocks_host = (blocks >= 1 && g_norm_in_kernel == 2 && (n >> 2) <= (long long)blocks * kBlock * kNormIt) ? blocks : 0;
+    return RLX_OK;
+}
+
+int rlx_adam_split_blocks(long long n, int blocks, const long long *ranges_host, int n_ranges, int *early_host,
+                          int *n_early_host, int *late_host, int *n_late_host) {
+    RLX_REQUIRE(n > 0 && blocks >= 1 && n_ranges >= 0 && (ranges_host || !n_ranges) && early_host && n_early_host &&
+                    late_host && n_late_host, "rlx_adam_split_blocks: bad arguments");
+    const long long n4 = n >> 2, stride = (long long)blocks * kBlock;
+    RLX_REQUIRE(n4 <= stride * kNormIt, "rlx_adam_split_blocks: %lld parameters do not fit %d register-held blocks", n, blocks);
+    int ne = 0, nl = 0;
+    for (int vb = 0; vb < blocks; ++vb) {
+        // run `it` of the block: the float4s [vb * 256 + it * stride, + 256) that exist, as floats [lo, hi)
+        bool early = !(vb == 0 && (n & 3));        // the <= 3 elements behind the last float4 belong to block 0's first threads
+        bool any = false;
+        for (int it = 0; it < kNormIt && early; ++it) {
+            const long long a = (long long)vb * kBlock + it * stride;
+            if (a >= n4) break;
+            const long long lo = 4 * a, hi = 4 * (a + kBlock < n4 ? a + kBlock : n4);
+            bool inside = false;
+            for (int r = 0; r < n_ranges && !inside; ++r) inside = ranges_host[2 * r] <= lo && hi <= ranges_host[2 * r + 1];
+            early = inside;
+            any = true;
+        }
+        // (a block without elements has only its zero partial sum to write: late, where the ticket is)
+        if (early && any) early_host[ne++] = vb;
+        else late_host[nl++] = vb;
+    }
+    if (nl == 0) late_host[nl++] = early_host[--ne];     // the finish needs a late workgroup
+    *n_early_host = ne;
+    *n_late_host = nl;
+    return RLX_OK;
+}
+
+int rlx_adam_tf1_step_early(const rlx_adam_split_desc *d, int workgroups, void *stream) {
+    rlx_adam::EarlyDev e;
+    const int rc = rlx_adam::early_dev(d, &e, "rlx_adam_tf1_step_early");
+    if (rc != RLX_OK) return rc;
+    RLX_REQUIRE(workgroups >= 1 && workgroups <= 1024, "rlx_adam_tf1_step_early: 1 .. 1024 workgroups");
+    if (e.n_early == 0) return RLX_OK;
+    if (workgroups > e.n_early) workgroups = e.n_early;
+    RLX_LAUNCH((adam_early_kernel), workgroups, kBlock, 0, rlx::as_stream(stream), e);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_adam_tf1_step_late(const rlx_adam_split_desc *d, float *norm_out, const float *acc_src, float *acc_dst, int n_acc,
+                           unsigned int *ticket, void *stream) {
+    rlx_adam::EarlyDev e;
+    const int rc = rlx_adam::early_dev(d, &e, "rlx_adam_tf1_step_late");
+    if (rc != RLX_OK) return rc;
+    RLX_REQUIRE(norm_out && ticket, "rlx_adam_tf1_step_late: null pointer");
+    RLX_REQUIRE(n_acc == 0 || (acc_src && acc_dst && n_acc > 0 && n_acc <= 64),
+                "rlx_adam_tf1_step_late: bad signal accumulation arguments");
+    RLX_LAUNCH((adam_late_kernel), d->n_late, kBlock, 0, rlx::as_stream(stream), d->weights, d->grads, d->m, d->v, d->n,
+               d->learning_rate, d->beta1, d->beta2, d->epsilon, d->state, d->grad_scale, d->partials, d->late, d->blocks, ticket,
+               norm_out, acc_src, acc_dst, n_acc);
+    RLX_LAUNCH_CHECK();
     return RLX_OK;
 }
 

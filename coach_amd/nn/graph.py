@@ -215,6 +215,13 @@ CONV_DW_U8 = True
 CONV_DW_F32 = True
 # ... and all of a backward pass's LDS-resident weight-gradient products as ONE launch (rlx_conv_dw_multi)
 CONV_DW_ONE_LAUNCH = True
+# rlx_conv_dw_multi_adam: workgroups that step an armed early Adam range inside that launch (the library takes at most one per
+# early block: 1024 = a rider per block), and whether they are dispatched in front of the convolution workgroups or behind them.
+# Same-box A/B of the C2 benchmark (profiles/adam_under_conv_dw_ab.txt): behind beats in front at every count, and behind,
+# more riders are better — 864 (a rider per block) 51.3, 512 51.5, 256 51.8, 128 53.8 ms per step against 53.0 without;
+# in front 256 51.9, 512 55.1 (the riders then hold the slots the long conv1 workgroups should start in).
+ADAM_RIDERS = 1024
+ADAM_RIDERS_FIRST = False
 
 
 class Workspace:
@@ -310,6 +317,7 @@ class Context:
 
     ppo_tail = None
     per_tail = None            # set by the agent in front of an update: PrioritizedExperienceReplay.priority_update_args()
+    early_adam = None          # an EarlyAdam armed by the agent for the backward pass that follows (AdamState.arm_early)
 
     def flush_ppo_tail(self):
         """the pending all-rows part of ppo_fc_rows as a launch of its own (no deferred-reduction launch took it along)."""
@@ -391,6 +399,11 @@ class Dense(Layer):
         self.init, self.params = init, params
         self.kname, self.bname = name + "/kernel", name + "/bias"
         params.add_group([(self.kname, (in_features, units)), (self.bname, (units,))], towers)
+
+    def group_range(self):
+        """[lo, hi) of the flat buffers: kernel and bias of ALL towers (the layer's FlatParams group, contiguous)."""
+        lo, _, towers, per = self.params.entries[self.kname]
+        return lo, lo + per * towers
 
     def initialize(self, rng):
         for t in range(self.T):
@@ -542,6 +555,10 @@ class Dense(Layer):
             x.grad_is_dz = lower is not None
         if need_dw:
             ctx.commit_deferred(job)
+            ea = ctx.early_adam
+            if ea is not None and job is not None and job.splits <= 1 and (t0, T) == (0, self.T) and p is ea.adam.params:
+                # the product reported nothing outstanding: dW and the bias column sums of every tower are final now
+                ea.final.append(self.group_range())
 
 
 class NoisyDense(Layer):
@@ -1307,7 +1324,13 @@ class Sequential:
                 # longest workgroups first: the uint8 layer, then the fp32 layers by reduction length
                 group = sorted(collect[:3], key=lambda e: (not e[0].x_is_u8, -e[0].H))
                 collect = collect[3:]
-                _rlx.conv_dw_multi([it for it, _ in group], [j for _, j in group], ctx.stream)
+                # an armed early Adam step whose ranges all reported final gradients rides on this launch (once per pass)
+                ea = ctx.early_adam
+                ride = ea is not None and not ea.done and _rlx.GEMM_HOOK is None and ea.covered()
+                _rlx.conv_dw_multi([it for it, _ in group], [j for _, j in group], ctx.stream,
+                                   adam=(ea.desc, ADAM_RIDERS, ADAM_RIDERS_FIRST) if ride else None)
+                if ride:
+                    ea.done = True
                 for _, j in group:
                     ctx.commit_deferred(j, reserved=True)
             while later:
@@ -1321,6 +1344,27 @@ class Sequential:
                 ctx.flush_deferred()
 
 
+class EarlyAdam:
+    """One Adam step whose early blocks run before the backward pass has ended (AdamState.arm_early).  Context.early_adam
+    holds it during that pass: a layer whose weight-gradient product reported nothing outstanding appends its range to
+    `final`; the convolution weight-gradient launch takes the early blocks along once every armed range is there
+    (`done`); the network's finish then runs the late launch — or, not done, the whole step as ever."""
+
+    def __init__(self, adam, ranges, split, grad_scale, lr):
+        blocks, lists, n_early, n_late, partials = split
+        self.adam, self.ranges, self.grad_scale = adam, ranges, float(grad_scale)
+        self.final, self.done = [], False
+        p, d = adam.params, _rlx.AdamSplitDesc()
+        d.weights, d.grads, d.m, d.v, d.n = p.weights.data_ptr(), p.grads.data_ptr(), adam.m.data_ptr(), adam.v.data_ptr(), p.size
+        d.learning_rate, d.beta1, d.beta2, d.epsilon, d.grad_scale = lr, adam.beta1, adam.beta2, adam.eps, float(grad_scale)
+        d.state, d.partials, d.blocks = adam.state.data_ptr(), partials.data_ptr(), blocks
+        d.early, d.late, d.n_early, d.n_late = lists.data_ptr(), lists.data_ptr() + 4 * n_early, n_early, n_late
+        self.desc = d
+
+    def covered(self):
+        return all(r in self.final for r in self.ranges)
+
+
 class AdamState:
     """tf.train.AdamOptimizer slots for one flat parameter buffer (general_network.py:390-394)."""
 
@@ -1332,6 +1376,8 @@ class AdamState:
         self.state = torch.empty(2, dtype=torch.float32, device=dev)
         self.ticket = torch.zeros(_rlx.ADAM_TICKET_WORDS, dtype=torch.int32, device=dev)   # rlx_adam_tf1_step's last-arriver count
         self.one_launch = True
+        self._splits = {}            # prepare_early: (ranges, workspace floats) -> split
+        self.split_steps = 0         # steps issued as early + late launches (step_late calls; a captured call counts once)
         _rlx.lib().adam_init(self.m, self.v, params.size, self.state, beta1, beta2, _rlx.current_stream())
 
     def step(self, grad_scale=1.0, lr=None, norm_out=None, workspace=None, acc=None, grads=None, mix_target=None,
@@ -1352,6 +1398,58 @@ class AdamState:
             return
         if mix_target is not None:
             raise ValueError("the two-launch Adam path does not fuse the target update")
+        self._step_two_launch(p, g, lr, grad_scale, norm_out, workspace, acc)
+
+    # ---- the one-launch step split in two (rlx_adam_tf1_step_early / _late, rlx_conv_dw_multi_adam): the blocks whose
+    # gradients are final early in the backward pass are stepped while the rest of it still runs
+    MAX_BLOCKS = 1024            # the widest grid rlx_adam_tf1_step launches
+
+    def prepare_early(self, ranges, workspace_floats=MAX_BLOCKS):
+        """The split of the step's virtual blocks for the float ranges [(lo, hi), ...] whose gradients are final early:
+        device lists and a partial-sum buffer of their own, built once per ranges — NOT inside a stream capture (it
+        allocates and copies).  None where rlx_adam_tf1_step would not take its register-held form, or nothing is early."""
+        key = (tuple((int(a), int(b)) for a, b in ranges), int(workspace_floats))
+        if key not in self._splits:
+            lib, n = _rlx.lib(), self.params.size
+            blocks = ctypes.c_int()
+            lib.adam_step_blocks(n, int(workspace_floats), ctypes.byref(blocks))
+            split = None
+            if self.one_launch and blocks.value >= 1 and key[0]:
+                nb = blocks.value
+                flat = (ctypes.c_longlong * (2 * len(key[0])))(*[x for r in key[0] for x in r])
+                early, late = (ctypes.c_int * nb)(), (ctypes.c_int * nb)()
+                ne, nl = ctypes.c_int(), ctypes.c_int()
+                lib.adam_split_blocks(n, nb, flat, len(key[0]), early, ctypes.byref(ne), late, ctypes.byref(nl))
+                if ne.value > 0:
+                    dev = self.m.device
+                    lists = torch.tensor(list(early[:ne.value]) + list(late[:nl.value]), dtype=torch.int32).to(dev)
+                    split = (nb, lists, ne.value, nl.value, torch.zeros(nb, dtype=torch.float32, device=dev))
+            self._splits[key] = split
+        return self._splits[key]
+
+    def arm_early(self, ranges, grad_scale=1.0, lr=None, workspace_floats=MAX_BLOCKS, prepare=True):
+        """-> an EarlyAdam for ONE step of this optimiser (rlx_adam_split_desc filled: learning rate and gradient scale are
+        host constants fixed now), or None where the split does not apply.  prepare=False: only a split that
+        prepare_early has already built (inside a stream capture)."""
+        key = (tuple((int(a), int(b)) for a, b in ranges), int(workspace_floats))
+        split = self.prepare_early(ranges, workspace_floats) if prepare else self._splits.get(key)
+        return EarlyAdam(self, key[0], split, grad_scale, self.lr if lr is None else lr) if split is not None else None
+
+    def step_early(self, ea, workgroups=256):
+        """the early blocks as a launch of their own (rlx_adam_tf1_step_early)"""
+        _rlx.lib().adam_tf1_step_early(ctypes.byref(ea.desc), int(workgroups), _rlx.current_stream())
+        ea.done = True
+
+    def step_late(self, ea, norm_out, acc=None):
+        """the late blocks and the finish (rlx_adam_tf1_step_late): with the early blocks stepped before, what step(norm_out=...)
+        leaves, bit for bit"""
+        if not ea.done:
+            raise ValueError("the early blocks of this step have not run")
+        self.split_steps += 1
+        _rlx.lib().adam_tf1_step_late(ctypes.byref(ea.desc), norm_out, acc[0] if acc else None, acc[1] if acc else None,
+                                      int(acc[2]) if acc else 0, self.ticket, _rlx.current_stream())
+
+    def _step_two_launch(self, p, g, lr, grad_scale, norm_out, workspace, acc):
         if norm_out is not None:
             _rlx.lib().adam_tf1_norm(p.weights, g, self.m, self.v, p.size, lr, self.beta1,
                                      self.beta2, self.eps, self.state, grad_scale, norm_out, workspace,

@@ -369,11 +369,44 @@ class ClippedPPONet(_NetBase):
         if k > 0:
             self.torso.backward(self.ctx, acts, layers=(0, k))
 
+    # ---- the Adam step of the dense torso layers under the convolution weight-gradient launch (G.EarlyAdam) ----
+    def early_adam_ranges(self):
+        """the flat-buffer ranges whose gradients are final before the convolution weight-gradient launch: the dense
+        layers of an image torso (both towers' kernel and bias: one contiguous group each)"""
+        if not self.image:
+            return []
+        return [l.group_range() for l in self.torso.layers if type(l) is G.Dense]
+
+    def prepare_early_adam(self):
+        """the split's device lists (call outside a stream capture) -> True if there is something to run early"""
+        ranges = self.early_adam_ranges()
+        return bool(ranges) and self.adam.prepare_early(ranges) is not None
+
+    def arm_early_adam(self, grad_scale=1.0, prepare=True):
+        """The forward_backward that follows may step the early ranges inside its convolution weight-gradient launch — it
+        does if every range's product reports nothing outstanding; finish_update(grad_scale) then runs the rest.  The
+        caller's decision (an agent that knows that nothing reduces or rescales the gradients in between); a
+        forward_backward that nobody armed leaves every weight alone, as ever."""
+        ranges = self.early_adam_ranges()
+        self.ctx.early_adam = self.adam.arm_early(ranges, grad_scale, prepare=prepare) if ranges else None
+        return self.ctx.early_adam is not None
+
+    def disarm_early_adam(self):
+        self.ctx.early_adam = None
+
     def finish_update(self, grad_scale=1.0, signal_acc=None):
         """apply_gradients (architecture.py:469-521): global norm fetch + Adam (+ the running sums of
-        [surrogate, entropy, kl, policy total, value loss, grad norm] into signal_acc)."""
-        self.apply_gradients(grad_scale, with_norm=True,
-                             acc=(self.scalars, signal_acc, 6) if signal_acc is not None else None)
+        [surrogate, entropy, kl, policy total, value loss, grad norm] into signal_acc).  Behind an armed backward pass
+        that ran the early blocks: the late launch (same result, bit for bit)."""
+        acc = (self.scalars, signal_acc, 6) if signal_acc is not None else None
+        ea, self.ctx.early_adam = self.ctx.early_adam, None
+        if ea is not None and ea.done:
+            if float(grad_scale) != ea.grad_scale:
+                raise ValueError("finish_update(%r): the early part of this step ran with gradient scale %r"
+                                 % (grad_scale, ea.grad_scale))
+            self.adam.step_late(ea, self.norm, acc)
+            return
+        self.apply_gradients(grad_scale, with_norm=True, acc=acc)
 
     def train_minibatch(self, obs, B, actions, advantages, value_targets, old_probs,
                         clip_rescaler=1.0, grad_scale=1.0, ratio_out=None, clipped_out=None):

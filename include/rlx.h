@@ -803,6 +803,36 @@ int rlx_adam_tf1_step(float *weights, const float *grads, float *m, float *v, lo
  * registers (falls back to 0 beyond 4.2 M parameters); 1: inside the grid-stride Adam launch (any size; measured equal to
  * 0); 0: the separate finish launch.  Process-wide, read at launch / capture time: for same-process A/Bs and tests. */
 int rlx_adam_norm_in_kernel(int on);
+/* The register-held one-launch step SPLIT over two launches.  Its grid is a list of VIRTUAL blocks (rlx_adam_step_blocks:
+ * the grid rlx_adam_tf1_step would launch for n parameters and this workspace, 0 where it would not take that form); a
+ * block's elements, its additions and its partial sum of squares do not depend on which launch runs it.  A block whose
+ * gradients are final early — rlx_adam_split_blocks: every existing float4 of its four runs lies inside one of the float
+ * ranges [lo, hi) of ranges_host (n_ranges pairs), and it owns none of the <= 3 elements behind the last float4 — can be
+ * stepped by rlx_adam_tf1_step_early (`workgroups` workgroups, each looping over early blocks; no ticket; no target mix)
+ * or by riders of the convolution weight-gradient launch (rlx_conv_dw_multi_adam) while the rest of the backward pass still
+ * runs.  rlx_adam_tf1_step_late then runs the late blocks (never none: the split keeps one), and the workgroup that finishes
+ * last sums the partials of ALL blocks in index order, writes the norm, advances the beta powers and adds the signal sums.
+ * Weights, slots, state, norm and signal sums are bit-identical to rlx_adam_tf1_step's.  `partials` ([blocks] floats) must
+ * stay untouched between the early and the late launch; early / late are device arrays (n_early + n_late == blocks), the
+ * *_host outputs of rlx_adam_split_blocks have room for `blocks` entries each. */
+typedef struct rlx_adam_split_desc {
+    float *weights;
+    const float *grads;
+    float *m, *v;
+    long long n;
+    float learning_rate, beta1, beta2, epsilon, grad_scale;
+    float *state;
+    float *partials;
+    int blocks;
+    const int *early, *late;
+    int n_early, n_late;
+} rlx_adam_split_desc;
+int rlx_adam_step_blocks(long long n, long long workspace_floats, int *blocks_host);
+int rlx_adam_split_blocks(long long n, int blocks, const long long *ranges_host, int n_ranges, int *early_host,
+                          int *n_early_host, int *late_host, int *n_late_host);
+int rlx_adam_tf1_step_early(const rlx_adam_split_desc *desc_host, int workgroups, void *stream);
+int rlx_adam_tf1_step_late(const rlx_adam_split_desc *desc_host, float *norm_out, const float *acc_src, float *acc_dst,
+                           int n_acc, unsigned int *ticket, void *stream);
 int rlx_mix_weights(float *target, const float *online, long long n, double rate,
                     void *stream);   /* architectures/tensorflow_components/architecture.py:598-607 */
 int rlx_global_norm(const float *x, long long n, float *norm_out, float *workspace,
@@ -1250,6 +1280,14 @@ typedef struct rlx_conv_dw_item {
     float *workspace; long long workspace_floats;
 } rlx_conv_dw_item;
 int rlx_conv_dw_multi(const rlx_conv_dw_item *items_host, rlx_splitk_job *jobs_host, int n_items, void *stream);
+/* rlx_conv_dw_multi + rlx_adam_tf1_step_early(adam, riders) as ONE launch: the grid of the one-launch form, taken with the
+ * four-pass bodies whatever rlx_conv_dw_passes says (<= 50 KB of LDS: three workgroups per CU, of which the convolution
+ * workgroups only ever fill two), plus `riders` workgroups that step the early blocks in the slot left over — dispatched
+ * in front of the convolution workgroups (riders_first) or behind them.  Gradients and jobs as rlx_conv_dw_multi's, the
+ * Adam step as rlx_adam_tf1_step_early's.  Items that do not take the one-launch form go out item by item and the early
+ * step as a launch of its own behind them.  Every call applies the early step: never replay one. */
+int rlx_conv_dw_multi_adam(const rlx_conv_dw_item *items_host, rlx_splitk_job *jobs_host, int n_items,
+                           const rlx_adam_split_desc *adam_host, int riders, int riders_first, void *stream);
 /* Process-wide (default 2): 2 = the one-launch form stages conv1's and conv2's operands in TWO passes over the output rows
  * (79 KB of LDS per workgroup instead of 157 KB: two workgroups per CU, one's fills under the other's products).  Weight
  * gradients identical; the inner layer's bias gradient sums its positions in another grouping (last bits).  -6 us per Clipped-PPO
