@@ -125,7 +125,7 @@ class ClippedPPOAgent(object):
         # (_decide_overlap); True / False = forced (tests, A/B)
         self.overlap_allreduce = None if self.dist is not None else False
         self.overlap_decision = None
-        alg, net = self.ap.algorithm, self.ap.network_wrappers["main"]
+        alg = self.ap.algorithm
         ep = environment.p
         self.continuous = ep.action_dim is not None      # BoxActionSpace -> continuous PPO head
         self.n_env, self.A = ep.num_envs, (ep.action_dim if self.continuous else ep.num_actions)
@@ -138,13 +138,7 @@ class ClippedPPOAgent(object):
         if self.ap.seed is not None:
             random.seed(self.ap.seed)
             np.random.seed(self.ap.seed)
-        self.networks = {"main": ClippedPPONet(
-            self.device, obs_shape, self.A, activation=net.activation_function,
-            embedder=net.embedder_scheme, middleware=net.middleware_scheme,
-            learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
-            adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon,
-            clip_likelihood_ratio_using_epsilon=alg.clip_likelihood_ratio_using_epsilon,
-            beta_entropy=alg.beta_entropy, seed=self.ap.seed or 0, continuous=self.continuous)}
+        self.networks = self._build_networks(obs_shape)
         if self.dist is not None and self.ap.seed is not None:
             # rank-offset sampling seed (coach.py:746 seed + task_index) AFTER the shared weight init
             random.seed(self.ap.seed + self.dist.rank)
@@ -205,6 +199,16 @@ class ClippedPPOAgent(object):
         self._eval_mem = None
         self._alloc_training_buffers()
         self.memory.reset(self.env.reset_internal_state())
+
+    def _build_networks(self, obs_shape):
+        alg, net = self.ap.algorithm, self.ap.network_wrappers["main"]
+        return {"main": ClippedPPONet(
+            self.device, obs_shape, self.A, activation=net.activation_function,
+            embedder=net.embedder_scheme, middleware=net.middleware_scheme,
+            learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
+            adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon,
+            clip_likelihood_ratio_using_epsilon=alg.clip_likelihood_ratio_using_epsilon,
+            beta_entropy=alg.beta_entropy, seed=self.ap.seed or 0, continuous=self.continuous)}
 
     # ------------------------------------------------------------------------------- buffers
     def _alloc_training_buffers(self):

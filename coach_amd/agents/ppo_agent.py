@@ -1,0 +1,272 @@
+"""PPO with the KL penalty (the PPO paper's PPO-penalty; rl_coach/agents/ppo_agent.py) on the device engine.
+
+Separate actor and critic networks, each with a target copy; an unclipped surrogate whose loss carries
+kl_coefficient * KL + high_kl_penalty_coefficient * max(0, KL - 2 * target_kl)^2; the coefficient adapted by x1.5 / /1.5
+after every training phase.  Acting, the episodic rollout buffer, the observation-normalisation filter, evaluation and
+the "train once num_consecutive_playing_steps transitions lie in complete episodes" rule are ClippedPPOAgent's, which
+this class extends; what differs is the training phase (train(), :362-391):
+
+  sync both networks -> fill_advantages over the whole dataset (critic online V(s), per-episode GAE with a zero
+  bootstrap, standardisation over all rows; the old policy from the TARGET actor) -> the first
+  num_consecutive_playing_steps rows are the training set -> ONE value epoch (targets: discounted returns to the
+  episode's end, rounded to fp32 once) -> TEN policy epochs, minibatches in dataset order, no shuffle, the tail dropped
+  (rlx_ppo_kl_discrete_loss / rlx_ppo_kl_continuous_loss, csrc/ppo_kl.hip) -> rlx_ppo_kl_coefficient_update from the LAST
+  epoch's running sums -> memory.clean().
+
+Nothing is read back inside the phase; an epoch is one captured graph where use_graphs is on.  The target critic's
+prediction, which the reference computes and never feeds (:219-231: VHead has no such input), is not computed.
+tests/ppo_kl_ref.py restates the phase; tests/golden/ppo_kl.npz pins it to the reference's own PPOAgent."""
+import numpy as np
+import torch
+
+from .. import _rlx
+from ..architectures.scheme_views import SchemeViews
+from ..core_types import EnvironmentSteps
+from ..nn.networks import PPOActorNet, PPOCriticNet
+from ..schedules import ConstantSchedule
+from .clipped_ppo_agent import ClippedPPOAgent
+from .policy_optimization_agent import PolicyGradientRescaler
+
+POLICY_EPOCHS, VALUE_EPOCHS = 10, 1                      # train(): train_value_network(dataset, 1), train_policy_network(dataset, 10)
+
+
+class _PPONetworkParameters(SchemeViews):
+    def __init__(self):
+        self.activation_function = 'tanh'                # embedder and middleware (:43-44, :55-56)
+        self.embedder_scheme = 'Medium'
+        self.middleware_scheme = 'Medium'
+        self.optimizer_type = 'Adam'
+        self.learning_rate = 0.00025                     # base_parameters.py NetworkParameters defaults
+        self.adam_optimizer_beta1 = 0.9
+        self.adam_optimizer_beta2 = 0.99
+        self.optimizer_epsilon = 0.0001
+        self.clip_gradients = None
+        self.async_training = True
+        self.l2_regularization = 0
+        self.create_target_network = True
+        self.batch_size = 128
+        self.learning_rate_decay_rate = 0
+
+
+class PPOCriticNetworkParameters(_PPONetworkParameters):  # ppo_agent.py:40-49
+    heads = (("VHeadParameters", 1.0),)
+
+
+class PPOActorNetworkParameters(_PPONetworkParameters):   # ppo_agent.py:52-62
+    heads = (("PPOHeadParameters", 1.0),)
+
+
+class PPOAlgorithmParameters(object):                    # ppo_agent.py:65-124
+    def __init__(self):
+        self.discount = 0.99
+        self.policy_gradient_rescaler = PolicyGradientRescaler.GAE
+        self.gae_lambda = 0.96
+        self.target_kl_divergence = 0.01
+        self.initial_kl_coefficient = 1.0
+        self.high_kl_penalty_coefficient = 1000
+        self.clip_likelihood_ratio_using_epsilon = None
+        self.value_targets_mix_fraction = 0.1
+        self.estimate_state_value_using_gae = True
+        self.use_kl_regularization = True
+        self.beta_entropy = 0.01
+        self.num_consecutive_playing_steps = EnvironmentSteps(5000)
+        self.num_consecutive_training_steps = 1
+        self.act_for_full_episodes = True
+        self.distributed_coach_synchronization_type = None
+        # the engine's flat fields (filters of the preset, folded by compat.resolve_reference_style)
+        self.clipping_decay_schedule = ConstantSchedule(1)   # stepped by the shared acting path; this agent never clips
+        self.reward_clipping = None
+        self.reward_rescale = 1.0
+        self.normalize_observations = False
+
+
+class PPOAgentParameters(object):                        # ppo_agent.py:127-137
+    def __init__(self):
+        self.algorithm = PPOAlgorithmParameters()
+        self.network_wrappers = {"critic": PPOCriticNetworkParameters(), "actor": PPOActorNetworkParameters()}
+        self.seed = 0
+
+    @property
+    def path(self):
+        return 'coach_amd.agents.ppo_agent:PPOAgent'
+
+
+def check_served(agent_parameters, environment_parameters, dist=None):
+    """What this agent does not serve, raised from the parameters alone (before anything touches the device)."""
+    alg = agent_parameters.algorithm
+    if getattr(environment_parameters, "kind", "vector") == "image":
+        raise ValueError("PPOAgent serves vector observations only (image observations: ClippedPPOAgent)")
+    if dist is not None and getattr(dist, "enabled", False):
+        raise ValueError("PPOAgent does not serve data-parallel training")
+    if alg.clip_likelihood_ratio_using_epsilon is not None:
+        raise ValueError("clip_likelihood_ratio_using_epsilon is not None: that is ClippedPPOAgent; PPOAgent is the "
+                         "KL-penalised variant")
+    if alg.policy_gradient_rescaler == PolicyGradientRescaler.A_VALUE:
+        raise ValueError("PPOAgent serves the GAE policy gradient rescaler only (A_VALUE is not built)")
+    if alg.policy_gradient_rescaler != PolicyGradientRescaler.GAE:
+        raise ValueError("The requested policy gradient rescaler is not available")          # ppo_agent.py:186
+    if agent_parameters.network_wrappers["critic"].optimizer_type == 'LBFGS':
+        raise ValueError("the LBFGS critic (and value_targets_mix_fraction) is not built: use optimizer_type 'Adam'")
+
+
+class _ActingView(object):
+    """What the shared acting / evaluation / fill_advantages code asks of networks['main']: the policy from the actor,
+    V(s) from the critic."""
+
+    def __init__(self, actor, critic, lib):
+        self.actor, self.critic, self.lib = actor, critic, lib
+
+    def policy_probs(self, obs, B, use_target=False, tag="act", out=None, sample=None):
+        probs = self.actor.policy_probs(obs, B, use_target=use_target, tag=tag, out=out)
+        if sample is not None:                                       # categorical.py:45-48
+            uniforms, actions = sample
+            self.lib.categorical_sample(probs, self.actor.A, uniforms, B, self.actor.A, actions, _rlx.current_stream())
+            return None
+        return probs
+
+    def policy_mean_std(self, *args, **kw):
+        return self.actor.policy_mean_std(*args, **kw)
+
+    def values(self, obs, B, tag="val", out=None):
+        v = self.critic.values(obs, B, tag=tag)
+        if out is not None:
+            out.copy_(v)
+            return out
+        return v
+
+    def check_status(self):
+        pass
+
+
+class PPOAgent(ClippedPPOAgent):
+    RECORD_WHILE_ACTING = False
+
+    def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
+        check_served(agent_parameters, environment.p, dist)
+        super().__init__(agent_parameters, environment, device, None, use_graphs)
+        self.kl_coefficient_history = [float(agent_parameters.algorithm.initial_kl_coefficient)]
+
+    def _build_networks(self, obs_shape):
+        alg, seed = self.ap.algorithm, self.ap.seed or 0
+
+        def common(net):
+            return dict(activation=net.activation_function, embedder=net.embedder_scheme, middleware=net.middleware_scheme,
+                        learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
+                        adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon, seed=seed)
+        critic = PPOCriticNet(self.device, obs_shape, **common(self.ap.network_wrappers["critic"]))
+        actor = PPOActorNet(self.device, obs_shape, self.A, beta_entropy=alg.beta_entropy,
+                            target_kl_divergence=alg.target_kl_divergence,
+                            initial_kl_coefficient=alg.initial_kl_coefficient,
+                            high_kl_penalty_coefficient=alg.high_kl_penalty_coefficient,
+                            use_kl_regularization=alg.use_kl_regularization, continuous=self.continuous,
+                            **common(self.ap.network_wrappers["actor"]))
+        return {"critic": critic, "actor": actor, "main": _ActingView(actor, critic, self.lib)}
+
+    def _alloc_training_buffers(self):
+        from ..staging import Stager
+        dev, cap = self.device, self.memory.cap
+        f32, f64 = torch.float32, torch.float64
+        self.ds_reward = torch.empty(cap, dtype=f32, device=dev)
+        self.ds_done = torch.empty(cap, dtype=torch.uint8, device=dev)
+        self.ds_action = torch.empty((cap, self.A) if self.continuous else (cap,), dtype=self.actions.dtype, device=dev)
+        self.ds_value = torch.empty(cap, dtype=f32, device=dev)
+        self.ds_adv64 = torch.empty(cap, dtype=f64, device=dev)
+        self.ds_adv = torch.empty(cap, dtype=f32, device=dev)
+        self.ds_gae_target = torch.empty(cap, dtype=f32, device=dev)      # rlx_gae's V target: not this agent's
+        self.ds_ret64 = torch.empty(cap, dtype=f64, device=dev)
+        self.ds_vtarget = torch.empty(cap, dtype=f32, device=dev)
+        self.ds_old_probs = torch.empty(cap, self.A, dtype=f32, device=dev)     # discrete: probs; continuous: mean
+        self.ds_old_std = torch.empty(cap, self.A, dtype=f32, device=dev) if self.continuous else None
+        D = self.memory.obs_dim
+        self.ds_obs_raw = torch.empty(cap, D, dtype=f32, device=dev) if self.norm is not None else None
+        self.ds_obs = torch.empty(cap, D, dtype=f32, device=dev)          # the (normalised) states in dataset order
+        self.adv_stats = torch.empty(2, dtype=f64, device=dev)
+        self.chunk = min(int(self.DATASET_CHUNK), cap)
+        self.chunk_obs = torch.empty((self.chunk, D), dtype=f32, device=dev)
+        self.value_acc = torch.zeros(2, dtype=f32, device=dev)            # sums of the value losses, their count
+        self.norm_acc = torch.zeros(1, dtype=f32, device=dev)             # sum of the policy epoch's gradient norms
+        shape = (self.steps_per_phase, self.n_env, self.A) if self.continuous else (self.steps_per_phase, self.n_env)
+        if self.ragged:
+            shape = (1,) + shape[1:]
+        self._uniforms = Stager(shape, f64, dev, depth=32 if self.ragged else 4)
+        self.uniforms_all = self._uniforms.dst
+
+    # ------------------------------------------------------------------------------- training
+    def _fill_advantages_device(self, n, rows, n_train=None, recorded=False):
+        """fill_advantages (:156-195) and what the two training loops read: V(s), GAE, standardisation and the target
+        actor's outputs are the shared code's; added here: the value targets (:207) and, without a normalisation filter,
+        the states in dataset order."""
+        self.ds_vtarget, keep = self.ds_gae_target, self.ds_vtarget
+        try:
+            super()._fill_advantages_device(n, rows, n_train, False)
+        finally:
+            self.ds_vtarget = keep
+        n_seq = 1 if self.ragged else self.memory.n_env
+        self.lib.discounted_returns(self.ds_reward, self.ds_done, n_seq, n // n_seq, self.ap.algorithm.discount,
+                                    self.ds_ret64, self.ds_vtarget, _rlx.current_stream())
+        if self.norm is None:
+            self.memory.gather_states(rows[:n_train], n_train, self.ds_obs[:n_train])
+
+    def training_set(self):
+        """(rows of the training set, critic minibatches, actor minibatches): the first num_consecutive_playing_steps
+        rows of the dataset (:377), split in dataset order with the tail dropped (:212, :260)"""
+        n = min(self.memory.num_transitions(), self.ap.algorithm.num_consecutive_playing_steps.num_steps)
+        nets = self.ap.network_wrappers
+        return n, n // nets["critic"].batch_size, n // nets["actor"].batch_size
+
+    def _value_epoch(self, n_batches):
+        critic, B = self.networks["critic"], self.ap.network_wrappers["critic"].batch_size
+        for i in range(n_batches):
+            sl = slice(i * B, (i + 1) * B)
+            critic.train_minibatch(self.ds_obs[sl], B, self.ds_vtarget[sl])
+            self.value_acc[0:1].add_(critic.loss)
+            self.value_acc[1:2].add_(1.0)
+
+    def _policy_epoch(self, n_batches):
+        actor, B = self.networks["actor"], self.ap.network_wrappers["actor"].batch_size
+        actor.reset_epoch_sums()
+        self.norm_acc.zero_()
+        for i in range(n_batches):
+            sl = slice(i * B, (i + 1) * B)
+            old = (self.ds_old_probs[sl], self.ds_old_std[sl]) if self.continuous else self.ds_old_probs[sl]
+            actor.train_minibatch(self.ds_obs[sl], B, self.ds_action[sl], self.ds_adv[sl], old)
+            self.norm_acc.add_(actor.norm)
+
+    def train(self):
+        """PPOAgent.train (:362-391)"""
+        if not self._should_train():
+            return None
+        alg = self.ap.algorithm
+        actor, critic = self.networks["actor"], self.networks["critic"]
+        for _ in range(alg.num_consecutive_training_steps):
+            actor.update_target(1.0)                                      # networks['actor'].sync() (:369-370)
+            critic.update_target(1.0)
+            self.fill_advantages()
+            n, n_value, n_policy = self.training_set()
+            self.batches_of_last_phase = (n, n_value * VALUE_EPOCHS, n_policy * POLICY_EPOCHS)
+            self.value_acc.zero_()
+            for _ in range(VALUE_EPOCHS):
+                self._run(("value", n_value), lambda: self._value_epoch(n_value))
+            for _ in range(POLICY_EPOCHS):
+                self._run(("policy", n_policy), lambda: self._policy_epoch(n_policy))
+        if alg.use_kl_regularization:                                     # post_training_commands (:355-360)
+            actor.update_kl_coefficient()
+        self.memory.clean()
+        self._rec_missing = False
+        self.training_iteration += 1
+        # the phase is over: the last epoch's means (:303-304, :324-326) and the value epoch's mean loss (:241)
+        sums = actor.epoch_sums.cpu().numpy()
+        count = max(float(sums[3]), 1.0)
+        value = self.value_acc.cpu().numpy()
+        self.kl_coefficient_history.append(float(actor.kl_coefficient.item()))
+        self.signals = {"Value Loss": float(value[0]) / max(float(value[1]), 1.0), "Policy Loss": float(sums[2]) / count,
+                        "KL Divergence": float(sums[0]) / count, "Entropy": float(sums[1]) / count,
+                        "Advantages": self.ds_adv[:n], "Grads (unclipped)": float(self.norm_acc.item()) / count}
+        return self.signals
+
+    def check_status(self):
+        bits = int(self.memory.status.item())
+        if bits:
+            self.memory.status.zero_()
+            raise ValueError("rollout buffer kernel reported an out-of-range row (status bits %d)" % bits)
+        self.networks["actor"].check_status()

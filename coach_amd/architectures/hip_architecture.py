@@ -47,7 +47,8 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import (ACERNet, ActorCriticNet, ClippedPPONet, DQNNet, NStepQNet, PolicyGradientNet,
+from ..nn.networks import (ACERNet, ActorCriticNet, ClippedPPONet, DQNNet, NStepQNet, PPOActorNet, PPOCriticNet,
+                           PolicyGradientNet,
                            acer_net_kwargs, actor_critic_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs,
                            policy_gradient_net_kwargs)
 from .architecture import Architecture
@@ -809,7 +810,113 @@ class ACERArchitecture(HipArchitecture):
         return float(sc[0]), losses, float(net.norm.item()), [table[f]() for f in additional_fetches]
 
 
+# ================================================================================ PPO (KL penalty)
+def _ppo_net_common(np_, seed):
+    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
+                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1, adam_beta2=np_.adam_optimizer_beta2,
+                optimizer_epsilon=np_.optimizer_epsilon, seed=seed)
+
+
+class PPOActorArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> PPOHead without a clip range and with the KL penalty, fed the way
+    PPOAgent.train_policy_network feeds it (ppo_agent.py:278-288): inputs 'observation', 'output_0_0' = actions,
+    'output_0_1' (, 'output_0_2') = the old policy's probabilities (mean, std); targets = [advantages].  predict -> the
+    action probabilities, or [mean, std].  The head's kl_coefficient is readable / assignable through
+    get_variable_value / set_variable_value (ppo_agent.py:336-351)."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        alg = agent_parameters.algorithm
+        if alg.clip_likelihood_ratio_using_epsilon is not None:
+            raise ValueError("clip_likelihood_ratio_using_epsilon is not None: that is the Clipped PPO network")
+        continuous = not hasattr(spaces.action, "actions")
+        n_act = int(spaces.action.shape[0]) if continuous else len(spaces.action.actions)
+        return PPOActorNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape), n_act,
+                           beta_entropy=alg.beta_entropy, target_kl_divergence=alg.target_kl_divergence,
+                           initial_kl_coefficient=alg.initial_kl_coefficient,
+                           high_kl_penalty_coefficient=alg.high_kl_penalty_coefficient,
+                           use_kl_regularization=alg.use_kl_regularization, continuous=continuous,
+                           **_ppo_net_common(np_, seed))
+
+    def _handles(self):
+        self.n_dist = 2 if self.net.continuous else 1
+        self.inputs = ['observation'] + ['output_0_%d' % i for i in range(self.n_dist + 1)]
+        self.output_heads = [_HeadFetches(0, ['kl_divergence', 'entropy', 'likelihood_ratio', 'output', 'kl_coefficient',
+                                              'assign_kl_coefficient', 'kl_coefficient_ph'])]
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        net, tag = self.net, "%s_%d" % (tag, B)
+        if net.continuous:
+            return list(net.policy_mean_std(obs, B, use_target=self.is_target, tag=tag))
+        return [net.policy_probs(obs, B, use_target=self.is_target, tag=tag)]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net, n_dist = self.net, self.n_dist
+        obs, B = self._observation(inputs)
+        for k in self.inputs[1:]:
+            if k not in inputs:
+                raise ValueError("the PPO head needs the input {}".format(k))
+        f32 = torch.float32
+        actions = self._to_device(inputs['output_0_0'], f32 if net.continuous else torch.int32).contiguous()
+        old = [self._to_device(inputs['output_0_%d' % (i + 1)], f32).contiguous() for i in range(n_dist)]
+        advantages = self._per_sample(targets, B, "targets ([advantages])")
+        if actions.shape[0] != B or any(tuple(o.shape) != (B, net.A) for o in old):
+            raise ValueError("head inputs do not match the batch size {}".format(B))
+        ratio = torch.empty(B, dtype=f32, device=self.device)
+        net.forward_backward(obs, B, actions, advantages, tuple(old) if net.continuous else old[0], ratio,
+                             accumulate=False)
+        net.grad_norm()
+        sc = net.scalars.cpu().numpy()      # [surrogate, entropy, kl, total, penalty factor]
+        net.check_status()
+        head = self.output_heads[0]
+        table = {head.kl_divergence: lambda: sc[2], head.entropy: lambda: sc[1],
+                 head.likelihood_ratio: lambda: ratio.cpu().numpy()}
+        if any(f not in table for f in additional_fetches):
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        return float(sc[3]), [float(sc[0])], float(net.norm.item()), [table[f]() for f in additional_fetches]
+
+    def get_variable_value(self, variable):
+        if variable == self.output_heads[0].kl_coefficient:
+            return np.float32(self.net.kl_coefficient.item())
+        return super().get_variable_value(variable)
+
+    def set_variable_value(self, assign_op, value, placeholder=None):
+        if assign_op == self.output_heads[0].assign_kl_coefficient:
+            self.net.kl_coefficient.fill_(float(np.float32(value)))
+            return
+        super().set_variable_value(assign_op, value, placeholder)
+
+
+class PPOCriticArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> the plain VHead (MSE), fed the way PPOAgent.train_value_network feeds it
+    (ppo_agent.py:227-233): inputs 'observation', targets = the returns (B, 1).  predict -> V (B, 1)."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        return PPOCriticNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
+                            **_ppo_net_common(np_, seed))
+
+    def _handles(self):
+        self.inputs = ['observation']
+        self.output_heads = [_HeadFetches(0, ['output'])]
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        return [self.net.values(obs, B, use_target=self.is_target, tag="%s_%d" % (tag, B)).view(B, 1)]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        obs, B = self._observation(inputs)
+        if additional_fetches:
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        net.forward_backward(obs, B, self._per_sample(targets, B, "targets (the returns)"))
+        net.grad_norm()
+        loss = float(net.loss.item())
+        return loss, [loss], float(net.norm.item()), []
+
+
 _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
+                       "PPOActorNetworkParameters": PPOActorArchitecture,
+                       "PPOCriticNetworkParameters": PPOCriticArchitecture,
                        "ACERNetworkParameters": ACERArchitecture,
                        "ActorCriticNetworkParameters": ActorCriticArchitecture,
                        "NStepQNetworkParameters": NStepQArchitecture,

@@ -102,6 +102,15 @@ def resolve_reference_style(agent_params, env_params):
         # the level's default input filter: the Atari chain clips, GymVectorEnvironment has none
         # (gym_environment.py:76-81,106-113)
         alg.reward_clipping = (-1.0, 1.0) if env_params.is_atari else None
+    if flt is not None and getattr(flt, "_observation_filters", None) and hasattr(alg, "normalize_observations"):
+        # an ObservationNormalizationFilter of the INPUT filter (presets/Mujoco_PPO.py:33-34): the same running
+        # statistics, served by the agent's normalisation path
+        for d in flt._observation_filters.values():
+            for f in d.values():
+                if isinstance(f, ObservationNormalizationFilter):
+                    alg.normalize_observations = True
+                else:
+                    raise ValueError("input observation filter {!r} has no device implementation".format(f))
     pre = getattr(agent_params, "pre_network_filter", None)
     if pre is not None and hasattr(pre, "_observation_filters"):
         for d in pre._observation_filters.values():

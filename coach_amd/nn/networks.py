@@ -1457,3 +1457,137 @@ class ACERNet(_WindowAccumulatingNet):
     def apply_accumulated(self, grad_scale=1.0):
         super().apply_accumulated(grad_scale)
         self.adam_steps += 1
+
+
+class PPOCriticNet(_NetBase):
+    """PPOCriticNetworkParameters (agents/ppo_agent.py:40-49): one embedder + FC middleware tower (tanh) under the plain
+    VHead (heads/v_head.py:43-52: Dense(feat, 1), normalized-columns(1.0) initialisation, MSE through
+    rlx_regression_loss), with a target copy."""
+
+    def __init__(self, device, obs_shape, activation="tanh", embedder="Medium", middleware="Medium", learning_rate=2.5e-4,
+                 adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, seed=0):
+        self.obs_shape, self.image = tuple(obs_shape), len(obs_shape) == 3
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        self.v_head = G.Dense(self.params, "main/v_head/dense", feat, 1, None, 1, init=G.normalized_columns(1.0))
+        self.modules = [self.torso, self.v_head]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
+        self.scalars = torch.zeros(1, dtype=torch.float32, device=device)
+        self.loss = self.scalars[0:1]
+
+    def values(self, obs, B, use_target=False, tag="val"):
+        """V(s) [B] (fill_advantages, ppo_agent.py:163)"""
+        w = self.target if use_target else None
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        return self.v_head.forward(self.ctx, acts[-1], tag=tag, weights=w).data.view(-1)
+
+    def forward_backward(self, obs, B, value_targets):
+        """accumulate_gradients of one critic minibatch (:233): forward, MSE against the fp32 targets [B], backward;
+        the loss in self.loss"""
+        ctx = self.ctx
+        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+        v = self.v_head.forward(ctx, acts[-1], tag="train")
+        self.lib.regression_loss(v.data, 1, value_targets, 1, None, B, 1, 0, 1.0, 1.0, v.ensure_grad(), 1, self.loss,
+                                 ctx.stream)
+        self.v_head.backward(ctx, acts[-1], v)
+        self.torso.backward(ctx, acts)
+
+    def train_minibatch(self, obs, B, value_targets, grad_scale=1.0):
+        self.forward_backward(obs, B, value_targets)
+        self.apply_gradients(grad_scale, with_norm=True)
+        return self.loss
+
+
+class PPOActorNet(_NetBase):
+    """PPOActorNetworkParameters (agents/ppo_agent.py:52-62): one embedder + FC middleware tower (tanh) under the PPOHead
+    built WITHOUT a clip range and with the KL penalty (heads/ppo_head.py:40-47, :66-72) — discrete: Dense(feat, A)
+    'policy_fc'; continuous: 'policy_mean' with the normalized-columns(0.01) initialiser plus the state-independent
+    'policy_log_std' vector — with a target copy (the old policy).  The head's loss and gradient are ONE launch
+    (rlx_ppo_kl_discrete_loss / rlx_ppo_kl_continuous_loss, csrc/ppo_kl.hip); kl_coefficient lives on the device, an
+    epoch's fetch sums in `epoch_sums`, and update_kl_coefficient() is ppo_agent.py:329-353 without a host read."""
+
+    def __init__(self, device, obs_shape, n_actions, activation="tanh", embedder="Medium", middleware="Medium",
+                 learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, beta_entropy=0.01,
+                 target_kl_divergence=0.01, initial_kl_coefficient=1.0, high_kl_penalty_coefficient=1000.0,
+                 use_kl_regularization=True, seed=0, continuous=False):
+        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        self.continuous = bool(continuous)
+        limit = 32 if self.continuous else 18
+        if not 1 <= self.A <= limit:
+            raise ValueError("the PPO head serves 1 .. %d %s (got %d)"
+                             % (limit, "action dimensions" if self.continuous else "actions", self.A))
+        self.beta, self.use_kl = float(beta_entropy), bool(use_kl_regularization)
+        self.target_kl, self.high_kl = float(target_kl_divergence), float(high_kl_penalty_coefficient)
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        if self.continuous:
+            self.pi_head = G.Dense(self.params, "main/ppo_head/policy_mean", feat, self.A, None, 1,
+                                   init=G.normalized_columns(0.01))
+            self.params.add_group([("main/ppo_head/policy_log_std", (self.A,))])        # zeros (ppo_head.py:133-137)
+        else:
+            self.pi_head = G.Dense(self.params, "main/ppo_head/policy_fc", feat, self.A, None, 1)
+        self.modules = [self.torso, self.pi_head]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
+        # [surrogate, mean entropy, mean KL, total, penalty factor c]
+        self.scalars = torch.zeros(5, dtype=torch.float32, device=device)
+        self.kl_coefficient = torch.full((1,), float(initial_kl_coefficient), dtype=torch.float32, device=device)
+        self.epoch_sums = torch.zeros(4, dtype=torch.float32, device=device)   # += {KL, entropy, total, 1} per minibatch
+        self.kl_mean = torch.zeros(1, dtype=torch.float32, device=device)
+
+    def policy_probs(self, obs, B, use_target=False, tag="act", out=None):
+        """softmax(policy_fc(tower(obs))) [B, A]; the target weights are the old policy"""
+        w = self.target if use_target else None
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        logits = self.pi_head.forward(self.ctx, acts[-1], tag=tag, weights=w)
+        probs = out if out is not None else self.ctx.buffer("probs", (B, self.A), tag=tag)
+        self.lib.softmax(logits.data, self.A, B, self.A, probs, self.A, self.ctx.stream)
+        return probs
+
+    def policy_mean_std(self, obs, B, use_target=False, tag="act", out_mean=None, out_std=None):
+        """[policy_mean, policy_std] [B, A] each (ppo_head.py:138-144): std = exp(log_std) tiled over the batch"""
+        w = self.target if use_target else None
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        mean = self.pi_head.forward(self.ctx, acts[-1], tag=tag, weights=w).data.view(B, self.A)
+        std = out_std if out_std is not None else self.ctx.buffer("policy_std", (B, self.A), tag=tag)
+        self.lib.exp_rows(self.params.w("main/ppo_head/policy_log_std", 0, w), std, B, self.A, self.ctx.stream)
+        if out_mean is not None:
+            out_mean.copy_(mean)
+            mean = out_mean
+        return mean, std
+
+    def forward_backward(self, obs, B, actions, advantages, old_policy, ratio_out=None, accumulate=True):
+        """accumulate_gradients of one actor minibatch (ppo_agent.py:278-288): forward, the head launch, backward.
+        old_policy: the old probabilities [B, A], or (old_mean, old_std).  accumulate: add the minibatch's fetches onto
+        epoch_sums."""
+        ctx = self.ctx
+        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+        z = self.pi_head.forward(ctx, acts[-1], tag="train")
+        acc = self.epoch_sums if accumulate else None
+        if self.continuous:
+            old_mean, old_std = old_policy
+            self.lib.ppo_kl_continuous_loss(z.data, self.A, self.params.w("main/ppo_head/policy_log_std"), actions,
+                                            advantages, old_mean, old_std, self.A, B, self.A, self.beta, 1.0,
+                                            self.kl_coefficient, 2.0 * self.target_kl, self.high_kl, int(self.use_kl),
+                                            z.ensure_grad(), self.A, self.params.g("main/ppo_head/policy_log_std"),
+                                            self.scalars, ratio_out, acc, ctx.stream)
+        else:
+            self.lib.ppo_kl_discrete_loss(z.data, self.A, actions, advantages, old_policy, self.A, B, self.A, self.beta,
+                                          1.0, self.kl_coefficient, 2.0 * self.target_kl, self.high_kl, int(self.use_kl),
+                                          z.ensure_grad(), self.A, self.scalars, ratio_out, self.status, acc, ctx.stream)
+        self.pi_head.backward(ctx, acts[-1], z)
+        self.torso.backward(ctx, acts)
+
+    def train_minibatch(self, obs, B, actions, advantages, old_policy, grad_scale=1.0, ratio_out=None):
+        self.forward_backward(obs, B, actions, advantages, old_policy, ratio_out)
+        self.apply_gradients(grad_scale, with_norm=True)
+        return self.scalars
+
+    def reset_epoch_sums(self):
+        self.epoch_sums.zero_()
+
+    def update_kl_coefficient(self):
+        """update_kl_coefficient (ppo_agent.py:329-353) from epoch_sums (the LAST epoch's: call reset_epoch_sums() before
+        every epoch — forward_backward adds onto them by default); the mean KL goes to kl_mean.  With nothing
+        accumulated since the reset the coefficient is kept and kl_mean is 0.  Nothing is read on the host."""
+        self.lib.ppo_kl_coefficient_update(self.epoch_sums, self.target_kl, self.kl_coefficient, self.kl_mean,
+                                           self.ctx.stream)

@@ -768,6 +768,38 @@ int rlx_ppo_continuous_loss(const float *mean, long long ld, const float *log_st
                             float *dlog_std, float *scalars, float *likelihood_ratio,
                             float *clipped_likelihood_ratio, const float *clip_scale, void *stream);
 
+/* PPO-penalty head (agents/ppo_agent.py; heads/ppo_head.py:52-98 without clipping): unclipped surrogate plus
+ * kl_coefficient * KL + high_kl_penalty_coefficient * max(0, KL - kl_cutoff)^2 with KL the BATCH mean of
+ * KL(old || new), so every gradient row carries c = kl_coefficient + 2 * high * max(0, KL - kl_cutoff).  One launch of
+ * one workgroup, batch <= 1024, no float atomics.  Arguments as rlx_ppo_discrete_loss / rlx_ppo_continuous_loss without
+ * the clip ones; kl_coefficient is a DEVICE scalar (read by the kernel, so a captured graph follows
+ * rlx_ppo_kl_coefficient_update); kl_cutoff = 2 * target_kl_divergence; use_kl_regularization = 0 drops both KL terms.
+ * scalars[5] = {surrogate loss, mean entropy, mean KL, total, c}.  accumulate (optional, 4 device floats) receives
+ * += {mean KL, mean entropy, total, 1}: an epoch's running sums.  Every output is optional.
+ * Discrete: 1 <= n_actions <= 18; an action outside [0, n_actions) sets status bit 0, and its row adds no term (the
+ * means still divide by batch), gets a zero gradient row and a likelihood ratio of 0.
+ * Continuous: 1 <= action_dim <= 32; dlog_std[action_dim] receives the batch-summed gradient. */
+int rlx_ppo_kl_discrete_loss(const float *logits, long long ld, const int *actions, const float *advantages,
+                             const float *old_probs, long long ld_old, int batch, int n_actions, float beta_entropy,
+                             float grad_scale, const float *kl_coefficient, float kl_cutoff,
+                             float high_kl_penalty_coefficient, int use_kl_regularization, float *dlogits,
+                             long long ld_grad, float *scalars, float *likelihood_ratio, int *status, float *accumulate,
+                             void *stream);
+int rlx_ppo_kl_continuous_loss(const float *mean, long long ld, const float *log_std, const float *actions,
+                               const float *advantages, const float *old_mean, const float *old_std, long long ld_old,
+                               int batch, int action_dim, float beta_entropy, float grad_scale,
+                               const float *kl_coefficient, float kl_cutoff, float high_kl_penalty_coefficient,
+                               int use_kl_regularization, float *dmean, long long ld_grad, float *dlog_std,
+                               float *scalars, float *likelihood_ratio, float *accumulate, void *stream);
+/* update_kl_coefficient (agents/ppo_agent.py:329-353) on the device: mean KL = epoch_sums[0] / epoch_sums[3] (the
+ * accumulate buffer above); kl_coefficient[0] *= 1.5 when it exceeds 1.3 * target_kl, /= 1.5 when it is below
+ * 0.7 * target_kl (fp32 comparisons against the fp64 products rounded to fp32, fp32 product / quotient);
+ * kl_mean_out (optional) receives the mean.  A count epoch_sums[3] of 0 (nothing accumulated) leaves the coefficient
+ * as it is and writes a mean of 0.  target_kl is the python float itself: float(1.3 * 0.01) differs from
+ * float(1.3 * float(0.01)). */
+int rlx_ppo_kl_coefficient_update(const float *epoch_sums, double target_kl, float *kl_coefficient, float *kl_mean_out,
+                                  void *stream);
+
 /* ------------------------------------------ optimiser / target mixing (K11) -- */
 /* state = {beta1_power, beta2_power} (2 device floats).  tf.train.AdamOptimizer as built in
  * architectures/tensorflow_components/general_network.py:390-394. */
