@@ -99,3 +99,15 @@ class ACERPolicyHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='acer_policy_head_params',
                  rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class MeasurementsPredictionHeadParameters(HeadParameters):
+    """MeasurementsPredictionHeadParameters (head_parameters.py:141-149): an expectation stream Dense(256, activation) ->
+    Dense(K) and an action stream Dense(256, activation) -> Dense(A * K), K = num_predicted_steps_ahead * measurements,
+    merged like a dueling head (heads/measurements_prediction_head.py:39-57).  The merge, the NaN-ignoring squared loss
+    and the gradients of the two stream outputs come from rlx_dfp_head_loss."""
+    head_type = "MeasurementsPredictionHead"
+
+    def __init__(self, activation_function='relu', name='measurements_prediction_head_params',
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

@@ -47,9 +47,9 @@ import torch
 
 from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
-from ..nn.networks import (ACERNet, ActorCriticNet, ClippedPPONet, DQNNet, NStepQNet, PPOActorNet, PPOCriticNet,
+from ..nn.networks import (ACERNet, ActorCriticNet, ClippedPPONet, DFPNet, DQNNet, NStepQNet, PPOActorNet, PPOCriticNet,
                            PolicyGradientNet,
-                           acer_net_kwargs, actor_critic_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs,
+                           acer_net_kwargs, actor_critic_net_kwargs, dfp_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs,
                            policy_gradient_net_kwargs)
 from .architecture import Architecture
 
@@ -914,7 +914,94 @@ class PPOCriticArchitecture(HipArchitecture):
         return loss, [loss], float(net.norm.item()), []
 
 
+# ==================================================================================== DFP
+class DFPArchitecture(HipArchitecture):
+    """goal / measurements / observation embedders -> concatenation -> MeasurementsPredictionHead, no target network, fed
+    the way DFPAgent feeds it (dfp_agent.py:150-167, :172-174): inputs 'observation' (B, D), 'measurements' (B, M) and
+    'goal' (B, M) — a missing or an extra key is refused; targets = the prediction with the taken actions' rows replaced
+    by the stored future measurements (B, A, K), NaN where a step lies past the episode's end.  predict -> the prediction
+    (B, A, K).  A full target tensor is the head's loss against every entry: the entries that equal the prediction and
+    the NaN entries give exactly zero, so the row with the differing entries is the taken action's
+    (rlx_dfp_head_loss; more than one differing row per sample is refused).  accumulate_gradients -> total loss, [the
+    head's loss], the gradients' norm."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        if not hasattr(spaces.action, "actions"):
+            raise ValueError("a Box action space is not served: the DFP network predicts measurements per discrete action")
+        if len(spaces.state['observation'].shape) != 1:
+            raise ValueError("image observations are not served: the DFP network has vector embedders only")
+        return DFPNet(self.device, int(spaces.state['observation'].shape[0]), int(spaces.state['measurements'].shape[0]),
+                      len(spaces.action.actions), int(agent_parameters.algorithm.num_predicted_steps_ahead),
+                      **dfp_net_kwargs(np_, seed))
+
+    def _handles(self):
+        self.inputs = list(DFPNet.INPUTS)
+        self.output_heads = [_HeadFetches(0, ['output'])]
+
+    def _inputs(self, inputs):
+        if sorted(inputs) != sorted(self.inputs):
+            raise ValueError('the DFP network takes the inputs {}, got {}'.format(self.inputs, sorted(inputs)))
+        net = self.net
+        B = int(np.asarray(inputs['observation']).shape[0]) if not isinstance(inputs['observation'], torch.Tensor) \
+            else int(inputs['observation'].shape[0])
+        out = {}
+        for k in self.inputs:
+            t = self._to_device(inputs[k], torch.float32).contiguous()
+            if tuple(t.shape) != (B, net.dims[k]):
+                raise ValueError("input {} has shape {}, the network takes {}".format(k, tuple(t.shape), (B, net.dims[k])))
+            out[k] = t
+        return out, B
+
+    def _merged(self, e, x, B):
+        """the head's output from the two stream outputs: rlx_dfp_head_loss's y_out with no valid target (all NaN)."""
+        net = self.net
+        y = torch.empty(B, net.A, net.K, dtype=torch.float32, device=self.device)
+        nan = torch.full((B, net.K), float("nan"), dtype=torch.float32, device=self.device)
+        zero = torch.zeros(B, dtype=torch.int32, device=self.device)
+        de = torch.empty(B, net.K, dtype=torch.float32, device=self.device)           # (all zero: nothing to learn from)
+        dx = torch.empty(B, net.A * net.K, dtype=torch.float32, device=self.device)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        net.lib.dfp_head_loss(e, net.K, x, net.A * net.K, zero, nan, net.A, net.K, B, 1.0, de, net.K, dx, net.A * net.K,
+                              net.loss_ws, net.ticket, loss, net.status, y, None, _rlx.current_stream())
+        return y
+
+    def _queue(self, inputs, tag):
+        ins, B = self._inputs(inputs)
+        if B > 256:
+            raise ValueError("the DFP head's launches take at most 256 rows")
+        e, x = self.net.streams(ins, B, tag="%s_%d" % (tag, B))
+        return [self._merged(e, x, B)]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        ins, B = self._inputs(inputs)
+        if importance_weights is not None:
+            raise ValueError("the measurements prediction head takes no importance weights")
+        if additional_fetches:
+            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        target = targets[0] if isinstance(targets, (list, tuple)) else targets
+        target = self._to_device(target, torch.float32).contiguous()
+        if tuple(target.shape) != (B, net.A, net.K):
+            raise ValueError("targets shape {} does not match the head output {}"
+                             .format(tuple(target.shape), (B, net.A, net.K)))
+        # which row of every sample differs from the prediction?  (NaN entries differ from everything: they count, so an
+        # all-NaN row is found as well; its loss and gradient are zero either way)
+        e, x = net.streams(ins, B, tag="targets_%d" % B)
+        y = self._merged(e, x, B)
+        differs = ((target != y) | torch.isnan(target)).any(dim=2)
+        if int((differs.sum(dim=1) > 1).sum().item()):
+            raise ValueError("the targets differ from the prediction in more than one action's row of a sample")
+        actions = differs.int().argmax(dim=1).int().contiguous()
+        future = target[torch.arange(B, device=self.device), actions.long()].contiguous()
+        net.accumulate(ins, B, actions, future)
+        net.grad_norm()
+        total_loss = float(net.loss.item())
+        net.check_status()
+        return total_loss, [total_loss], float(net.norm.item()), []
+
+
 _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
+                       "DFPNetworkParameters": DFPArchitecture,
                        "PPOActorNetworkParameters": PPOActorArchitecture,
                        "PPOCriticNetworkParameters": PPOCriticArchitecture,
                        "ACERNetworkParameters": ACERArchitecture,

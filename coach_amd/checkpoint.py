@@ -22,7 +22,8 @@ def _tensors_of(obj, names):
 
 _MEMORY_TENSORS = ["ring", "fpos", "epoff", "t_fpos", "t_epoff", "cur_state", "obs", "next_obs", "action",
                    "reward", "game_over", "mask", "sum_tree", "min_tree", "max_tree", "max_priority",
-                   "n_step_discounted_rewards", "act_value", "act_probs"]
+                   "n_step_discounted_rewards", "act_value", "act_probs",
+                   "measurements", "future_measurements"]      # DFP: the states' measurements and their future targets
 _MEMORY_SCALARS = ["cursor", "count", "pending", "committed_total", "steps", "_open", "_list_len",
                    "next_leaf_idx_to_write", "_frames_total", "_episode_steps", "_step_frames",
                    "_steps_written", "_gstep", "_ep_start", "_episodes", "_episode_first_step", "_order", "_order_head", "_order_len"]
@@ -51,7 +52,9 @@ def agent_state(agent):
     st["agent"]["scalars"] = {k: copy.deepcopy(getattr(agent, k)) for k in _AGENT_SCALARS if hasattr(agent, k)}
     st["agent"]["phase"] = agent.phase.name                   # RunPhase of the agent (and its policy)
     # uniforms_all: the exploration draws of the running PPO phase (made at its first step)
-    st["agent"]["tensors"] = _tensors_of(agent, ["ep_return", "ep_len", "ep_acc", "uniforms_all"])
+    # accumulated_reward, cur_measurements(32): DFP's running sum of shaped rewards and the current states' measurements
+    st["agent"]["tensors"] = _tensors_of(agent, ["ep_return", "ep_len", "ep_acc", "uniforms_all", "accumulated_reward",
+                                                 "cur_measurements", "cur_measurements32"])
     st["env"] = {"tensors": _tensors_of(agent.env, ["obs", "episode", "step_in_episode"]),
                  "total_steps": agent.env.total_steps,
                  "host": {k: getattr(agent.env, k).copy() for k in ("t_host", "dones_host") if hasattr(agent.env, k)}}

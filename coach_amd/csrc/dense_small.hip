@@ -16,6 +16,7 @@
 //             for both dW and the activation derivative of the layer below (dx is written as the
 //             lower layer's dz), the 4 row-group partials of dW are combined in a fixed order.
 // Latency-bound by construction (a few hundred KB); the point is 2 launches per head instead of ~8.
+#define RLX_DENSE_SMALL_LEAKY      // these launches serve RLX_ACT_LEAKY_RELU (the fused users of the body do not)
 #include "dense_small_body.hpp"
 
 namespace {
@@ -61,7 +62,7 @@ int rlx_dense_small_forward(const float *x, long long x_tower_stride, const floa
     RLX_REQUIRE(x && w && y, "rlx_dense_small_forward: null pointer");
     RLX_REQUIRE(towers > 0 && M > 0 && K > 0 && N > 0 && N <= kMaxN,
                 "rlx_dense_small_forward: need 1 <= N <= %d (got M=%d K=%d N=%d)", kMaxN, M, K, N);
-    RLX_REQUIRE(activation >= 0 && activation <= 2, "rlx_dense_small_forward: unknown activation");
+    RLX_REQUIRE(activation >= 0 && activation <= RLX_ACT_LEAKY_RELU, "rlx_dense_small_forward: unknown activation");
     SmallDense p{x, x_tower_stride, w, w_tower_stride, bias, bias_tower_stride, y, y_tower_stride,
                  M, K, N, activation};
     dim3 grid(M, towers);
@@ -84,7 +85,8 @@ int rlx_dense_small_backward(const float *x, long long x_tower_stride, const flo
     RLX_REQUIRE(dw || dx, "rlx_dense_small_backward: nothing to produce");
     RLX_REQUIRE(towers > 0 && M > 0 && K > 0 && N > 0 && N <= kMaxN,
                 "rlx_dense_small_backward: need 1 <= N <= %d (got M=%d K=%d N=%d)", kMaxN, M, K, N);
-    RLX_REQUIRE(activation >= 0 && activation <= 2 && lower_activation >= 0 && lower_activation <= 2,
+    RLX_REQUIRE(activation >= 0 && activation <= RLX_ACT_LEAKY_RELU && lower_activation >= 0 &&
+                    lower_activation <= RLX_ACT_LEAKY_RELU,
                 "rlx_dense_small_backward: unknown activation");
     RLX_REQUIRE(activation == 0 || y, "rlx_dense_small_backward: the activation derivative needs y");
     const int NN = N <= 1 ? 1 : N <= 4 ? 4 : N <= 8 ? 8 : 16;
@@ -119,7 +121,7 @@ int rlx_dense_small_forward_multi(const rlx_small_dense_problem *problems_host, 
         RLX_REQUIRE(q.x && q.w && q.y, "rlx_dense_small_forward_multi: null pointer in problem %d", i);
         RLX_REQUIRE(q.towers > 0 && q.M > 0 && q.K > 0 && q.N > 0 && q.N <= kMaxN,
                     "rlx_dense_small_forward_multi: problem %d needs 1 <= N <= %d", i, kMaxN);
-        RLX_REQUIRE(q.activation >= 0 && q.activation <= 2, "rlx_dense_small_forward_multi: unknown activation");
+        RLX_REQUIRE(q.activation >= 0 && q.activation <= RLX_ACT_LEAKY_RELU, "rlx_dense_small_forward_multi: unknown activation");
         m.p[i] = SmallDense{q.x, q.x_tower_stride, q.w, q.w_tower_stride, q.bias, q.bias_tower_stride,
                             q.y, q.y_tower_stride, q.M, q.K, q.N, q.activation};
         m.towers[i] = q.towers;
@@ -150,7 +152,8 @@ int rlx_dense_small_backward_multi(const rlx_small_dense_problem *problems_host,
                     "rlx_dense_small_backward_multi: null pointer in problem %d", i);
         RLX_REQUIRE(q.towers > 0 && q.M > 0 && q.K > 0 && q.N > 0 && q.N <= kMaxN,
                     "rlx_dense_small_backward_multi: problem %d needs 1 <= N <= %d", i, kMaxN);
-        RLX_REQUIRE(q.activation >= 0 && q.activation <= 2 && q.lower_activation >= 0 && q.lower_activation <= 2,
+        RLX_REQUIRE(q.activation >= 0 && q.activation <= RLX_ACT_LEAKY_RELU && q.lower_activation >= 0 &&
+                        q.lower_activation <= RLX_ACT_LEAKY_RELU,
                     "rlx_dense_small_backward_multi: unknown activation");
         RLX_REQUIRE(q.activation == 0 || q.y, "rlx_dense_small_backward_multi: the activation derivative needs y");
         m.p[i] = SmallDenseBwd{q.x, q.x_tower_stride, q.w, q.w_tower_stride, q.dy, q.dy_tower_stride,

@@ -9,11 +9,17 @@ constexpr int kMaxN = 16;
 __device__ __forceinline__ float act_apply(float v, int act) {
     if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == RLX_ACT_TANH) return tanhf(v);
+#ifdef RLX_DENSE_SMALL_LEAKY      // dense_small.hip alone: every other file that includes this body compiles as before
+    if (act == RLX_ACT_LEAKY_RELU) return v > 0.f ? v : 0.2f * v;
+#endif
     return v;
 }
 __device__ __forceinline__ float act_deriv_out(float y, int kind) {
     if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
     if (kind == RLX_ACT_TANH) return 1.f - y * y;
+#ifdef RLX_DENSE_SMALL_LEAKY
+    if (kind == RLX_ACT_LEAKY_RELU) return y > 0.f ? 1.f : 0.2f;
+#endif
     return 1.f;
 }
 

@@ -2065,6 +2065,19 @@ __global__ void act_backward_kernel(float *__restrict__ dy, const float *__restr
         dy[i] *= act_deriv(y[i], kind);
 }
 
+// RLX_ACT_LEAKY_RELU (alpha 0.2, tf.nn.leaky_relu's default) as launches of its own: the epilogues above, and so every hot
+// kernel of this file, compile exactly as they did before the activation existed.
+__global__ void leaky_relu_kernel(float *__restrict__ y, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float v = y[i];
+        y[i] = v > 0.f ? v : 0.2f * v;
+    }
+}
+__global__ void leaky_relu_backward_kernel(float *__restrict__ dy, const float *__restrict__ y, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        dy[i] *= y[i] > 0.f ? 1.f : 0.2f;                  // alpha at 0, as TF's gradient
+}
+
 // im2col offset tables (see header comment).
 __global__ void conv_tables_kernel(int *__restrict__ rowbase, int *__restrict__ koff, int batch,
                                    int H, int W, int C, int KH, int KW, int stride, int OH, int OW) {
@@ -3002,9 +3015,21 @@ int rlx_colsum(const float *x, int M, int N, long long ld, float *out, int accum
 
 int rlx_act_backward(float *dy, const float *y, long long n, int kind, void *stream) {
     RLX_REQUIRE(dy && y && n > 0, "rlx_act_backward: bad arguments");
-    RLX_REQUIRE(kind >= 0 && kind <= 2, "rlx_act_backward: unknown activation %d", kind);
+    RLX_REQUIRE(kind >= 0 && kind <= RLX_ACT_LEAKY_RELU, "rlx_act_backward: unknown activation %d", kind);
     if (kind == RLX_ACT_NONE) return RLX_OK;
+    if (kind == RLX_ACT_LEAKY_RELU) {
+        RLX_LAUNCH((leaky_relu_backward_kernel), rlx::grid_for(n, 256), 256, 0, rlx::as_stream(stream), dy, y, n);
+        RLX_LAUNCH_CHECK();
+        return RLX_OK;
+    }
     RLX_LAUNCH((act_backward_kernel), rlx::grid_for(n, 256), 256, 0, rlx::as_stream(stream), dy, y, n, kind);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_leaky_relu(float *y, long long n, void *stream) {
+    RLX_REQUIRE(y && n > 0, "rlx_leaky_relu: bad arguments");
+    RLX_LAUNCH((leaky_relu_kernel), rlx::grid_for(n, 256), 256, 0, rlx::as_stream(stream), y, n);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -46,12 +46,18 @@ class EpisodicExperienceReplayParameters(ExperienceReplayParameters):        # :
 
 class EpisodicExperienceReplay(ExperienceReplay):
     def __init__(self, max_size, allow_duplicates_in_batch_sampling=True, n_step=-1, discount=0.99,
-                 max_episode_length=None, **device_kwargs):
+                 max_episode_length=None, measurements_dim=None, future_measurements=None, **device_kwargs):
         """
         :param max_size: (MemoryGranularity.Transitions | Episodes, n)               (reference signature)
         :param n_step: steps summed into n_step_discounted_rewards (-1: to the episode end)   (reference signature)
         :param discount: Episode(discount=...) — the agent's discount factor (agent.py:619)
         :param max_episode_length: the env's time limit; bounds the ring (defaults to min_episode_length)
+        :param measurements_dim: M — keep an fp64 column [rows][M] of the STATE's measurements (Direct Future Prediction;
+                                 store() then takes them per step); absent (None) unless asked for
+        :param future_measurements: (steps S, scale factors [M], last_step) — keep an fp32 column [rows][S * M] of every
+                                 transition's future-measurement targets as well, written from the episode's own future
+                                 when an env's episode is stored (DFPAgent._update_measurements_targets,
+                                 rlx_dfp_future_measurements); last_step: HandlingTargetsAfterEpisodeEnd.LastStep, else NAN
         """
         if not isinstance(n_step, int) or (n_step < 1 and n_step != -1):
             raise ValueError("n-step should be an integer with value >= 1, or set to -1 for always setting to "
@@ -73,6 +79,20 @@ class EpisodicExperienceReplay(ExperienceReplay):
                          **device_kwargs)
         self.max_size = (unit, int(amount))
         self.n_step_discounted_rewards = torch.zeros(self.rows, dtype=torch.float64, device=self.device)
+        self.measurements = self.future_measurements = None
+        if future_measurements is not None and measurements_dim is None:
+            raise ValueError("the future-measurements column is computed from the measurements column")
+        if measurements_dim is not None:
+            self.M = int(measurements_dim)
+            self.measurements = torch.zeros(self.rows, self.M, dtype=torch.float64, device=self.device)
+        if future_measurements is not None:
+            steps, scale, last_step = future_measurements
+            if len(scale) != self.M:
+                raise ValueError("one scale factor per measurement: got {} for {}".format(len(scale), self.M))
+            self.future_steps, self.future_last_step = int(steps), bool(last_step)
+            self.future_scale = torch.tensor([float(x) for x in scale], dtype=torch.float64, device=self.device)
+            self.future_measurements = torch.zeros(self.rows, self.future_steps * self.M, dtype=torch.float32,
+                                                   device=self.device)
         self._order = np.zeros(transitions + 2 * self.Tmax + 1, dtype=np.int64)   # ring of listed rows
         self.clean()
 
@@ -108,8 +128,10 @@ class EpisodicExperienceReplay(ExperienceReplay):
 
     # ------------------------------------------------------------------------------ rollout side
     def store(self, actions, rewards, game_overs, next_obs, reset_obs, record=True, dones=None, defer=False,
-              episode_end=False, dones_host=None):
-        """One vector step (Agent.observe_transition -> current_episode_buffer.insert, agent.py:956-962), then
+              episode_end=False, dones_host=None, measurements=None):
+        """measurements: the STATES' measurements of this step's transitions (device fp64 [n_env][M]); required where
+        the memory keeps the column.
+        One vector step (Agent.observe_transition -> current_episode_buffer.insert, agent.py:956-962), then
         `store_episode` for every env whose episode ended (dones_host: host bool[n_env]; None = lockstep envs,
         all ended iff episode_end).  `defer` is irrelevant here: an episode becomes sampleable only when it is
         complete, and its terminal transition is observed at once (level_manager.py:260-264)."""
@@ -132,6 +154,11 @@ class EpisodicExperienceReplay(ExperienceReplay):
             row0 = (self._gstep % self._ring_steps) * self.n_env
             pairs = [(actions, self.action), (rewards, self.reward), (stored_go, self.game_over),
                      (self.cur_state, self.obs), (next_obs, self.next_obs)]
+            if (measurements is None) != (self.measurements is None):
+                raise ValueError("a memory with a measurements column is stored with measurements, one without it "
+                                 "without them")
+            if measurements is not None:
+                pairs.append((measurements, self.measurements))
             self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, None, 0, row0, self.n_env,
                                   self.rows, self.n_env, self.status, s)
         self.lib.select_rows(game_overs, reset_obs, next_obs, self.cur_state, self.n_env, self.obs_dim * 4, s)
@@ -163,6 +190,10 @@ class EpisodicExperienceReplay(ExperienceReplay):
         self._episode_first_step.append(s0)
         self.lib.episode_nstep_returns(self.reward, self.n_step_discounted_rewards, None, s0, T, e, self.n_env,
                                        self._ring_steps, self.discount, self.n_step, _rlx.current_stream())
+        if self.future_measurements is not None:
+            self.lib.dfp_future_measurements(self.measurements, self.future_measurements, self.future_scale, s0, T, e,
+                                             self.n_env, self._ring_steps, self.future_steps, self.M,
+                                             int(self.future_last_step), _rlx.current_stream())
         # _enforce_max_length: whole oldest episodes leave (:300-317)
         if self.max_episodes is not None:
             while len(self._episodes) > self.max_episodes:
@@ -207,17 +238,34 @@ class EpisodicExperienceReplay(ExperienceReplay):
         b = super()._batch_buffers(size)
         if "n_step_discounted_rewards" not in b:
             b["n_step_discounted_rewards"] = torch.empty(size, dtype=torch.float64, device=self.device)
+            if self.measurements is not None:
+                b["measurements64"] = torch.empty(size, self.M, dtype=torch.float64, device=self.device)
+                b["measurements"] = torch.empty(size, self.M, dtype=torch.float32, device=self.device)
+            if self.future_measurements is not None:
+                b["future_measurements"] = torch.empty(size, self.future_steps * self.M, dtype=torch.float32,
+                                                       device=self.device)
         return b
 
     def _extra_gather_columns(self):
-        return [(self.n_step_discounted_rewards, "n_step_discounted_rewards")]
+        cols = [(self.n_step_discounted_rewards, "n_step_discounted_rewards")]
+        if self.measurements is not None:
+            cols.append((self.measurements, "measurements64"))
+        if self.future_measurements is not None:
+            cols.append((self.future_measurements, "future_measurements"))
+        return cols
 
     def collate(self, drawn, size, rows_dev=None):
         b = self._gather_rows(drawn, size, rows_dev)
-        return DeviceBatch(size, {"observation": b["state"]}, {"observation": b["next_state"]},
-                           b["action"], b["reward"], b["game_over"],
-                           info={"logical_idx": drawn, "states_pair": b["states_pair"],
-                                 "n_step_discounted_rewards": b["n_step_discounted_rewards"]})
+        states = {"observation": b["state"]}
+        info = {"logical_idx": drawn, "states_pair": b["states_pair"],
+                "n_step_discounted_rewards": b["n_step_discounted_rewards"]}
+        if self.measurements is not None:
+            b["measurements"].copy_(b["measurements64"])          # the network's input is fp32 (a cast, no arithmetic)
+            states["measurements"] = b["measurements"]
+        if self.future_measurements is not None:
+            info["future_measurements"] = b["future_measurements"]
+        return DeviceBatch(size, states, {"observation": b["next_state"]}, b["action"], b["reward"], b["game_over"],
+                           info=info)
 
     def _steps_written_now(self):
         return self._gstep

@@ -391,6 +391,15 @@ class Layer:
         return t0, nt
 
 
+# What rlx_gemm's epilogue and the fused launches implement (conv, noisy dense, batch norm, the PPO head launches, the row
+# chains and the fused MLP updates).  "leaky_relu" is served by the rlx_dense_small_* launches, rlx_act_backward and
+# rlx_leaky_relu only (a branch in the GEMM epilogues cost the flagship update 0.35 %, so the hot kernels were left as
+# they are): a wide leaky layer is a product without an activation followed by rlx_leaky_relu, its derivative is never
+# folded into a product's epilogue, and a fused launch is never offered a leaky layer — its adapter declines (the layer
+# launches take over) or raises.
+FUSED_ACTS = (None, "relu", "tanh")
+
+
 class Dense(Layer):
     """y = act(x W + b), tf.layers.dense (layers.py:168-185).  `towers` copies in one launch."""
 
@@ -437,6 +446,10 @@ class Dense(Layer):
             a_stride, TT = x.tower_stride(), T
         y = ctx.buffer(self.name, (TT, M, self.N), tag=tag)
         desc, head_outs = None, None
+        gemm_act = self.act if self.act in FUSED_ACTS else None          # leaky_relu: a launch of its own behind the product
+        if gemm_act is not self.act and not (self.N <= SMALL_N and not x.u8) and (pair or row_heads or not launch):
+            raise NotImplementedError("a wide %s layer runs as a product and an activation launch of its own (no "
+                                      "paired / row-head / deferred form)" % self.act)
         if self.N <= SMALL_N and not x.u8:
             # heads: coalesced FMA kernel, no MFMA tile / split-K round trip (csrc/dense_small.hip)
             if not pair:
@@ -458,17 +471,21 @@ class Dense(Layer):
             # the T towers read the SAME input: one GEMM over T*N columns loads (gathers) it once
             _rlx.gemm(M, T * self.N, self.K, x.data, p.w(self.kname, t0, weights), y,
                       b_strides=(self.N, 1), ldc=self.N, bias=p.w(self.bname, t0, weights),
-                      activation=self.act, batch=1, b_batch_stride=wstride, c_batch_stride=M * self.N,
+                      activation=gemm_act, batch=1, b_batch_stride=wstride, c_batch_stride=M * self.N,
                       bias_batch_stride=bstride, workspace=ctx.ws.splitk, n_fold=self.N)
+            if gemm_act is not self.act:
+                ctx.lib.leaky_relu(y, y.numel(), ctx.stream)
         else:
             if row_heads:
                 heads_arr, head_outs = row_head_problems(ctx, row_heads, y, M, self.N, tag, weights)
                 kw = dict(kw, row_heads=heads_arr)
             desc = _rlx.gemm(M, self.N, self.K, x.data, p.w(self.kname, t0, weights), y,
-                             bias=p.w(self.bname, t0, weights), activation=self.act, batch=TT,
+                             bias=p.w(self.bname, t0, weights), activation=gemm_act, batch=TT,
                              a_batch_stride=a_stride, b_batch_stride=wstride,
                              c_batch_stride=M * self.N, bias_batch_stride=bstride,
                              workspace=ctx.ws.splitk, launch=launch, **kw)
+            if gemm_act is not self.act:
+                ctx.lib.leaky_relu(y, y.numel(), ctx.stream)
         T = TT
         out = Tensor(y, M, self.N, T, grad_key=(ctx, self.name, tag), act=self.act)
         if row_heads:
@@ -502,6 +519,8 @@ class Dense(Layer):
             if need_dx:
                 x.grad_is_dz = lower is not None
             return
+        if lower not in FUSED_ACTS:                   # declined: no product's epilogue carries the leaky derivative, the
+            lower = None                              # lower layer applies its own (x.grad_is_dz stays False)
         if own_act is not None:                       # dz = dy * act'(y), in place
             ctx.lib.act_backward(dz, y.data, T * M * self.N, _rlx.ACT[own_act], ctx.stream)
         # dW[K,N] = x^T dz : A(k, m) = x[m, k]
@@ -577,6 +596,8 @@ class NoisyDense(Layer):
     def __init__(self, params, name, in_features, units, activation=None, towers=1, init=None):
         if towers != 1 or init is not None:
             raise NotImplementedError("NoisyDense: one tower, the layer's own initialiser")
+        if activation not in FUSED_ACTS:
+            raise NotImplementedError("NoisyDense: csrc/noisy_dense.hip implements %s, not %r" % (FUSED_ACTS, activation))
         self.name, self.K, self.N, self.act, self.T, self.params = name, in_features, units, activation, 1, params
         self.wmname, self.bmname = name + "/weight_mean", name + "/bias_mean"
         self.wsname, self.bsname = name + "/weight_stddev", name + "/bias_stddev"
@@ -617,6 +638,8 @@ class NoisyDense(Layer):
         if self.act is not None and not y.grad_is_dz:
             ctx.lib.act_backward(dz, y.data, M * self.N, _rlx.ACT[self.act], ctx.stream)
         lower = x.act if need_dx else None
+        if lower not in FUSED_ACTS:                  # declined: the lower layer applies its own derivative (grad_is_dz False)
+            lower = None
         g = (lambda n: p.g(n)) if need_dw else (lambda n: None)
         ctx.lib.noisy_dense_backward(x.data, self.K, p.w(self.wmname, 0, weights), p.w(self.wsname, 0, weights), dz,
                                      self.N, self.noise(ctx, y.grad_key[2]), g(self.wmname), g(self.wsname),
@@ -990,7 +1013,7 @@ def ppo_fc_rows(ctx, layer, x, v_head, pi_head, value_targets, actions, advantag
     p, hp = layer.params, v_head.params
     if not (layer.T == 2 and x.towers == 2 and not x.u8 and x.cols == layer.K and v_head.T == 1 and pi_head.T == 1 and
             v_head.N == 1 and 2 <= pi_head.N <= SMALL_N and v_head.K == layer.N and pi_head.K == layer.N and
-            v_head.act is None and pi_head.act is None and x.rows <= 256):
+            v_head.act is None and pi_head.act is None and x.rows <= 256 and layer.act in FUSED_ACTS):
         return None
     M, N, K = x.rows, layer.N, layer.K
     y = ctx.buffer(layer.name, (2, M, N), tag=tag)
@@ -1038,7 +1061,7 @@ def ppo_fc_rows(ctx, layer, x, v_head, pi_head, value_targets, actions, advantag
 def ppo_fc_heads_supported(ctx, layer, x, v_head, pi_head):
     """Can rlx_ppo_fc_heads run `layer` (the torso's last Dense, two towers) + both discrete heads + losses + the heads'
     backward pass as one launch?"""
-    return (isinstance(layer, Dense) and layer.T == 2 and x.towers == 2 and not x.u8 and v_head.T == 1 and pi_head.T == 1 and
+    return (isinstance(layer, Dense) and layer.act in FUSED_ACTS and layer.T == 2 and x.towers == 2 and not x.u8 and v_head.T == 1 and pi_head.T == 1 and
             v_head.N == 1 and v_head.K == layer.N and pi_head.K == layer.N and v_head.act is None and pi_head.act is None and
             x.data.data_ptr() % 16 == 0 and layer.params.stride(layer.kname) % 4 == 0 and
             bool(ctx.lib.ppo_fc_heads_supported(x.rows, layer.K, layer.N, pi_head.N)))

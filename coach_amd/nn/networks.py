@@ -1591,3 +1591,134 @@ class PPOActorNet(_NetBase):
         accumulated since the reset the coefficient is kept and kl_mean is 0.  Nothing is read on the host."""
         self.lib.ppo_kl_coefficient_update(self.epoch_sums, self.target_kl, self.kl_coefficient, self.kl_mean,
                                            self.ctx.stream)
+
+
+def dfp_net_kwargs(np_, seed):
+    """DFPNetworkParameters -> the keywords of DFPNet's constructor (behind the shapes)."""
+    head = np_.heads_parameters[0]
+    return dict(embedders={k: (np_.embedder_schemes[k], np_.embedder_activations[k]) for k in DFPNet.INPUTS},
+                head_activation=head.activation_function, learning_rate=np_.learning_rate,
+                adam_beta1=np_.adam_optimizer_beta1, adam_beta2=np_.adam_optimizer_beta2,
+                optimizer_epsilon=np_.optimizer_epsilon, clip_gradients=getattr(np_, "clip_gradients", None), seed=seed)
+
+
+class DFPNet(_NetBase):
+    """DFPNetworkParameters (agents/dfp_agent.py:42-73): three vector input embedders — goal, measurements, observation,
+    each with its own scheme and activation — whose outputs are concatenated in sorted name order
+    (general_network.py:252,277), no middleware (MiddlewareScheme.Empty), and the MeasurementsPredictionHead
+    (heads/measurements_prediction_head.py:39-62): an expectation stream Dense(256, act) -> Dense(K) and an action stream
+    Dense(256, act) -> Dense(A * K), K = num_predicted_steps_ahead * num_measurements, merged as csrc/dfp_merge.hpp
+    states.  No target network.  The merge, the loss and the gradients of the two stream outputs are ONE launch
+    (rlx_dfp_head_loss), acting is the forward pass + rlx_dfp_egreedy / rlx_dfp_argmax; every layer is a generic G.Dense
+    launch (leaky_relu by default, which no fused launch serves).
+
+    The goal is an input like the others: [B, M] rows (the agent repeats its current goal), so its embedder's weight
+    gradients are sums over the rows like any layer's."""
+    INPUTS = ("goal", "measurements", "observation")            # sorted: the order of the concatenation
+
+    def __init__(self, device, obs_dim, n_measurements, n_actions, n_steps, embedders=None, head_activation="leaky_relu",
+                 learning_rate=2.5e-4, adam_beta1=0.95, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None,
+                 seed=0):
+        self.obs_dim, self.M, self.A, self.S = int(obs_dim), int(n_measurements), int(n_actions), int(n_steps)
+        self.K = self.S * self.M
+        self.image = False
+        self.clip_gradients = clip_gradients
+        self.dims = {"goal": self.M, "measurements": self.M, "observation": self.obs_dim}
+        default = {"goal": ([128, 128, 128], "leaky_relu"), "measurements": ([128, 128, 128], "leaky_relu"),
+                   "observation": ("Medium", "leaky_relu")}
+        embedders = dict(default, **(embedders or {}))
+        if sorted(embedders) != list(self.INPUTS):
+            raise ValueError("DFPNet takes the input embedders {}, got {}".format(list(self.INPUTS), sorted(embedders)))
+        self.params = G.FlatParams()
+        self.embedders, self.offsets, feat = {}, {}, 0
+        for name in self.INPUTS:
+            scheme, act = embedders[name]
+            units = VECTOR_EMBEDDER[scheme] if isinstance(scheme, str) else list(scheme)
+            layers, d = [], self.dims[name]
+            for i, u in enumerate(units):
+                layers.append(G.Dense(self.params, "main/%s/embedder/dense%d" % (name, i), d, int(u), act, 1))
+                d = int(u)
+            self.embedders[name] = G.Sequential(layers)
+            self.offsets[name] = (feat, d)
+            feat += d
+        self.feat = feat
+        hn = "main/future_measurements_head"
+        self.e_fc = G.Dense(self.params, hn + "/expectation_stream/fc1", feat, 256, head_activation, 1)
+        self.e_out = G.Dense(self.params, hn + "/expectation_stream/output", 256, self.K, None, 1)
+        self.a_fc = G.Dense(self.params, hn + "/action_stream/fc1", feat, 256, head_activation, 1)
+        self.a_out = G.Dense(self.params, hn + "/action_stream/output", 256, self.A * self.K, None, 1)
+        self.modules = [self.embedders[n] for n in self.INPUTS] + [self.e_fc, self.e_out, self.a_fc, self.a_out]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=device)
+        self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)       # per-row loss partials
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def forward(self, inputs, B, tag="act", weights=None):
+        """inputs: {'goal' [B, M], 'measurements' [B, M], 'observation' [B, D]} fp32 device tensors
+        -> (E Tensor [1, B, K], X Tensor [1, B, A*K], saved)."""
+        ctx = self.ctx
+        merged = ctx.buffer("main/merged", (1, B, self.feat), tag=tag)
+        acts = {}
+        for name in self.INPUTS:
+            x = G.input_tensor(inputs[name], B, self.dims[name])
+            a = self.embedders[name].forward(ctx, x, tag=tag, weights=weights)
+            off, d = self.offsets[name]
+            self.lib.copy_2d(a[-1].data, d, merged.data_ptr() + 4 * off, self.feat, B, d, 1.0, ctx.stream)
+            acts[name] = a
+        m = G.Tensor(merged, B, self.feat, 1, grad_key=(ctx, "main/merged", tag))
+        he = self.e_fc.forward(ctx, m, tag=tag, weights=weights)
+        e = self.e_out.forward(ctx, he, tag=tag, weights=weights)
+        ha = self.a_fc.forward(ctx, m, tag=tag, weights=weights)
+        x = self.a_out.forward(ctx, ha, tag=tag, weights=weights)
+        return e, x, (acts, m, he, ha)
+
+    def can_act_fused(self, n_env):
+        return False
+
+    def streams(self, inputs, B, tag="act"):
+        """the two stream outputs of a forward pass: E [B, K] and X [B, A*K] (what the acting launches read)."""
+        e, x, _ = self.forward(inputs, B, tag=tag)
+        return e.data.view(B, self.K), x.data.view(B, self.A * self.K)
+
+    def backward(self, e, x, saved, B):
+        """e.grad / x.grad hold the gradients of the two stream outputs -> params.grads."""
+        ctx = self.ctx
+        acts, m, he, ha = saved
+        self.e_out.backward(ctx, he, e)
+        self.a_out.backward(ctx, ha, x)
+        # the two streams' input gradients add up in the concatenation's gradient
+        side = G.Tensor(m.data, m.rows, m.cols, 1)
+        side.grad = ctx.buffer("main/merged/side:grad", tuple(m.data.shape), tag="train")
+        self.e_fc.backward(ctx, m, he)
+        self.a_fc.backward(ctx, side, ha)
+        g = m.grad
+        self.lib.axpby(g, 1.0, g, 1.0, side.grad, g.numel(), ctx.stream)
+        for name in self.INPUTS:
+            seq, a = self.embedders[name], acts[name]
+            if not seq.layers:
+                continue
+            off, d = self.offsets[name]
+            out = a[-1]
+            self.lib.copy_2d(g.data_ptr() + 4 * off, self.feat, out.ensure_grad(), d, B, d, 1.0, ctx.stream)
+            out.grad_is_dz = False
+            seq.backward(ctx, a)
+
+    def accumulate(self, inputs, B, actions, future_measurements, y_out=None, targets_out=None):
+        """forward, rlx_dfp_head_loss, backward: the gradients in params.grads, the loss in self.loss.
+        future_measurements: fp32 [B, K], may hold NaN."""
+        e, x, saved = self.forward(inputs, B, tag="train")
+        K, AK = self.K, self.A * self.K
+        self.lib.dfp_head_loss(e.data, K, x.data, AK, actions, future_measurements, self.A, K, B, 1.0, e.ensure_grad(), K,
+                               x.ensure_grad(), AK, self.loss_ws, self.ticket, self.loss, self.status, y_out, targets_out,
+                               self.ctx.stream)
+        self.backward(e, x, saved, B)
+
+    def learn_from_batch(self, inputs, B, actions, future_measurements, grad_scale=1.0, sync=None):
+        """DFPAgent.learn_from_batch (agents/dfp_agent.py:150-167), all on device: ONE forward pass, the loss launch,
+        backward, clip, Adam."""
+        self.accumulate(inputs, B, actions, future_measurements)
+        clipped = self.clip_by_global_norm()
+        if sync is not None:
+            sync.all_reduce_sum(self.params.grads)
+        self.apply_gradients(grad_scale, with_norm=not clipped)
+        return self.loss

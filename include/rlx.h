@@ -418,7 +418,12 @@ int rlx_reward_filter(const float *rewards, float *out, long long n, double resc
                       void *stream);   /* filters/reward/reward_rescale_filter.py:37-39, reward_clipping_filter.py:41-49 */
 
 /* ------------------------------------------- dense / conv layers (fp32 MFMA) -- */
-enum { RLX_ACT_NONE = 0, RLX_ACT_RELU = 1, RLX_ACT_TANH = 2 };
+/* RLX_ACT_LEAKY_RELU: v > 0 ? v : 0.2f * v (tf.nn.leaky_relu's default alpha, tensorflow_components/utils.py:34); its
+ * derivative through the output is y > 0 ? 1 : 0.2f (alpha at 0, as TF's gradient).  Served by the rlx_dense_small_*
+ * launches, rlx_act_backward and rlx_leaky_relu (a wide layer is rlx_gemm without an activation, then rlx_leaky_relu in
+ * place); rlx_gemm's epilogue and every fused launch (conv, noisy dense, batch norm, the row chains and the fused MLP /
+ * PPO updates) refuse an activation above 2 — the hot kernels compile as they did before the activation existed. */
+enum { RLX_ACT_NONE = 0, RLX_ACT_RELU = 1, RLX_ACT_TANH = 2, RLX_ACT_LEAKY_RELU = 3 };
 
 /* C[M,N] (+)= epilogue(A[M,K] * B[K,N]) for `batch` independent problems (strided).
  * A(m,k) = A[off_m + off_k] with off_* = index*stride or a lookup in an int32 table (implicit
@@ -569,6 +574,7 @@ int rlx_gemm_debug_calls(long long *out_host, int max_calls, int *n_calls_host);
 int rlx_colsum(const float *x, int M, int N, long long ld, float *out, int accumulate,
                float *workspace, long long workspace_floats, void *stream);  /* bias gradients */
 int rlx_act_backward(float *dy, const float *y, long long n, int kind, void *stream); /* dy *= act'(y) */
+int rlx_leaky_relu(float *y, long long n, void *stream);             /* y = y > 0 ? y : 0.2f * y, in place */
 int rlx_conv_tables(int *rowbase, int *koff, int batch, int H, int W, int C, int KH, int KW,
                     int stride, void *stream);      /* VALID-padding NHWC im2col offsets */
 int rlx_col2im(const float *dcol, float *dx, const float *x_out, int deriv_kind, int batch, int H,
@@ -987,6 +993,61 @@ int rlx_categorical_egreedy(const float *logits, long long ld, const double *z, 
                             const double *explore_uniforms, const int *random_actions,
                             const double *tie_break_uniforms, double epsilon, int n_env, int n_actions, double *q_out,
                             int *actions, void *stream);
+
+/* ------------------------------------------------------------ Direct Future Prediction (DFP) -- */
+/* The MeasurementsPredictionHead (heads/measurements_prediction_head.py:39-62) works on two Dense outputs: expectation
+ * [rows][K] and action_stream [rows][A*K] (column a*K + k), K = n_steps * n_measurements (step s, measurement m is column
+ * s*M + m).  The merge, fp32, for every column k (csrc/dfp_merge.hpp): s = 0.f, then plus X[a][k] for a = 0 .. A-1 in
+ * this order; mean = s / (float)A; y[a][k] = E[k] + (X[a][k] - mean) — rlx_dueling_combine's order, bit-identical to it
+ * for K = 1.
+ *
+ * rlx_dfp_head_loss: DFPAgent.learn_from_batch (agents/dfp_agent.py:150-167) + the head's loss in ONE launch, one
+ * workgroup per batch row.  future_measurements [batch][K] fp32 may hold NaN.  The targets equal the prediction y
+ * everywhere but in the taken action's row, which is future_measurements with every NaN replaced by the prediction.  On
+ * the taken action's non-NaN entries d = target - y; loss = (sum over b in row order of (sum over k in index order of
+ * d * d)) / (float)batch; g[k] = ((grad_scale * 2.f) * (y - target)) / (float)batch there and 0 elsewhere.
+ * d_expectation[b][k] = g[k]; d_action_stream[b][a][k] = g[k] * ((a == a_b ? 1.f : 0.f) - 1.f / (float)A) (0 where g is
+ * not formed).  row_partials: [batch] floats of workspace; ticket: one zero-initialised word (left at zero); the loss
+ * does not depend on the order in which the workgroups finish.  status |= 1 for an action outside [0, A): that row adds no
+ * term and gets a zero gradient.  y_out and targets_out, [batch][A*K], are optional (null).
+ * 1 <= A <= 18, 1 <= K <= 64, batch <= 256. */
+int rlx_dfp_head_loss(const float *expectation, long long ld_e, const float *action_stream, long long ld_x,
+                      const int *actions, const float *future_measurements, int n_actions, int n_columns, int batch,
+                      float grad_scale, float *d_expectation, long long ld_de, float *d_action_stream, long long ld_dx,
+                      float *row_partials, unsigned int *ticket, float *loss_scalar, int *status, float *y_out,
+                      float *targets_out, void *stream);
+/* The acting step of DFPAgent.choose_action (dfp_agent.py:169-199) for n_env rows: the merge, then the fp64 score of every
+ * action, v[a] = sum_{j = 0 .. W-1} (sum_{m = 0 .. M-1} (double)y[a][(S - W + j)*M + m] * goal[m]) * weights[j] (both sums
+ * from 0.0 in index order: the last W steps), then rlx_categorical_egreedy's choice on the scores (the same code).  goal
+ * [M] and weights [W] are fp64 device arrays, W <= S; the draws as rlx_egreedy takes them; q_out [n_env][A] fp64 is
+ * optional (null).  A <= 18, S * M <= 64. */
+int rlx_dfp_egreedy(const float *expectation, long long ld_e, const float *action_stream, long long ld_x,
+                    const double *goal, const double *weights, int n_steps, int n_measurements, int n_weights,
+                    const double *explore_uniforms, const int *random_actions, const double *tie_break_uniforms,
+                    double epsilon, int n_env, int n_actions, double *q_out, int *actions, void *stream);
+/* The same scores, np.argmax (the first maximum, no draws): ParameterNoise acting (parameter_noise.py:62-68). */
+int rlx_dfp_argmax(const float *expectation, long long ld_e, const float *action_stream, long long ld_x,
+                   const double *goal, const double *weights, int n_steps, int n_measurements, int n_weights, int n_env,
+                   int n_actions, double *q_out, int *actions, void *stream);
+/* DFPAgent._update_measurements_targets (dfp_agent.py:235-255) for ONE completed episode stored time-major (the addressing
+ * of rlx_episode_nstep_returns: row of step k = ((first_step + k) mod ring_steps) * n_env + env).  measurements: the fp64
+ * column [rows][M] of the STATE's measurements; future_measurements: the fp32 column [rows][S*M]; scale: [M] fp64 on the
+ * device.  For transition i and step s, off = i + 2^s: off < length -> out[i][s][m] = (float)(scale[m] * (meas[off][m] -
+ * meas[i][m])), fp64 rounded once; off >= length -> a quiet NaN (last_step_mode 0, HandlingTargetsAfterEpisodeEnd.NAN) or
+ * off = length - 1, the LAST transition's state (last_step_mode 1, LastStep).  One thread per (i, s); S <= 8, M <= 8. */
+int rlx_dfp_future_measurements(const double *measurements, float *future_measurements, const double *scale,
+                                long long first_step, int length, int env, int n_env, long long ring_steps, int n_steps,
+                                int n_measurements, int last_step_mode, void *stream);
+/* use_accumulated_reward_as_measurement (agents/agent.py:920-925 injects the running sum of shaped rewards into the next
+ * state BEFORE :958 adds the step's reward) for n_env envs after one vector step.  accumulated [n_env] fp64: the sum;
+ * measurements [n_env][M] fp64 (and measurements32, its fp32 twin for the network, optional): the CURRENT state's
+ * measurements, whose column `column` is the accumulated reward.  Per env: state_measurements_out[e] (optional, [n_env][M])
+ * = measurements[e] (the state the step was taken in: the replay's column); measurements[e][column] = game_over ? 0 :
+ * accumulated[e]; accumulated[e] = game_over ? 0 : accumulated[e] + rewards[e].  So the state after step t carries the
+ * rewards of steps 1 .. t-1, and the first two states of an episode carry 0.  M <= 8. */
+int rlx_dfp_accumulated_reward_step(const float *rewards, const unsigned char *game_overs, double *accumulated,
+                                    double *measurements, float *measurements32, double *state_measurements_out, int n_env,
+                                    int n_measurements, int column, void *stream);
 
 /* ------------------------------------------------ synthetic vector environment -- */
 /* Device-resident stand-in for Environment.step (environments/environment.py:276-327) on the
