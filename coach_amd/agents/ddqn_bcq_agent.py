@@ -1,0 +1,293 @@
+"""Batch-constrained Double DQN (DDQN-BCQ) — the device half of rl_coach/agents/ddqn_bcq_agent.py: its parameter classes
+(:31-62) and the kNN action mask of DDQNBCQAgent.select_actions (:107-133) with the key sets and average_dist that
+improve_reward_model builds (:187-216).
+
+What is here is the part of the agent with GPU work.  ``KNNActionMask`` holds, per action, the embeddings of the
+dataset's transitions that took that action (the reference's one AnnoyDictionary per action) as ONE device matrix
+grouped by action, and answers ``select_actions`` up to its argmax with two launches: rlx_nn_min_distance (every next
+state against every action's set, exactly — the reference asks an approximate Annoy forest, one query at a time, on the
+host) and rlx_bcq_masked_selector (-inf where the distance exceeds average_dist_coefficient * average_dist, device
+uniforms for a row that keeps no action).  Its output is the ``q_next_selector`` operand of rlx_dqn_head_loss, whose
+first-maximum argmax is the reference's np.argmax.
+
+``DDQNBCQAgent`` is driven by graph_managers/batch_rl_graph_manager.py; the dataset side — freeze, training /
+evaluation split, shuffled epochs — is in memories/episodic/episodic_experience_replay.py.  NNImitationModelParameters
+is a parameter class only: the imitation network it asks for is not served, and the agent refuses it.
+
+Departures from the reference, all stated in DESIGN §8: the search is exact; the zero-confidence rows draw
+counter-based device uniforms (Philox, keyed by seed and rank, at a device event counter) instead of np.random.rand,
+because how many such rows there are is device data; more than knn_size keys for one action is a ValueError where the
+reference's dictionary evicts its least recently used keys.
+"""
+from copy import deepcopy
+
+import numpy as np
+import torch
+
+from .. import _rlx
+from ..base_parameters import Parameters
+from ..core_types import EnvironmentSteps, RunPhase
+from ..exploration_policies.parameter_noise import ParameterNoiseParameters, network_is_noisy
+from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
+from ..nn.networks import DQNNet, dqn_net_kwargs
+from ..schedules import LinearSchedule
+from .dqn_agent import DQNAgent, DQNAgentParameters, DQNAlgorithmParameters
+
+
+class NNImitationModelParameters(Parameters):            # ddqn_bcq_agent.py:31-38 (a parameter class only)
+    def __init__(self):
+        super().__init__()
+        self.imitation_model_num_epochs = 100
+        self.mask_out_actions_threshold = 0.35
+
+
+class KNNParameters(Parameters):                         # ddqn_bcq_agent.py:41-49
+    def __init__(self):
+        super().__init__()
+        self.average_dist_coefficient = 1
+        self.knn_size = 50000
+        self.use_state_embedding_instead_of_state = True  # useful when the state is too big to be used for kNN
+
+
+class DDQNBCQAlgorithmParameters(DQNAlgorithmParameters):     # ddqn_bcq_agent.py:52-62
+    def __init__(self):
+        super().__init__()
+        self.action_drop_method_parameters = KNNParameters()
+        self.num_steps_between_copying_online_weights_to_target = EnvironmentSteps(30000)
+
+
+class KNNActionMask(object):
+    QUERY_CHUNK = 4096            # queries of one rlx_nn_min_distance call while the dataset is measured against itself
+
+    def __init__(self, device, n_actions, parameters=None, seed=0, rank=0):
+        parameters = KNNParameters() if parameters is None else parameters
+        if not isinstance(parameters, KNNParameters):
+            raise ValueError('Unsupported action drop method {} for DDQNBCQAgent (NNImitationModelParameters is not '
+                             'served yet: only the kNN action mask is)'.format(type(parameters)))
+        if not 1 <= int(n_actions) <= 18:
+            raise ValueError("the kNN action mask serves 1 to 18 actions, got %d" % n_actions)
+        self.lib = _rlx.lib()
+        self.device, self.A, self.p = device, int(n_actions), parameters
+        self.seed, self.rank = int(seed) & 0xFFFFFFFF, int(rank) & 0xFFFFFFFF
+        self.keys = self.set_offsets = None
+        self.average_dist = 0
+        self.counts = [0] * self.A
+        self.zero_rows = torch.zeros(1, dtype=torch.int32, device=device)
+
+    # ------------------------------------------------------------------------------------------------ the key sets
+    def build(self, embeddings, actions):
+        """ddqn_bcq_agent.py:187-216.  embeddings: device fp32 [n, W] of every transition of the dataset's complete
+        episodes, in stored order; actions: their actions (device or host integers [n]; copied to the host once).
+        Groups the embeddings by action, keeping the stored order inside a group, and measures average_dist: every
+        transition's distance to every action's set (rlx_nn_min_distance over the whole dataset), summed on the host in
+        the reference's order — tree by tree, transition by transition, in fp64 — and divided by the number of transitions."""
+        if embeddings.dim() != 2 or embeddings.dtype != torch.float32 or not 1 <= embeddings.shape[1] <= 512:
+            raise ValueError("embeddings are fp32 [n, width] with 1 <= width <= 512")
+        actions_host = actions.cpu().numpy() if hasattr(actions, "cpu") else np.asarray(actions)
+        n = embeddings.shape[0]
+        if actions_host.shape != (n,) or n < 1:
+            raise ValueError("one action per embedded transition")
+        if actions_host.min() < 0 or actions_host.max() >= self.A:
+            raise ValueError("an action outside [0, %d)" % self.A)
+        groups = [np.nonzero(actions_host == a)[0] for a in range(self.A)]
+        self.counts = [len(g) for g in groups]
+        for a, c in enumerate(self.counts):
+            if c > self.p.knn_size:
+                raise ValueError("action %d has %d keys, knn_size is %d (the reference's dictionary would evict its least "
+                                 "recently used keys; this one refuses)" % (a, c, self.p.knn_size))
+        order = torch.from_numpy(np.concatenate(groups).astype(np.int64)).to(self.device)
+        self.keys = embeddings.index_select(0, order).contiguous()
+        self.set_offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)).to(self.device)
+        dist = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
+        for i in range(0, n, self.QUERY_CHUNK):
+            m = min(self.QUERY_CHUNK, n - i)
+            self.distances(embeddings[i:i + m], out=dist[i:i + m])
+        host = dist.cpu().numpy()
+        self.average_dist = sum([float(x) for a in range(self.A) for x in host[:, a]]) / n
+        return self.average_dist
+
+    @property
+    def threshold(self):
+        return self.p.average_dist_coefficient * self.average_dist
+
+    # ------------------------------------------------------------------------------------------------ per update
+    def distances(self, embeddings, out=None):
+        """familiarity [n, A] (device fp32): each embedding's distance to its nearest key of every action's set"""
+        if self.keys is None:
+            raise RuntimeError("the key sets are built first (improve_reward_model)")
+        n, W = embeddings.shape
+        if W != self.keys.shape[1] or embeddings.dtype != torch.float32 or embeddings.stride(1) != 1:
+            raise ValueError("embeddings are fp32 [n, %d] rows" % self.keys.shape[1])
+        if out is None:
+            out = torch.empty(n, self.A, dtype=torch.float32, device=self.device)
+        self.lib.nn_min_distance(embeddings.data_ptr(), embeddings.stride(0), n, W, self.keys, W, self.keys.shape[0],
+                                 self.set_offsets, self.A, out.data_ptr(), out.stride(0), _rlx.current_stream())
+        return out
+
+    def selector(self, q_next_online, embeddings_next, event, familiarity=None, out=None):
+        """-> sel [B, A]: the online network's Q values on s' with the unfamiliar actions at -inf (uniforms in a row that
+        keeps none) — rlx_dqn_head_loss's q_next_selector.  event: a device int64 (the update's index): read by the
+        launch, so a captured graph follows it.  self.zero_rows (device int) counts the rows that kept no action."""
+        B, A = q_next_online.shape
+        if A != self.A or q_next_online.dtype != torch.float32 or q_next_online.stride(1) != 1:
+            raise ValueError("q_next_online is fp32 [B, %d] rows" % self.A)
+        fam = self.distances(embeddings_next, out=familiarity)
+        if out is None:
+            out = torch.empty(B, A, dtype=torch.float32, device=self.device)
+        self.lib.bcq_masked_selector(q_next_online.data_ptr(), q_next_online.stride(0), fam.data_ptr(), fam.stride(0),
+                                     float(self.threshold), B, A, self.seed, self.rank, event, out.data_ptr(),
+                                     out.stride(0), self.zero_rows, _rlx.current_stream())
+        return out
+
+
+class DDQNBCQAgentParameters(DQNAgentParameters):        # ddqn_bcq_agent.py:65-74
+    def __init__(self):
+        super().__init__()
+        self.algorithm = DDQNBCQAlgorithmParameters()
+        self.exploration.epsilon_schedule = LinearSchedule(1, 0.01, 1000000)
+        self.exploration.evaluation_epsilon = 0.001
+
+    @property
+    def path(self):
+        return 'coach_amd.agents.ddqn_bcq_agent:DDQNBCQAgent'
+
+
+class DDQNBCQAgent(DQNAgent):
+    """Double DQN on a frozen dataset whose target action is restricted by the kNN action mask (ddqn_bcq_agent.py:79-223).
+    It never steps an environment to learn: train() is one shuffled epoch over the memory's training set.  A second
+    network, `reward_model` (a DQNNet of its own wrapper parameters), is fitted to the rewards first; the embeddings
+    the mask compares are its input embedder's output."""
+    EMBED_CHUNK = 1024
+
+    def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
+        ap = agent_parameters                          # every refusal comes before anything touches the device
+        if not getattr(ap, "is_batch_rl_training", False):
+            raise ValueError('DDQNBCQ agent can only be used in BatchRL')
+        drop = ap.algorithm.action_drop_method_parameters
+        if isinstance(drop, NNImitationModelParameters):
+            raise ValueError('NNImitationModelParameters is not served yet by DDQNBCQAgent: only KNNParameters is')
+        if not isinstance(drop, KNNParameters):
+            raise ValueError('Unsupported action drop method {} for DDQNBCQAgent'.format(type(drop)))
+        if environment.p.kind == "image":
+            raise ValueError("DDQNBCQAgent serves vector observations, not image observations")
+        if not isinstance(ap.memory, EpisodicExperienceReplayParameters):
+            raise ValueError("DDQNBCQAgent learns from a frozen episodic dataset: use EpisodicExperienceReplayParameters, "
+                             "not %s" % type(ap.memory).__name__)
+        if isinstance(ap.exploration, ParameterNoiseParameters) or network_is_noisy(ap.network_wrappers["main"]):
+            raise ValueError("the ParameterNoise exploration policy (noisy dense layers) is not implemented for "
+                             "DDQNBCQAgent")
+        if 'reward_model' not in ap.network_wrappers:
+            ap.network_wrappers['reward_model'] = deepcopy(ap.network_wrappers['main'])
+        super().__init__(ap, environment, device, dist, use_graphs)
+        main, rmp = self.networks["main"], ap.network_wrappers['reward_model']
+        main.l2_regularization = float(getattr(ap.network_wrappers["main"], "l2_regularization", 0) or 0)
+        obs_shape = tuple(environment.p.observation_shape)
+        rm = self.networks["reward_model"] = DQNNet(self.device, obs_shape, self.A, **dqn_net_kwargs(rmp, ap.seed or 0))
+        rm.l2_regularization = float(getattr(rmp, "l2_regularization", 0) or 0)
+        self.mask = KNNActionMask(self.device, self.A, drop, seed=ap.seed or 0,
+                                  rank=self.dist.rank if self.dist is not None else 0)
+        self.training_epoch = 0
+        self.target_copies = 0
+        self._event = torch.zeros(1, dtype=torch.int64, device=self.device)
+        # reporting: updates with a zero-confidence row, and such rows in all (nodes of the update's captured graph)
+        self.zero_row_updates = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.zero_rows_total = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._zero_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._bcq_buffers = {}
+
+    def _step_graph_ok(self):
+        return False
+
+    def _has_td_errors(self):
+        return False
+
+    # ------------------------------------------------------------------------------ reward model and key sets
+    def embedding(self, states, B, tag="embed"):
+        """to_embedding (:87-96): the reward model's input-embedder output, or the raw observation"""
+        if self.ap.algorithm.action_drop_method_parameters.use_state_embedding_instead_of_state:
+            return self.networks["reward_model"].state_embedding(states, B, tag)
+        return states.view(B, -1)
+
+    def _reward_update(self, batch, B, targets):
+        """get_reward_model_loss (value_optimization_agent.py:173-180) + train_and_sync_networks"""
+        rm = self.networks["reward_model"]
+        obs = batch._states["observation"]
+        pred = rm.q_values(obs, B, tag="rm_pred").data.view(B, self.A)
+        self.lib.reward_model_targets(pred, self.A, batch.actions(), batch.rewards(), B, self.A, targets, self.A,
+                                      rm.status, _rlx.current_stream())
+        rm.accumulate_regression(obs, B, targets)
+        rm.apply_gradients(self._grad_scale("reward_model"))
+
+    def improve_reward_model(self, epochs):
+        """:135-216: `epochs` shuffled epochs of the reward model over the training set, then the per-action key sets
+        and average_dist over every transition of the complete episodes"""
+        size = self.ap.network_wrappers['reward_model'].batch_size
+        self.reward_model_losses = []
+        for _ in range(epochs):
+            total = torch.zeros(1, dtype=torch.float32, device=self.device)
+            for batch in self.memory.get_shuffled_training_data_generator(size):
+                B = batch.size
+                targets = self._buffers(B)["targets"]
+                self._run(("reward_model", B), lambda: self._reward_update(batch, B, targets))
+                total += self.networks["reward_model"].loss
+            self.reward_model_losses.append(total)
+        mem = self.memory
+        n = mem.num_transitions_in_complete_episodes()
+        emb, actions = None, torch.empty(n, dtype=torch.int32, device=self.device)
+        for i in range(0, n, self.EMBED_CHUNK):
+            m = min(self.EMBED_CHUNK, n - i)
+            b = mem.gather(mem.physical_rows(np.arange(i, i + m)), m)
+            e = self.embedding(b["state"], m, tag="embed")
+            if emb is None:
+                emb = torch.empty(n, e.shape[1], dtype=torch.float32, device=self.device)
+            emb[i:i + m].copy_(e)
+            actions[i:i + m].copy_(b["action"])
+        return self.mask.build(emb, actions)
+
+    # ------------------------------------------------------------------------------------------- training
+    def _buffers(self, B):
+        b = self._bcq_buffers.get(B)
+        if b is None:
+            f = lambda: torch.empty(B, self.A, dtype=torch.float32, device=self.device)
+            b = self._bcq_buffers[B] = dict(familiarity=f(), selector=f(), targets=f())
+        return b
+
+    def _bcq_update(self, batch, B, bufs):
+        main = self.networks["main"]
+        nxt = batch._next_states["observation"]
+        q_sel = main.q_values(nxt, B, tag="next_o", noise_pass="online_next").data.view(B, self.A)
+        sel = self.mask.selector(q_sel, self.embedding(nxt, B, tag="embed_next"), self._event,
+                                 familiarity=bufs["familiarity"], out=bufs["selector"])
+        torch.clamp(self.mask.zero_rows, max=1, out=self._zero_flag)
+        self.zero_row_updates.add_(self._zero_flag)
+        self.zero_rows_total.add_(self.mask.zero_rows)
+        main.learn_from_batch(batch._states["observation"], nxt, B, batch.actions(), batch.rewards(), batch.game_overs(),
+                              self.ap.algorithm.discount, grad_scale=self._grad_scale(),
+                              sync=self if self.dist is not None else None, states_pair=batch._info.get("states_pair"),
+                              selector=sel)
+
+    def learn_from_batch(self, batch):
+        """DQNAgent.learn_from_batch with select_actions = the masked argmax (:107-133); one captured graph per batch
+        size (an epoch's last batch has its own)"""
+        B = batch.size
+        bufs = self._buffers(B)
+        self._event.fill_(self.training_iteration)               # the zero-confidence rows' draws follow the update's index
+        self._run(("bcq_learn", B), lambda: self._bcq_update(batch, B, bufs))
+        return self._loss_signals()
+
+    def train(self):
+        """Agent.train in batch mode (agent.py:701-765): training_epoch += 1, one pass over the shuffled training set,
+        the target copy checked after every update (TrainingSteps count updates)"""
+        if self.phase != RunPhase.TRAIN:
+            return None
+        self.training_epoch += 1
+        loss = None
+        for batch in self.memory.get_shuffled_training_data_generator(self.batch_size):
+            loss = self.learn_from_batch(batch)
+            self.training_iteration += 1
+            if self.signal_stats is not None:
+                self._accumulate_signals()
+            if self._should_update_online_weights_to_target():
+                self.networks["main"].update_target(self.ap.algorithm.rate_for_copying_weights_to_target)
+                self.target_copies += 1
+        return loss

@@ -354,7 +354,8 @@ class VectorOffPolicyAgent(GraphRunner):
         if isinstance(mp, EpisodicExperienceReplayParameters):
             return EpisodicExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling,
                                             n_step=getattr(mp, "n_step", -1), discount=self.ap.algorithm.discount,
-                                            max_episode_length=self.L, **kw)
+                                            max_episode_length=self.L,
+                                            train_to_eval_ratio=getattr(mp, "train_to_eval_ratio", 1), **kw)
         if getattr(self, "MASK_COLUMN", False):
             kw["mask_column"] = True
         return ExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling, **kw)

@@ -36,6 +36,16 @@ class DuelingQHeadParameters(HeadParameters):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
 
 
+class ClassificationHeadParameters(HeadParameters):
+    """head_parameters.py:194-201 — a parameter class only: presets may name it (Batch RL's imitation model), no device
+    network has this head and an agent that is asked to build one refuses."""
+    head_type = "ClassificationHead"
+
+    def __init__(self, activation_function='relu', name='classification_head_params',
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
 class QuantileRegressionQHeadParameters(HeadParameters):
     """QuantileRegressionQHeadParameters (head_parameters.py:204-212): one Dense layer of A * atoms outputs, read as
     [batch, A, atoms] (heads/quantile_regression_q_head.py:40-81); the atom count is the algorithm's `atoms`."""

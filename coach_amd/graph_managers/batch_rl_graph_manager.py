@@ -1,0 +1,107 @@
+"""Batch RL — host-side mirror of rl_coach/graph_managers/batch_rl_graph_manager.py (constructor :68-94, _create_graph
+:96-154, improve :156-245).
+
+A dataset is collected once — by random heat-up, or by a second, experience-generating agent that runs its own full
+improve() under its own schedule on the same environment —, handed to the trained agent's memory, frozen and split into
+training and evaluation episodes.  The trained agent never plays to learn: after the reward-model epochs
+(improve_reward_model, which also builds DDQN-BCQ's key sets), the loop is "train the scheduled number of EPOCHS, then
+evaluate against the environment".  Time is counted in epochs (TimeTypes.Epoch of the reference): the evaluation rows'
+'Episode #' is the epoch, so a preset's max_episodes_to_achieve_reward bounds epochs.
+
+Out of scope: the off-policy evaluators (IPS, DM, DR, WIS, sequential DR) with softmax_temperature /
+should_get_softmax_probabilities, load_memory_from_file_path, NEC as the trained agent, a checkpoint per epoch.
+"""
+from copy import deepcopy
+
+from ..core_types import EnvironmentSteps, RunPhase
+from .basic_rl_graph_manager import BasicRLGraphManager, dynamic_import
+
+
+class BatchRLGraphManager(BasicRLGraphManager):
+    def __init__(self, agent_params, env_params, schedule_params, vis_params=None, preset_validation_params=None,
+                 name='batch_rl_graph', spaces_definition=None, reward_model_num_epochs=100, train_to_eval_ratio=0.8,
+                 experience_generating_agent_params=None, experience_generating_schedule_params=None, device=None,
+                 dist=None, csv_path=None):
+        """Reference signature (:68-75) + where to run and where to log, as BasicRLGraphManager."""
+        super().__init__(agent_params, env_params, schedule_params, vis_params, preset_validation_params, name,
+                         device=device, dist=dist, csv_path=csv_path)
+        self.is_batch_rl = True
+        self.reward_model_num_epochs = reward_model_num_epochs
+        self.spaces_definition = spaces_definition
+        self.is_collecting_random_dataset = experience_generating_agent_params is None
+        self.experience_generating_agent_params = experience_generating_agent_params
+        self.experience_generating_schedule_params = experience_generating_schedule_params
+        self.experience_generating_agent = None
+        # by default the memory's ratio is 1 (no evaluation set), so it is set here (:84-89)
+        if self.is_collecting_random_dataset:
+            agent_params.memory.train_to_eval_ratio = train_to_eval_ratio
+        else:
+            experience_generating_agent_params.memory.train_to_eval_ratio = train_to_eval_ratio
+        self.epochs = 0
+        self.dataset_training_steps = 0     # updates of the experience-generating agent
+
+    def create_graph(self):                                                     # :96-154
+        from ..agents.dqn_agent import DQNAgentParameters
+        from ..compat import resolve_reference_style
+        from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
+        if self.env_params is None:
+            raise ValueError("a BatchRLGraphManager without an environment needs load_memory_from_file_path, which is "
+                             "not served")
+        if not isinstance(self.agent_params, DQNAgentParameters):
+            raise ValueError("Only DQN variants are supported at this point (NEC as the trained agent is not served)")
+        if not isinstance(self.agent_params.memory, EpisodicExperienceReplayParameters):
+            raise ValueError("Only Episodic memories are supported in Batch RL")
+        rank = self.dist.rank if self.dist is not None else 0
+        ap = self.agent_params
+        ap.is_batch_rl_training = True
+        if 'reward_model' not in ap.network_wrappers:
+            ap.network_wrappers['reward_model'] = deepcopy(ap.network_wrappers['main'])
+        resolve_reference_style(ap, self.env_params)
+        self.environment = dynamic_import(self.env_params.path)(self.env_params, self.device, rank=rank)
+        self.trained_agent = dynamic_import(ap.path)(ap, self.environment, self.device, dist=self.dist,
+                                                     use_graphs=self.use_graphs)
+        if not self.is_collecting_random_dataset:
+            gp = self.experience_generating_agent_params
+            gp.input_filter = getattr(ap, "input_filter", None)                 # :133-134
+            resolve_reference_style(gp, self.env_params)
+            self.experience_generating_agent = dynamic_import(gp.path)(gp, self.environment, self.device, dist=self.dist,
+                                                                       use_graphs=self.use_graphs)
+        self.agent = self.trained_agent
+        return self
+
+    def improve(self, should_stop=None):                                        # :156-245
+        self.verify_graph_was_created()
+        trained = self.trained_agent
+        if self.is_collecting_random_dataset:
+            self.heatup(self.schedule.heatup_steps)
+        else:
+            # the experience-generating agent's full improve() under its own schedule, then its memory changes hands
+            # (its episodes and evaluations are not logged: the reference turns its dump_csv off, :127)
+            from .basic_rl_graph_manager import CsvLogger
+            self.agent, own, log = self.experience_generating_agent, self.schedule, self.logger
+            self.schedule = self.schedule_params = self.experience_generating_schedule_params
+            self.logger = CsvLogger(None)
+            super().improve()
+            self.schedule = self.schedule_params = own
+            self.agent, self.logger = trained, log
+            self.dataset_training_steps, self.training_steps = self.training_steps, 0
+            trained.memory = self.experience_generating_agent.memory
+        trained.ap.algorithm.num_consecutive_playing_steps = EnvironmentSteps(0)      # this agent never actually plays
+        trained.memory.drop_open_episode()
+        trained.memory.freeze()
+        trained.memory.prepare_evaluation_dataset()
+        trained.improve_reward_model(self.reward_model_num_epochs)
+        end = self.epochs + self.schedule.improve_steps.num_steps
+        while self.epochs < end:
+            self._set_phase(RunPhase.TRAIN)
+            for _ in range(self.schedule.steps_between_evaluation_periods.num_steps):
+                before = trained.training_iteration
+                trained.train()
+                self.training_steps += trained.training_iteration - before
+                self.epochs += 1
+            self._episodes_logged = self.epochs                                  # time is counted in epochs
+            self.evaluate(self.schedule.evaluation_steps)
+            if should_stop is not None and should_stop():
+                break
+        self.check_status()
+        return self.logger.rows

@@ -21,6 +21,8 @@ listed.  The ring is sized so that no listed row can be overwritten: capacity + 
 
 With n_env = 1 the table is the identity and every draw selects what the reference selects.
 """
+import math
+import random
 from collections import deque
 
 import numpy as np
@@ -46,7 +48,8 @@ class EpisodicExperienceReplayParameters(ExperienceReplayParameters):        # :
 
 class EpisodicExperienceReplay(ExperienceReplay):
     def __init__(self, max_size, allow_duplicates_in_batch_sampling=True, n_step=-1, discount=0.99,
-                 max_episode_length=None, measurements_dim=None, future_measurements=None, **device_kwargs):
+                 max_episode_length=None, measurements_dim=None, future_measurements=None, train_to_eval_ratio=1,
+                 **device_kwargs):
         """
         :param max_size: (MemoryGranularity.Transitions | Episodes, n)               (reference signature)
         :param n_step: steps summed into n_step_discounted_rewards (-1: to the episode end)   (reference signature)
@@ -58,6 +61,7 @@ class EpisodicExperienceReplay(ExperienceReplay):
                                  transition's future-measurement targets as well, written from the episode's own future
                                  when an env's episode is stored (DFPAgent._update_measurements_targets,
                                  rlx_dfp_future_measurements); last_step: HandlingTargetsAfterEpisodeEnd.LastStep, else NAN
+        :param train_to_eval_ratio: Batch RL: the share of the frozen dataset that is trained on          (reference signature)
         """
         if not isinstance(n_step, int) or (n_step < 1 and n_step != -1):
             raise ValueError("n-step should be an integer with value >= 1, or set to -1 for always setting to "
@@ -94,6 +98,12 @@ class EpisodicExperienceReplay(ExperienceReplay):
             self.future_measurements = torch.zeros(self.rows, self.future_steps * self.M, dtype=torch.float32,
                                                    device=self.device)
         self._order = np.zeros(transitions + 2 * self.Tmax + 1, dtype=np.int64)   # ring of listed rows
+        self.train_to_eval_ratio = train_to_eval_ratio            # used in batch-rl (:69-75)
+        self.last_training_set_episode_id = None
+        self.last_training_set_transition_id = None
+        self.evaluation_dataset_as_episodes = None
+        self.evaluation_dataset_as_transitions = None
+        self.frozen = False
         self.clean()
 
     def _physical_rows(self, cap, n_env):
@@ -140,6 +150,7 @@ class EpisodicExperienceReplay(ExperienceReplay):
         if dones is not None:
             game_overs = dones
         if record:
+            self.assert_not_frozen()
             if self._evaluating:
                 raise RuntimeError("the replay memory is not written during evaluation")
             # BEFORE the write: the ring slot of this step may still hold the oldest listed episode when steps were
@@ -272,3 +283,61 @@ class EpisodicExperienceReplay(ExperienceReplay):
 
     def episode_lengths(self):
         return list(self._episodes)
+
+    # ------------------------------------------------------------------ Batch RL: a frozen dataset (:167-187, :497-546)
+    def freeze(self):
+        """no new transitions from here on: the memory is a dataset (batch-rl)"""
+        self.frozen = True
+
+    def assert_not_frozen(self):
+        assert self.frozen is False, "Memory is frozen, and cannot be changed."
+
+    def get_last_training_set_episode_id(self):
+        return self.last_training_set_episode_id
+
+    def _split_training_and_evaluation_datasets(self):
+        """:532-546.  The transition at round(ratio * transitions) names the last training episode; the training set is
+        every whole episode up to and including it."""
+        if self.last_training_set_transition_id is None:
+            if self.train_to_eval_ratio < 0 or self.train_to_eval_ratio >= 1:
+                raise ValueError('train_to_eval_ratio should be in the (0, 1] range.')
+            index = round(self.train_to_eval_ratio * self.num_transitions_in_complete_episodes())
+            if index >= self.num_transitions_in_complete_episodes():      # self.transitions[index] of the reference
+                raise IndexError('train_to_eval_ratio {} of {} transitions selects transition {}, past the last one'
+                                 .format(self.train_to_eval_ratio, self.num_transitions_in_complete_episodes(), index))
+            seen = 0
+            for episode_num, T in enumerate(self._episodes):
+                seen += T
+                if index < seen:
+                    break
+            self.last_training_set_episode_id = episode_num
+            self.last_training_set_transition_id = seen
+
+    def prepare_evaluation_dataset(self):
+        """:512-530, with the evaluation set held as ranges of logical rows, not as copies: one (first, end) per episode
+        in evaluation_dataset_as_episodes, the whole span in evaluation_dataset_as_transitions."""
+        self._split_training_and_evaluation_datasets()
+        first, episodes = self.last_training_set_transition_id, []
+        for T in list(self._episodes)[self.get_last_training_set_episode_id() + 1:]:
+            episodes.append((first, first + T))
+            first += T
+        self.evaluation_dataset_as_episodes = episodes
+        if len(self.evaluation_dataset_as_episodes) == 0:
+            raise ValueError('train_to_eval_ratio is too high causing the evaluation set to be empty. '
+                             'Consider decreasing its value.')
+        self.evaluation_dataset_as_transitions = (self.last_training_set_transition_id, first)
+
+    def shuffled_training_index_batches(self, size):
+        """the host half of get_shuffled_training_data_generator (:179-184): one random.shuffle of the training set's
+        logical indices, cut into ceil(n / size) batches, the last one smaller"""
+        shuffled_transition_indices = list(range(self.last_training_set_transition_id))
+        random.shuffle(shuffled_transition_indices)
+        return [shuffled_transition_indices[i * size: (i + 1) * size]
+                for i in range(math.ceil(len(shuffled_transition_indices) / size))]
+
+    def get_shuffled_training_data_generator(self, size):
+        """:167-187 -> one DeviceBatch per batch of the shuffled training set (gathered through the listed-rows table by
+        the memory's gather launch; a batch size has its own buffers, so the last, smaller batch has too).  A batch is
+        valid until the next one of its size is drawn."""
+        for part in self.shuffled_training_index_batches(size):
+            yield self.collate(np.asarray(part, dtype=np.int64), len(part))

@@ -474,6 +474,9 @@ class DQNNet(_NetBase):
             self.modules = [self.torso, self.q_head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
         self.loss = torch.zeros(1, dtype=torch.float32, device=device)
+        self.l2_norm = torch.zeros(1, dtype=torch.float32, device=device)
+        mids = FC_MIDDLEWARE[middleware] if isinstance(middleware, str) else middleware
+        self.embedder_layers = len(self.torso.layers) - len(mids)      # state_embedding: the output of the last of them
         self._noisy_setup()
         self._fused = self._fused_mlp_setup()
         self._act = self._act_setup()
@@ -642,6 +645,14 @@ class DQNNet(_NetBase):
             return self._dueling_forward(acts[-1], B, tag, w)[0]
         return self.q_head.forward(self.ctx, acts[-1], tag=tag, weights=w)
 
+    l2_regularization = 0.0      # NetworkParameters.l2_regularization; read by _apply_update (the layer-by-layer update)
+
+    def state_embedding(self, obs, B, tag="embed"):
+        """the input embedder's output on obs, before the middleware (general_network.py's state_embedding[0]):
+        fp32 [B, width] rows, valid until the next pass under the same tag"""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
+        return acts[self.embedder_layers].data.view(B, -1)
+
     def _backward_from_q(self, acts, q, saved, B):
         ctx = self.ctx
         if self.dueling:
@@ -706,6 +717,14 @@ class DQNNet(_NetBase):
 
     def _apply_update(self, grad_scale, sync):
         """the gradients in params.grads -> the weights: clip, share between the workers, Adam."""
+        if self.l2_regularization:
+            # general_network.py:354-358: l2_regularization * sum over every weight of tf.nn.l2_loss (sum w^2 / 2) joins
+            # the loss — its gradient, lambda * w, joins the flat gradient before clip and Adam; the loss signal gets the term
+            lam, p = float(self.l2_regularization), self.params
+            self.lib.axpby(p.grads, 1.0, p.grads, lam, p.weights, p.size, self.ctx.stream)
+            self.lib.global_norm(p.weights, p.size, self.l2_norm, self.ctx.ws.small, self.ctx.ws.small.numel(),
+                                 self.ctx.stream)
+            self.loss.addcmul_(self.l2_norm, self.l2_norm, value=0.5 * lam)
         clipped = self.clip_by_global_norm()          # this worker's gradient, before it is shared
         if sync is not None:                          # data-parallel: ONE all-reduce of the flat buffer
             sync.all_reduce_sum(self.params.grads)
@@ -725,17 +744,26 @@ class DQNNet(_NetBase):
 
     def learn_from_batch(self, obs, next_obs, B, actions, rewards, game_overs, discount,
                          importance_weights=None, td_errors=None, double_dqn=False, grad_scale=1.0,
-                         sync=None, states_pair=None):
-        """DQNAgent.learn_from_batch (agents/dqn_agent.py:81-113), all on device."""
+                         sync=None, states_pair=None, selector=None):
+        """DQNAgent.learn_from_batch (agents/dqn_agent.py:81-113), all on device.
+        selector: fp32 [B, A] (contiguous) whose row argmax picks the action the target network is evaluated at — the
+        caller's own select_actions (DDQN-BCQ's masked online Q values, agents/ddqn_bcq_agent.py).  With it the update
+        goes layer by layer (the one-launch small-MLP update computes its own selection) and double_dqn is not read."""
         ctx = self.ctx
-        if self._fused is not None and sync is None and B <= 32 and obs.is_contiguous() and next_obs.is_contiguous():
+        if selector is None and self._fused is not None and sync is None and B <= 32 and obs.is_contiguous() and \
+                next_obs.is_contiguous():
             w = importance_weights
             if w is not None and w.dtype != torch.float64:
                 w = w.double()
             return self._fused_learn(obs, next_obs, B, actions, rewards, game_overs, discount, w, td_errors,
                                      double_dqn, grad_scale)
-        sel = self.q_values(next_obs, B, tag="next_o", noise_pass="online_next").data.view(B, self.A) \
-            if double_dqn else None
+        if selector is not None:
+            if tuple(selector.shape) != (B, self.A) or selector.dtype != torch.float32 or not selector.is_contiguous():
+                raise ValueError("selector is a contiguous fp32 [%d, %d] tensor" % (B, self.A))
+            sel = selector
+        else:
+            sel = self.q_values(next_obs, B, tag="next_o", noise_pass="online_next").data.view(B, self.A) \
+                if double_dqn else None
 
         def head_loss(acts, q, saved, q_next, dq):
             # TD targets, |TD errors|, QHead loss and its gradient in one launch (importance weights are

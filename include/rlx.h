@@ -1630,6 +1630,45 @@ int rlx_acer_window_loss(const float *q, long long ld_q, const float *logits, lo
                          long long ld_tt, float *dq, long long ld_dq, float *dlogits, long long ld_dlogits,
                          float *scalars, int *status, void *stream);
 
+/* ------------------------------------------------- Batch RL: DDQN-BCQ's action mask -- */
+/* (csrc/bcq.hip; bit-exact numpy twin: tests/bcq_ref.py.  Entry points ADDED under ABI version 11: no existing
+ * signature or structure changed.)
+ *
+ * rlx_nn_min_distance: what AnnoyDictionary._get_k_nearest_neighbors_indices(keys, 1) returns as distances
+ * (memories/non_episodic/differentiable_neural_dictionary.py, as agents/ddqn_bcq_agent.py:109-111 and :212-214 use it),
+ * computed EXACTLY instead of by an approximate forest.  keys is one fp32 matrix [n_keys][ld_k]; rows set_offsets[s] ..
+ * set_offsets[s + 1] - 1 are set s (one set per action; set_offsets: device int32 [n_sets + 1], non-decreasing; the
+ * launch clamps it to [0, n_keys], so a bad table cannot read past the keys).  dist_out[i][s] (fp32 [n_queries][ld_out])
+ * is the Euclidean distance from query i to its nearest key of set s:
+ *   per (query, key) pair acc = 0.f; for w = 0 .. width - 1 in this order t = q[w] - k[w]; acc = acc + t * t (separate
+ *   fp32 roundings, no FMA); the set's value is min over its keys of acc, then one correctly rounded sqrtf.
+ * Identical vectors give exactly 0.0f; an empty set gives +inf.  Input range: every |q[w] - k[w]| below 2^63 / sqrt(width),
+ * so that no difference and no accumulator overflows (network embeddings are far inside it); beyond it a pair's inf - inf is a
+ * NaN, whose bit pattern sorts above +inf in the unsigned minimum and is dropped, where numpy's min would return NaN.  The keys are split over
+ * workgroups in chunks of RLX_NN_KEY_CHUNK and the partial minima meet in an integer atomicMin on the bit pattern of
+ * the non-negative squared distance: deterministic.  Three launches (fill, search, square root), all capturable.
+ * 1 <= width <= 512, 1 <= n_sets <= 18, n_queries >= 1, ld_q, ld_k >= width, ld_out >= n_sets. */
+#define RLX_NN_KEY_CHUNK 128
+int rlx_nn_min_distance(const float *queries, long long ld_q, int n_queries, int width, const float *keys,
+                        long long ld_k, long long n_keys, const int *set_offsets, int n_sets, float *dist_out,
+                        long long ld_out, void *stream);
+/* DDQNBCQAgent.select_actions up to its argmax (agents/ddqn_bcq_agent.py:107-133): sel_out[b][a] = q_next_online[b][a],
+ * or -inf where (double)familiarity[b][a] > threshold (threshold = average_dist_coefficient * average_dist, a double).
+ * A row whose maximum is then -inf (every action masked) gets sel_out[b][a] = u(b, a) instead: uniforms in [0, 1), the
+ * top 24 bits of word 0 of Philox4x32-10 under the key (seed, rank) at the counter (event low word, event high word, b,
+ * a), times 2^-24.  (The reference draws np.random.rand(number of such rows, A) on the host; that number is device
+ * data here.)  event is READ FROM DEVICE MEMORY (one int64), so a captured graph follows it.  zero_rows_out (optional
+ * device int): the number of such rows.  sel_out is the q_next_selector operand of rlx_dqn_head_loss, whose argmax
+ * (first maximum) is the reference's np.argmax.  One workgroup: batch <= 1024, 1 <= n_actions <= 18. */
+int rlx_bcq_masked_selector(const float *q_next_online, long long ld_q, const float *familiarity, long long ld_f,
+                            double threshold, int batch, int n_actions, unsigned int seed, unsigned int rank,
+                            const long long *event, float *sel_out, long long ld_sel, int *zero_rows_out, void *stream);
+/* The reward model's regression targets (agents/value_optimization_agent.py:173-180): targets = prediction with
+ * targets[b][actions[b]] = rewards[b].  targets may be prediction itself (same pointer AND ld_t == ld_p).  status bit 1: an action outside [0, n_actions)
+ * (that row stays the prediction). */
+int rlx_reward_model_targets(const float *prediction, long long ld_p, const int *actions, const float *rewards, int batch,
+                             int n_actions, float *targets, long long ld_t, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
