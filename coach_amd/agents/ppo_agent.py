@@ -22,7 +22,7 @@ import torch
 from .. import _rlx
 from ..architectures.scheme_views import SchemeViews
 from ..core_types import EnvironmentSteps
-from ..nn.networks import PPOActorNet, PPOCriticNet
+from ..nn.networks import PPOActorNet, PPOCriticNet, common_net_kwargs
 from ..schedules import ConstantSchedule
 from .clipped_ppo_agent import ClippedPPOAgent
 from .policy_optimization_agent import PolicyGradientRescaler
@@ -148,11 +148,7 @@ class PPOAgent(ClippedPPOAgent):
 
     def _build_networks(self, obs_shape):
         alg, seed = self.ap.algorithm, self.ap.seed or 0
-
-        def common(net):
-            return dict(activation=net.activation_function, embedder=net.embedder_scheme, middleware=net.middleware_scheme,
-                        learning_rate=net.learning_rate, adam_beta1=net.adam_optimizer_beta1,
-                        adam_beta2=net.adam_optimizer_beta2, optimizer_epsilon=net.optimizer_epsilon, seed=seed)
+        common = lambda net: common_net_kwargs(net, seed)
         critic = PPOCriticNet(self.device, obs_shape, **common(self.ap.network_wrappers["critic"]))
         actor = PPOActorNet(self.device, obs_shape, self.A, beta_entropy=alg.beta_entropy,
                             target_kl_divergence=alg.target_kl_divergence,

@@ -49,8 +49,8 @@ from .. import _rlx
 from ..nn.actor_critic_nets import ActorNet, CriticNet, SACPolicyNet, SACQNet, SACValueNet
 from ..nn.networks import (ACERNet, ActorCriticNet, ClippedPPONet, DFPNet, DQNNet, NStepQNet, PPOActorNet, PPOCriticNet,
                            PolicyGradientNet,
-                           acer_net_kwargs, actor_critic_net_kwargs, dfp_net_kwargs, dqn_net_kwargs, n_step_q_net_kwargs,
-                           policy_gradient_net_kwargs)
+                           acer_net_kwargs, actor_critic_net_kwargs, common_net_kwargs, dfp_net_kwargs, dqn_net_kwargs,
+                           n_step_q_net_kwargs, policy_gradient_net_kwargs)
 from .architecture import Architecture
 
 
@@ -69,6 +69,32 @@ class _HeadFetches(object):
 
 def _adam_args(np_):
     return (np_.learning_rate, np_.adam_optimizer_beta1, np_.adam_optimizer_beta2, np_.optimizer_epsilon)
+
+
+def _obs_shape(spaces):
+    return tuple(int(x) for x in spaces.state['observation'].shape)
+
+
+def _discrete_actions(spaces, refusal):
+    """the number of actions of a discrete action space; any other space is refused with the family's own text"""
+    if not hasattr(spaces.action, "actions"):
+        raise ValueError(refusal)
+    return len(spaces.action.actions)
+
+
+def _fetched(table, additional_fetches):
+    """table: {fetch handle: a function that returns its value} -> the values of additional_fetches, in their order"""
+    if any(f not in table for f in additional_fetches):
+        raise ValueError("unknown fetch in {}".format(additional_fetches))
+    return [table[f]() for f in additional_fetches]
+
+
+def _with_entropy_regulariser(losses, net, mean_entropy):
+    """the heads' losses and, where beta_entropy is set, the regulariser as a loss of its own (policy_head.py:77-79,
+    acer_policy_head.py:56-58)"""
+    if net.beta_entropy:
+        losses.append(float(-np.float32(net.beta_entropy) * mean_entropy))
+    return losses
 
 
 class HipArchitecture(Architecture):
@@ -174,6 +200,22 @@ class HipArchitecture(Architecture):
         if t.numel() != B:
             raise ValueError("{} must hold one value per sample".format(what))
         return t
+
+    def _action_column(self, inputs, key, B):
+        """the discrete policy head's actions, inputs[key], as int32 [B]  (_action is the critics' fp32 [B, A] matrix)"""
+        if key not in inputs:
+            raise ValueError("the policy head needs the input {} (the actions)".format(key))
+        actions = self._to_device(inputs[key], torch.int32).reshape(-1).contiguous()
+        if actions.numel() != B:
+            raise ValueError("{} must hold one action per sample".format(key))
+        return actions
+
+    def _softmax(self, logits, B):
+        """logits [B, A] (a device buffer) -> the action probabilities in a fresh [B, A] tensor"""
+        net = self.net
+        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
+        net.lib.softmax(logits, net.A, B, net.A, probs, net.A, _rlx.current_stream())
+        return probs
 
     # ------------------------------------------------------------------------------ inference
     def predict(self, inputs, outputs=None, squeeze_output=True, initial_feed_dict=None):
@@ -281,8 +323,7 @@ class QArchitecture(HipArchitecture):
     """embedder -> FC middleware -> QHead | DuelingQHead; regression against explicit [B, A] targets."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        return DQNNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
-                      len(spaces.action.actions), **dqn_net_kwargs(np_, seed))
+        return DQNNet(self.device, _obs_shape(spaces), len(spaces.action.actions), **dqn_net_kwargs(np_, seed))
 
     def _queue(self, inputs, tag):
         obs, B = self._observation(inputs)
@@ -314,13 +355,9 @@ class PPOArchitecture(HipArchitecture):
         alg = agent_parameters.algorithm
         continuous = not hasattr(spaces.action, "actions")
         n_act = int(spaces.action.shape[0]) if continuous else len(spaces.action.actions)
-        return ClippedPPONet(
-            self.device, tuple(int(x) for x in spaces.state['observation'].shape), n_act,
-            activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
-            learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
-            adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
-            clip_likelihood_ratio_using_epsilon=alg.clip_likelihood_ratio_using_epsilon,
-            beta_entropy=alg.beta_entropy, seed=seed, continuous=continuous)
+        return ClippedPPONet(self.device, _obs_shape(spaces), n_act,
+                             clip_likelihood_ratio_using_epsilon=alg.clip_likelihood_ratio_using_epsilon,
+                             beta_entropy=alg.beta_entropy, continuous=continuous, **common_net_kwargs(np_, seed))
 
     def _handles(self):
         self.n_dist = 2 if self.net.continuous else 1           # old policy: [probs] or [mean, std]
@@ -369,10 +406,8 @@ class PPOArchitecture(HipArchitecture):
         table = {head.kl_divergence: lambda: sc[2], head.entropy: lambda: sc[1],
                  head.likelihood_ratio: lambda: ratio.cpu().numpy(),
                  head.clipped_likelihood_ratio: lambda: clipped.cpu().numpy()}
-        if any(f not in table for f in additional_fetches):
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
         losses = [float(sc[4]), float(sc[3])]                   # head 0 (V), head 1 (PPO)
-        return float(sc[4] + sc[3]), losses, float(sc[5]), [table[f]() for f in additional_fetches]
+        return float(sc[4] + sc[3]), losses, float(sc[5]), _fetched(table, additional_fetches)
 
 
 # ================================================================================ DDPG / TD3
@@ -579,11 +614,9 @@ class SACQArchitecture(HipArchitecture):
         net.train_backward(saved, target, B)
         net.grad_norm()
         loss = net.loss.cpu().numpy()
-        table = {head.q1_loss: loss[0], head.q2_loss: loss[1]}
-        if any(f not in table for f in additional_fetches):
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        table = {head.q1_loss: lambda: loss[0], head.q2_loss: lambda: loss[1]}
         total = float(loss[:2].sum())
-        return total, [total], float(net.norm.item()), [table[f] for f in additional_fetches]
+        return total, [total], float(net.norm.item()), _fetched(table, additional_fetches)
 
 
 class SACValueArchitecture(HipArchitecture):
@@ -613,12 +646,10 @@ class PolicyGradientArchitecture(HipArchitecture):
     returns (the head's `advantages` placeholder, fp32).  predict -> [action probabilities (B, A)]."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        if not hasattr(spaces.action, "actions"):
-            raise ValueError("the continuous PolicyHead (a Box action space) is not served: the policy-gradient "
-                             "network has the discrete head only")
-        return PolicyGradientNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
-                                 len(spaces.action.actions), **policy_gradient_net_kwargs(np_, agent_parameters.algorithm,
-                                                                                          seed))
+        A = _discrete_actions(spaces, "the continuous PolicyHead (a Box action space) is not served: the policy-gradient "
+                                      "network has the discrete head only")
+        return PolicyGradientNet(self.device, _obs_shape(spaces), A,
+                                 **policy_gradient_net_kwargs(np_, agent_parameters.algorithm, seed))
 
     def _handles(self):
         self.inputs = ['observation', 'output_0_0']
@@ -627,27 +658,18 @@ class PolicyGradientArchitecture(HipArchitecture):
     def _queue(self, inputs, tag):
         obs, B = self._observation(inputs)
         net = self.net
-        z = net.policy_values(obs, B, tag="%s_%d" % (tag, B)).data.view(B, net.A)
-        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
-        net.lib.softmax(z, net.A, B, net.A, probs, net.A, _rlx.current_stream())
-        return [probs]
+        return [self._softmax(net.policy_values(obs, B, tag="%s_%d" % (tag, B)).data.view(B, net.A), B)]
 
     def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
         net = self.net
         obs, B = self._observation(inputs)
-        if 'output_0_0' not in inputs:
-            raise ValueError("the policy head needs the input output_0_0 (the actions)")
-        actions = self._to_device(inputs['output_0_0'], torch.int32).reshape(-1).contiguous()
-        if actions.numel() != B:
-            raise ValueError("output_0_0 must hold one action per sample")
+        actions = self._action_column(inputs, 'output_0_0', B)
         advantages = self._per_sample(targets, B, "targets (the rescaled returns)")
         net.window_gradients(obs, B, actions, advantages)
         sc = net.scalars.cpu().numpy()
         net.check_status()
-        table = {self.output_heads[0].entropy: lambda: sc[1]}
-        if any(f not in table for f in additional_fetches):
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
-        return float(sc[0]), [float(sc[0])], float(net.norm.item()), [table[f]() for f in additional_fetches]
+        fetched = _fetched({self.output_heads[0].entropy: lambda: sc[1]}, additional_fetches)
+        return float(sc[0]), [float(sc[0])], float(net.norm.item()), fetched
 
 
 # ========================================================================== Actor-Critic
@@ -659,11 +681,10 @@ class ActorCriticArchitecture(HipArchitecture):
     accumulate_gradients -> total loss, [value loss, policy loss, the entropy regulariser], the gradients' norm."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        if not hasattr(spaces.action, "actions"):
-            raise ValueError("the continuous PolicyHead (a Box action space) is not served: the actor-critic network has "
-                             "the discrete head only")
-        return ActorCriticNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
-                              len(spaces.action.actions), **actor_critic_net_kwargs(np_, agent_parameters.algorithm, seed))
+        A = _discrete_actions(spaces, "the continuous PolicyHead (a Box action space) is not served: the actor-critic "
+                                      "network has the discrete head only")
+        return ActorCriticNet(self.device, _obs_shape(spaces), A,
+                              **actor_critic_net_kwargs(np_, agent_parameters.algorithm, seed))
 
     def _handles(self):
         self.inputs = ['observation', 'output_1_0']
@@ -673,18 +694,12 @@ class ActorCriticArchitecture(HipArchitecture):
         obs, B = self._observation(inputs)
         net = self.net
         v, z = net.predict(obs, B, tag="%s_%d" % (tag, B))
-        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
-        net.lib.softmax(z, net.A, B, net.A, probs, net.A, _rlx.current_stream())
-        return [v.view(B, 1), probs]
+        return [v.view(B, 1), self._softmax(z, B)]
 
     def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
         net = self.net
         obs, B = self._observation(inputs)
-        if 'output_1_0' not in inputs:
-            raise ValueError("the policy head needs the input output_1_0 (the actions)")
-        actions = self._to_device(inputs['output_1_0'], torch.int32).reshape(-1).contiguous()
-        if actions.numel() != B:
-            raise ValueError("output_1_0 must hold one action per sample")
+        actions = self._action_column(inputs, 'output_1_0', B)
         if not isinstance(targets, (list, tuple)) or len(targets) != 2:
             raise ValueError("targets must be [the V head's targets, the policy head's advantages]")
         value_targets, advantages = (self._to_device(t, torch.float64).reshape(-1).contiguous() for t in targets)
@@ -693,13 +708,9 @@ class ActorCriticArchitecture(HipArchitecture):
         net.window_gradients(obs, B, False, actions, value_targets, advantages)
         sc = net.scalars.cpu().numpy()
         net.check_status()
-        table = {self.output_heads[1].entropy: lambda: sc[3]}
-        if any(f not in table for f in additional_fetches):
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
-        losses = [float(sc[1]), float(sc[2])]
-        if net.beta_entropy:                             # the regulariser is a loss of its own (policy_head.py:77-79)
-            losses.append(float(-np.float32(net.beta_entropy) * sc[3]))
-        return float(sc[0]), losses, float(net.norm.item()), [table[f]() for f in additional_fetches]
+        fetched = _fetched({self.output_heads[1].entropy: lambda: sc[3]}, additional_fetches)
+        losses = _with_entropy_regulariser([float(sc[1]), float(sc[2])], net, sc[3])
+        return float(sc[0]), losses, float(net.norm.item()), fetched
 
 
 # =============================================================================== N-step Q
@@ -711,10 +722,8 @@ class NStepQArchitecture(HipArchitecture):
     view; accumulate_gradients -> total loss, [the Q head's loss], the gradients' norm."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        if not hasattr(spaces.action, "actions"):
-            raise ValueError("a Box action space is not served: the N-step Q network has the discrete QHead only")
-        return NStepQNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
-                         len(spaces.action.actions), **n_step_q_net_kwargs(np_, seed))
+        A = _discrete_actions(spaces, "a Box action space is not served: the N-step Q network has the discrete QHead only")
+        return NStepQNet(self.device, _obs_shape(spaces), A, **n_step_q_net_kwargs(np_, seed))
 
     def _queue(self, inputs, tag):
         obs, B = self._observation(inputs)
@@ -731,8 +740,7 @@ class NStepQArchitecture(HipArchitecture):
             raise ValueError("targets shape {} does not match the head output {}".format(tuple(target.shape), (B, net.A)))
         if importance_weights is not None:
             raise ValueError("the N-step Q head takes no importance weights")
-        if additional_fetches:
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        _fetched({}, additional_fetches)                 # (the head offers none)
         net.window_gradients(obs, B, None, None, target_matrix=target)
         total_loss = float(net.loss.item())
         return total_loss, [total_loss], float(net.norm.item()), []
@@ -750,10 +758,8 @@ class ACERArchitecture(HipArchitecture):
     kl_divergence of head 1."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        if not hasattr(spaces.action, "actions"):
-            raise ValueError("only discrete action spaces are supported for ACER")
-        return ACERNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
-                       len(spaces.action.actions), **acer_net_kwargs(np_, agent_parameters.algorithm, seed))
+        A = _discrete_actions(spaces, "only discrete action spaces are supported for ACER")
+        return ACERNet(self.device, _obs_shape(spaces), A, **acer_net_kwargs(np_, agent_parameters.algorithm, seed))
 
     def _handles(self):
         self.inputs = ['observation'] + ['output_1_%d' % i for i in range(6)]
@@ -762,16 +768,9 @@ class ACERArchitecture(HipArchitecture):
 
     def _queue(self, inputs, tag):
         obs, B = self._observation(inputs)
-        net, tag = self.net, "%s_%d" % (tag, B)
-        probs = torch.empty(B, net.A, dtype=torch.float32, device=self.device)
-        if self.is_target:
-            acts = net.torso.forward(net.ctx, net.obs_tensor(obs, B), tag=tag + "_t", weights=net.target)
-            q = net.q_head.forward(net.ctx, acts[-1], tag=tag + "_t", weights=net.target).data.view(B, net.A)
-            z = net.pi_head.forward(net.ctx, acts[-1], tag=tag + "_t", weights=net.target).data.view(B, net.A)
-        else:
-            q, z = net.predict(obs, B, tag=tag)
-        net.lib.softmax(z, net.A, B, net.A, probs, net.A, _rlx.current_stream())
-        return [q, probs]
+        tag = "%s_%d%s" % (tag, B, "_t" if self.is_target else "")
+        q, z = self.net.predict(obs, B, tag=tag, use_target=self.is_target)
+        return [q, self._softmax(z, B)]
 
     def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
         net = self.net
@@ -782,9 +781,7 @@ class ACERArchitecture(HipArchitecture):
         if not isinstance(targets, (list, tuple)) or len(targets) != 2:
             raise ValueError("targets must be [the Q head's target matrix, the state values]")
         f32 = lambda v, shape: self._to_device(v, torch.float32).reshape(shape).contiguous()
-        actions = self._to_device(inputs['output_1_0'], torch.int32).reshape(-1).contiguous()
-        if actions.numel() != B:
-            raise ValueError("output_1_0 must hold one action per sample")
+        actions = self._action_column(inputs, 'output_1_0', B)
         A = net.A
         try:
             given = dict(rho=f32(inputs['output_1_1'], (B, A)), rho_i=f32(inputs['output_1_2'], (B,)),
@@ -802,21 +799,12 @@ class ACERArchitecture(HipArchitecture):
         head = self.output_heads[1]
         table = {head.probability_loss: lambda: sc[3], head.bias_correction_loss: lambda: sc[4],
                  head.kl_divergence: lambda: sc[5]}
-        if any(f not in table for f in additional_fetches):
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
-        losses = [float(sc[1]), float(sc[2])]
-        if net.beta_entropy:                             # the regulariser is a loss of its own (acer_policy_head.py:56-58)
-            losses.append(float(-np.float32(net.beta_entropy) * sc[6]))
-        return float(sc[0]), losses, float(net.norm.item()), [table[f]() for f in additional_fetches]
+        fetched = _fetched(table, additional_fetches)
+        losses = _with_entropy_regulariser([float(sc[1]), float(sc[2])], net, sc[6])
+        return float(sc[0]), losses, float(net.norm.item()), fetched
 
 
 # ================================================================================ PPO (KL penalty)
-def _ppo_net_common(np_, seed):
-    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
-                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1, adam_beta2=np_.adam_optimizer_beta2,
-                optimizer_epsilon=np_.optimizer_epsilon, seed=seed)
-
-
 class PPOActorArchitecture(HipArchitecture):
     """embedder -> FC middleware -> PPOHead without a clip range and with the KL penalty, fed the way
     PPOAgent.train_policy_network feeds it (ppo_agent.py:278-288): inputs 'observation', 'output_0_0' = actions,
@@ -830,12 +818,12 @@ class PPOActorArchitecture(HipArchitecture):
             raise ValueError("clip_likelihood_ratio_using_epsilon is not None: that is the Clipped PPO network")
         continuous = not hasattr(spaces.action, "actions")
         n_act = int(spaces.action.shape[0]) if continuous else len(spaces.action.actions)
-        return PPOActorNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape), n_act,
+        return PPOActorNet(self.device, _obs_shape(spaces), n_act,
                            beta_entropy=alg.beta_entropy, target_kl_divergence=alg.target_kl_divergence,
                            initial_kl_coefficient=alg.initial_kl_coefficient,
                            high_kl_penalty_coefficient=alg.high_kl_penalty_coefficient,
                            use_kl_regularization=alg.use_kl_regularization, continuous=continuous,
-                           **_ppo_net_common(np_, seed))
+                           **common_net_kwargs(np_, seed))
 
     def _handles(self):
         self.n_dist = 2 if self.net.continuous else 1
@@ -871,9 +859,7 @@ class PPOActorArchitecture(HipArchitecture):
         head = self.output_heads[0]
         table = {head.kl_divergence: lambda: sc[2], head.entropy: lambda: sc[1],
                  head.likelihood_ratio: lambda: ratio.cpu().numpy()}
-        if any(f not in table for f in additional_fetches):
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
-        return float(sc[3]), [float(sc[0])], float(net.norm.item()), [table[f]() for f in additional_fetches]
+        return float(sc[3]), [float(sc[0])], float(net.norm.item()), _fetched(table, additional_fetches)
 
     def get_variable_value(self, variable):
         if variable == self.output_heads[0].kl_coefficient:
@@ -892,8 +878,7 @@ class PPOCriticArchitecture(HipArchitecture):
     (ppo_agent.py:227-233): inputs 'observation', targets = the returns (B, 1).  predict -> V (B, 1)."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        return PPOCriticNet(self.device, tuple(int(x) for x in spaces.state['observation'].shape),
-                            **_ppo_net_common(np_, seed))
+        return PPOCriticNet(self.device, _obs_shape(spaces), **common_net_kwargs(np_, seed))
 
     def _handles(self):
         self.inputs = ['observation']
@@ -906,8 +891,7 @@ class PPOCriticArchitecture(HipArchitecture):
     def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
         net = self.net
         obs, B = self._observation(inputs)
-        if additional_fetches:
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        _fetched({}, additional_fetches)                 # (the head offers none)
         net.forward_backward(obs, B, self._per_sample(targets, B, "targets (the returns)"))
         net.grad_norm()
         loss = float(net.loss.item())
@@ -926,12 +910,12 @@ class DFPArchitecture(HipArchitecture):
     head's loss], the gradients' norm."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
-        if not hasattr(spaces.action, "actions"):
-            raise ValueError("a Box action space is not served: the DFP network predicts measurements per discrete action")
+        A = _discrete_actions(spaces, "a Box action space is not served: the DFP network predicts measurements per discrete "
+                                      "action")
         if len(spaces.state['observation'].shape) != 1:
             raise ValueError("image observations are not served: the DFP network has vector embedders only")
         return DFPNet(self.device, int(spaces.state['observation'].shape[0]), int(spaces.state['measurements'].shape[0]),
-                      len(spaces.action.actions), int(agent_parameters.algorithm.num_predicted_steps_ahead),
+                      A, int(agent_parameters.algorithm.num_predicted_steps_ahead),
                       **dfp_net_kwargs(np_, seed))
 
     def _handles(self):
@@ -977,8 +961,7 @@ class DFPArchitecture(HipArchitecture):
         ins, B = self._inputs(inputs)
         if importance_weights is not None:
             raise ValueError("the measurements prediction head takes no importance weights")
-        if additional_fetches:
-            raise ValueError("unknown fetch in {}".format(additional_fetches))
+        _fetched({}, additional_fetches)                 # (the head offers none)
         target = targets[0] if isinstance(targets, (list, tuple)) else targets
         target = self._to_device(target, torch.float32).contiguous()
         if tuple(target.shape) != (B, net.A, net.K):

@@ -69,6 +69,58 @@ class _NetBase:
             return G.input_tensor(obs, B, int(np.prod(self.obs_shape)), u8=True, div=255.0)
         return G.input_tensor(obs, B, int(self.obs_shape[0]))
 
+    # ---- the single-tower networks: one embedder + FC middleware trunk under one or more Dense heads -------------
+    def _build_trunk(self, obs_shape, activation, embedder, middleware):
+        """the constructor's prologue: the observation's shape, the flat parameters and the one-tower torso -> the width
+        of the torso's output, which the heads read"""
+        self.obs_shape, self.image = tuple(obs_shape), len(obs_shape) == 3
+        self.params = G.FlatParams()
+        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        return feat
+
+    def trunk_forward(self, obs, B, tag, weights=None):
+        """the torso on obs -> its activations; the heads read the last one"""
+        return self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=weights)
+
+    def _fork(self, feat, heads, tag):
+        """a training pass's [(head layer, the Tensor it reads)]: the first head reads feat, every other head a Tensor
+        on the same data whose gradient is a buffer of its own (_heads_backward adds them onto feat.grad)"""
+        feat.ensure_grad()
+        pairs = [(heads[0], feat)]
+        for l in heads[1:]:
+            side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
+            side.grad = self.ctx.buffer(l.name + "/input:grad", tuple(feat.data.shape), tag=tag)
+            pairs.append((l, side))
+        return pairs
+
+    def _heads_forward(self, pairs, tag, weights=None):
+        """[(head layer, input Tensor)] -> [output Tensor]: the layers the narrow-dense kernels serve in ONE launch
+        (where there is more than one), the others as launches of their own"""
+        narrow = [p for p in pairs if p[0].N <= G.SMALL_N]
+        out = {}
+        if len(narrow) > 1:
+            ys = G.small_dense_forward_multi(self.ctx, narrow, tag=tag, weights=weights)
+            out = {l: y for (l, _), y in zip(narrow, ys)}
+        return [out[l] if l in out else l.forward(self.ctx, x, tag=tag, weights=weights) for l, x in pairs]
+
+    def _heads_backward(self, feat, pairs, outs):
+        """the heads' backward pass behind _fork and _heads_forward (every output's .grad is set): the narrow layers in
+        ONE launch where it takes their rows, the others as launches of their own; then the side gradients are added
+        onto feat.grad in head order"""
+        items = [(l, x, y) for (l, x), y in zip(pairs, outs)]
+        narrow = [it for it in items if it[0].N <= G.SMALL_N and feat.rows * it[0].N <= 1024]
+        together = set()
+        if len(narrow) > 1:
+            G.small_dense_backward_multi(self.ctx, narrow)
+            together = {l for l, _, _ in narrow}
+        for l, x, y in items:
+            if l not in together:
+                l.backward(self.ctx, x, y)
+        g = feat.grad
+        for _, x in pairs[1:]:
+            self.lib.axpby(g, 1.0, g, 1.0, x.grad, g.numel(), self.ctx.stream)
+        feat.grad_is_dz = all(x.grad_is_dz for _, x in pairs)
+
     def update_target(self, rate=1.0):
         """NetworkWrapper.update_target_network (network_wrapper.py:109-116): w_t <- rate*w_o + (1-rate)*w_t."""
         self.lib.mix_weights(self.target, self.params.weights, self.params.size, float(rate), self.ctx.stream)
@@ -417,14 +469,27 @@ class ClippedPPONet(_NetBase):
         return self.scalars
 
 
+def common_net_kwargs(np_, seed):
+    """a network parameters object -> the constructor keywords every network here takes: the torso's schemes and
+    activation, Adam's constants and the seed"""
+    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
+                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1, adam_beta2=np_.adam_optimizer_beta2,
+                optimizer_epsilon=np_.optimizer_epsilon, seed=seed)
+
+
+def discrete_policy_actions(n_actions):
+    """the action count of a network under the discrete policy head, checked against what its loss launches serve"""
+    A = int(n_actions)
+    if not 1 <= A <= 18:
+        raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % A)
+    return A
+
+
 def dqn_net_kwargs(np_, seed):
     """a DQN-family network's parameters object (DQNNetworkParameters and its subclasses) -> the keywords of DQNNet's
     constructor; `noisy` and a subclass's own arguments (atoms, heads) are the caller's."""
     head = np_.heads_parameters[0]
-    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
-                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
-                adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
-                replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss, seed=seed,
+    return dict(common_net_kwargs(np_, seed), replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss,
                 dueling=isinstance(head, DuelingQHeadParameters), head_activation=head.activation_function,
                 head_gradient_rescale=head.rescale_gradient_from_head_by_factor,
                 clip_gradients=getattr(np_, "clip_gradients", None))
@@ -990,11 +1055,10 @@ class NAFNet(_NetBase):
         A = int(action_dim)
         if not 1 <= A <= self.MAX_ACTIONS:
             raise ValueError("1 <= action dimension <= %d (rlx_naf_head_loss), got %d" % (self.MAX_ACTIONS, A))
-        self.obs_shape, self.image, self.A, self.NL = tuple(obs_shape), False, A, A * (A + 1) // 2
+        self.A, self.NL = A, A * (A + 1) // 2
         self.huber = bool(replace_mse_with_huber_loss)
         self.clip_gradients, self.clip_value = clip_gradients, bool(clip_by_value)
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         self.v_layer = G.Dense(self.params, self.HEAD + "/V", feat, 1, None, 1)
         self.mu_layer = G.Dense(self.params, self.HEAD + "/mu_unscaled", feat, A, head_activation, 1)
         self.l_layer = G.Dense(self.params, self.HEAD + "/l_vector", feat, self.NL, None, 1)
@@ -1008,25 +1072,10 @@ class NAFNet(_NetBase):
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
     # ---------------------------------------------------------------------------------- forward
-    def _heads_forward(self, feat, layers, tag, weights=None, inputs=None):
-        """the given head layers on the middleware's output -> {layer: output Tensor}; the narrow ones in one launch.
-        inputs: {layer: the Tensor it reads} (the training pass gives every layer its own gradient buffer)."""
-        ctx = self.ctx
-        x = lambda l: inputs[l] if inputs else feat
-        narrow = [l for l in layers if l.N <= G.SMALL_N]
-        out = {}
-        if len(narrow) > 1:
-            out.update(zip(narrow, G.small_dense_forward_multi(ctx, [(l, x(l)) for l in narrow], tag=tag,
-                                                                weights=weights)))
-        for l in layers:
-            if l not in out:
-                out[l] = l.forward(ctx, x(l), tag=tag, weights=weights)
-        return out
-
     def state_values(self, obs, B, use_target=False, tag="v"):
         """V(s) [B] (a view of the V layer's output)."""
         w = self.target if use_target else None
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        acts = self.trunk_forward(obs, B, tag, w)
         return self.v_layer.forward(self.ctx, acts[-1], tag=tag, weights=w).data.view(B)
 
     def head_forward(self, obs, B, actions=None, use_target=False, tag="act", mu_out=None, with_signals=False):
@@ -1034,9 +1083,8 @@ class NAFNet(_NetBase):
         (None: at u = mu, where Advantage = 0 and Q = V) — naf_agent.py:101-131."""
         ctx, A = self.ctx, self.A
         w = self.target if use_target else None
-        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
-        o = self._heads_forward(acts[-1], self.heads, tag, w)
-        v, m, l = (o[k].data for k in self.heads)
+        acts = self.trunk_forward(obs, B, tag, w)
+        v, m, l = (y.data for y in self._heads_forward([(k, acts[-1]) for k in self.heads], tag, w))
         mu = mu_out if mu_out is not None else ctx.buffer("naf/mu", (B, A), tag=tag)
         res = dict(mu=mu, V=v.view(B))
         q = adv = L = None
@@ -1075,31 +1123,14 @@ class NAFNet(_NetBase):
             raise ValueError("1 <= batch <= %d (rlx_naf_head_loss), got %d" % (self.MAX_BATCH, B))
         ctx, A, NL = self.ctx, self.A, self.NL
         v_next = self.state_values(next_obs, B, use_target=True, tag="next_t")
-        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
-        feat = acts[-1]
-        feat.ensure_grad()
-        # every head layer writes its input gradient into a buffer of its own; they are added into feat.grad below
-        ins = {self.v_layer: feat}
-        for l in self.heads[1:]:
-            side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
-            side.grad = ctx.buffer(l.name + "/input:grad", tuple(feat.data.shape), tag="train")
-            ins[l] = side
-        o = self._heads_forward(feat, self.heads, "train", inputs=ins)
-        v, m, l = (o[k] for k in self.heads)
+        acts = self.trunk_forward(obs, B, "train")
+        fork = self._fork(acts[-1], self.heads, "train")
+        v, m, l = outs = self._heads_forward(fork, "train")
         self.lib.naf_head_loss(v.data, 1, m.data, A, l.data, NL, self.scale, actions, A, v_next, 1, rewards, game_overs,
                                float(discount), B, A, int(self.huber), 1.0, v.ensure_grad(), 1, m.ensure_grad(), A,
                                l.ensure_grad(), NL, self.partials, self.ticket, self.loss, td_targets_out, q_out,
                                adv_out, ctx.stream)
-        narrow = [k for k in self.heads if k.N <= G.SMALL_N and B * k.N <= 1024]
-        if len(narrow) > 1:
-            G.small_dense_backward_multi(ctx, [(k, ins[k], o[k]) for k in narrow])
-        for k in self.heads:
-            if len(narrow) <= 1 or k not in narrow:
-                k.backward(ctx, ins[k], o[k])
-        g = feat.grad
-        for k in self.heads[1:]:
-            self.lib.axpby(g, 1.0, g, 1.0, ins[k].grad, g.numel(), ctx.stream)
-        feat.grad_is_dz = all(ins[k].grad_is_dz for k in self.heads)
+        self._heads_backward(acts[-1], fork, outs)
         self.torso.backward(ctx, acts)
         self._apply_update(grad_scale, sync, mix_rate)
         return self.loss
@@ -1107,11 +1138,8 @@ class NAFNet(_NetBase):
 
 def policy_gradient_net_kwargs(np_, alg, seed):
     """PolicyGradientNetworkParameters + the algorithm's beta_entropy -> the keywords of PolicyGradientNet's constructor"""
-    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
-                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
-                adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
-                clip_gradients=getattr(np_, "clip_gradients", None), beta_entropy=getattr(alg, "beta_entropy", 0) or 0,
-                seed=seed)
+    return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),
+                beta_entropy=getattr(alg, "beta_entropy", 0) or 0)
 
 
 class _WindowAccumulatingNet(_NetBase):
@@ -1119,10 +1147,22 @@ class _WindowAccumulatingNet(_NetBase):
     subclass gives `window_gradients(...)`, which leaves one update window's gradients in params.grads and returns the
     loss; an update window's gradient is ADDED onto `accumulated`, which one Adam step consumes and clears."""
 
-    def _finish_accumulating(self, n_scalars):
-        self.scalars = torch.zeros(n_scalars, dtype=torch.float32, device=self.device)
+    def _finish_accumulating(self, scalar_names):
+        """`scalars`, the record the window's loss launch writes, with a one-element view of every entry under its name
+        (the first is `loss`), and the accumulation buffer"""
+        self.scalars = torch.zeros(len(scalar_names), dtype=torch.float32, device=self.device)
+        for i, name in enumerate(scalar_names):
+            setattr(self, name, self.scalars[i:i + 1])
         self.accumulated = torch.zeros_like(self.params.grads)
         self._stage = {}
+
+    def _finish_window(self, acts):
+        """the tail of window_gradients behind the heads' backward pass: the torso backward, then the gradients clipped
+        by their global norm or the norm alone (self.norm either way) -> the window's loss"""
+        self.torso.backward(self.ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss
 
     def stage_rows(self, obs, last_next_obs):
         """a window's n states and a state that does not follow them in memory (the observation before the reset behind
@@ -1158,23 +1198,18 @@ class PolicyGradientNet(_WindowAccumulatingNet):
     def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
                  learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None,
                  beta_entropy=0.0, seed=0):
-        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
-        if not 1 <= self.A <= 18:
-            raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % self.A)
+        self.A = discrete_policy_actions(n_actions)
         self.clip_gradients = clip_gradients
         self.beta_entropy = float(beta_entropy)
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         self.head = G.Dense(self.params, "main/policy_values_head/fc", feat, self.A, None, 1)
         self.modules = [self.torso, self.head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
-        self._finish_accumulating(2)                                 # loss, mean entropy of the last window
-        self.loss, self.entropy = self.scalars[0:1], self.scalars[1:2]
+        self._finish_accumulating(("loss", "entropy"))               # (the mean entropy) of the last window
 
     def policy_values(self, obs, B, tag="act"):
         """the head's Dense output [B, A] (a Tensor; .data is the buffer): logits of the action probabilities"""
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
-        return self.head.forward(self.ctx, acts[-1], tag=tag)
+        return self.head.forward(self.ctx, self.trunk_forward(obs, B, tag)[-1], tag=tag)
 
     def window_gradients(self, obs, T, actions, advantages):
         """forward on the T states of one update window, the head loss against (actions, advantages), backward: the
@@ -1182,15 +1217,12 @@ class PolicyGradientNet(_WindowAccumulatingNet):
         tf.global_norm of the raw gradients in self.norm.  The context's buffers are keyed by shape, so every window
         length has its own activations and the means divide by the window's true length."""
         ctx = self.ctx
-        acts = self.torso.forward(ctx, self.obs_tensor(obs, T), tag="train")
+        acts = self.trunk_forward(obs, T, "train")
         z = self.head.forward(ctx, acts[-1], tag="train")
         self.lib.pg_head_loss(z.data, self.A, actions, advantages, self.beta_entropy, T, T, self.A, z.ensure_grad(),
                               self.A, self.scalars, self.status, ctx.stream)
         self.head.backward(ctx, acts[-1], z)
-        self.torso.backward(ctx, acts)
-        if not self.clip_by_global_norm():
-            self.grad_norm()
-        return self.loss
+        return self._finish_window(acts)
 
 
 def actor_critic_net_kwargs(np_, alg, seed):
@@ -1210,38 +1242,27 @@ class ActorCriticNet(_WindowAccumulatingNet):
     def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
                  learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=40.0,
                  beta_entropy=0.0, v_loss_weight=0.5, seed=0):
-        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
-        if not 1 <= self.A <= 18:
-            raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % self.A)
+        self.A = discrete_policy_actions(n_actions)
         self.clip_gradients = clip_gradients
         self.beta_entropy, self.v_loss_weight = float(beta_entropy), float(v_loss_weight)
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         self.v_head = G.Dense(self.params, "main/v_values_head/output", feat, 1, None, 1, init=G.normalized_columns(1.0))
         self.pi_head = G.Dense(self.params, "main/policy_values_head/fc", feat, self.A, None, 1)
         self.heads = [self.v_head, self.pi_head]
         self.modules = [self.torso] + self.heads
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
-        self._finish_accumulating(4)                 # total loss, value loss, policy loss, mean entropy of the last window
-        sc = self.scalars
-        self.loss, self.value_loss, self.policy_loss, self.entropy = sc[0:1], sc[1:2], sc[2:3], sc[3:4]
+        # total loss, value loss, policy loss, mean entropy of the last window
+        self._finish_accumulating(("loss", "value_loss", "policy_loss", "entropy"))
 
     def policy_values(self, obs, B, tag="act"):
         """the policy head's Dense output [B, A] (logits of the action probabilities); the V head is not run"""
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
-        return self.pi_head.forward(self.ctx, acts[-1], tag=tag)
+        return self.pi_head.forward(self.ctx, self.trunk_forward(obs, B, tag)[-1], tag=tag)
 
     def predict(self, obs, B, tag="predict"):
         """both heads -> (V [B], logits [B, A]) as buffers"""
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
-        v, z = self._heads_forward(acts[-1], acts[-1], tag)
+        feat = self.trunk_forward(obs, B, tag)[-1]
+        v, z = self._heads_forward([(l, feat) for l in self.heads], tag)
         return v.data.view(B), z.data.view(B, self.A)
-
-    def _heads_forward(self, x_v, x_pi, tag):
-        """both heads in one launch where the narrow-dense kernels serve the policy head's width"""
-        if self.A <= G.SMALL_N:
-            return G.small_dense_forward_multi(self.ctx, [(self.v_head, x_v), (self.pi_head, x_pi)], tag=tag)
-        return self.v_head.forward(self.ctx, x_v, tag=tag), self.pi_head.forward(self.ctx, x_pi, tag=tag)
 
     def window_gradients(self, obs_rows, T, bootstrap, actions, targets, advantages, rewards=None, game_over=None,
                          discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False):
@@ -1253,38 +1274,22 @@ class ActorCriticNet(_WindowAccumulatingNet):
         gradients in self.norm.  The context's buffers are keyed by shape; the means divide by T."""
         ctx, A = self.ctx, self.A
         rows = T + int(bool(bootstrap))
-        acts = self.torso.forward(ctx, self.obs_tensor(obs_rows, rows), tag="train")
-        feat = acts[-1]
-        feat.ensure_grad()
-        # each head writes its input gradient into a buffer of its own; they are added into feat.grad below
-        side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
-        side.grad = ctx.buffer(self.pi_head.name + "/input:grad", tuple(feat.data.shape), tag="train")
-        v, z = self._heads_forward(feat, side, "train")
+        acts = self.trunk_forward(obs_rows, rows, "train")
+        fork = self._fork(acts[-1], self.heads, "train")
+        v, z = outs = self._heads_forward(fork, "train")
         self.values = v.data.view(rows)                  # the 'Values' samples are its first T entries
         self.lib.a3c_window_loss(v.data, 1, z.data, A, actions, rewards, game_over, T, rows, A, float(discount),
                                  float(gae_lambda), int(rescaler), int(bool(estimate_with_gae)), self.beta_entropy,
                                  self.v_loss_weight, targets, advantages, v.ensure_grad(), 1, z.ensure_grad(), A,
                                  self.scalars, self.status, ctx.stream)
-        if A <= G.SMALL_N and rows * A <= 1024:
-            G.small_dense_backward_multi(ctx, [(self.v_head, feat, v), (self.pi_head, side, z)])
-        else:
-            self.v_head.backward(ctx, feat, v)
-            self.pi_head.backward(ctx, side, z)
-        self.lib.axpby(feat.grad, 1.0, feat.grad, 1.0, side.grad, feat.grad.numel(), ctx.stream)
-        feat.grad_is_dz = feat.grad_is_dz and side.grad_is_dz
-        self.torso.backward(ctx, acts)
-        if not self.clip_by_global_norm():
-            self.grad_norm()
-        return self.loss
+        self._heads_backward(acts[-1], fork, outs)
+        return self._finish_window(acts)
 
 
 def n_step_q_net_kwargs(np_, seed):
     """NStepQNetworkParameters -> the keywords of NStepQNet's constructor"""
-    return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
-                learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1,
-                adam_beta2=np_.adam_optimizer_beta2, optimizer_epsilon=np_.optimizer_epsilon,
-                clip_gradients=getattr(np_, "clip_gradients", None),
-                replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss, seed=seed)
+    return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),
+                replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss)
 
 
 class NStepQNet(_WindowAccumulatingNet):
@@ -1297,20 +1302,18 @@ class NStepQNet(_WindowAccumulatingNet):
     def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
                  learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None,
                  replace_mse_with_huber_loss=False, seed=0):
-        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        self.A = int(n_actions)
         self.clip_gradients = clip_gradients
         self.huber = bool(replace_mse_with_huber_loss)
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         self.q_head = G.Dense(self.params, "main/q_head/dense", feat, self.A, None, 1)
         self.modules = [self.torso, self.q_head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=True)
-        self._finish_accumulating(1)                                 # the loss of the last window
-        self.loss = self.scalars[0:1]
+        self._finish_accumulating(("loss",))                         # of the last window
         self.td_targets = None           # [T, A] of the last window: state_value_head_targets, the 'Q Values' samples
 
     def _q(self, obs, B, tag, weights=None):
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=weights)
+        acts = self.trunk_forward(obs, B, tag, weights)
         return acts, self.q_head.forward(self.ctx, acts[-1], tag=tag, weights=weights)
 
     def q_values(self, obs, B, tag="act"):
@@ -1345,10 +1348,7 @@ class NStepQNet(_WindowAccumulatingNet):
                                          int(horizon), int(self.huber), targets, self.td_targets, A, q.ensure_grad(), A,
                                          self.scalars, self.status, ctx.stream)
         self.q_head.backward(ctx, acts[-1], q)
-        self.torso.backward(ctx, acts)
-        if not self.clip_by_global_norm():
-            self.grad_norm()
-        return self.loss
+        return self._finish_window(acts)
 
 
 def acer_net_kwargs(np_, alg, seed):
@@ -1374,49 +1374,38 @@ class ACERNet(_WindowAccumulatingNet):
                  learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=40.0,
                  beta_entropy=0.0, q_loss_weight=0.5, importance_weight_truncation=10.0, max_kl_divergence=1.0,
                  trust_region=False, seed=0):
-        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
-        if not 1 <= self.A <= 18:
-            raise ValueError("the discrete policy head serves 1 .. 18 actions (got %d)" % self.A)
+        self.A = discrete_policy_actions(n_actions)
         self.clip_gradients = clip_gradients
         self.beta_entropy, self.q_loss_weight = float(beta_entropy), float(q_loss_weight)
         self.truncation, self.max_kl = float(importance_weight_truncation), float(max_kl_divergence)
         self.trust_region = bool(trust_region)
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         self.q_head = G.Dense(self.params, "main/q_head/dense", feat, self.A, None, 1)
         self.pi_head = G.Dense(self.params, "main/acer_policy_head/fc", feat, self.A, None, 1)
         self.heads = [self.q_head, self.pi_head]
         self.modules = [self.torso] + self.heads
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=True)
-        self._finish_accumulating(7)
-        sc = self.scalars
-        self.loss, self.q_loss, self.policy_loss, self.probability_loss = sc[0:1], sc[1:2], sc[2:3], sc[3:4]
-        self.bias_correction_loss, self.kl_divergence, self.entropy = sc[4:5], sc[5:6], sc[6:7]
+        self._finish_accumulating(("loss", "q_loss", "policy_loss", "probability_loss", "bias_correction_loss",
+                                   "kl_divergence", "entropy"))
         self.bootstrap_value = torch.zeros(1, dtype=torch.float32, device=device)
         self.adam_steps = 0
         self._window = {}
 
     def policy_values(self, obs, B, tag="act"):
         """the policy head's Dense output [B, A] (logits of the action probabilities); the Q head is not run"""
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
-        return self.pi_head.forward(self.ctx, acts[-1], tag=tag)
+        return self.pi_head.forward(self.ctx, self.trunk_forward(obs, B, tag)[-1], tag=tag)
 
-    def _heads_forward(self, x_q, x_pi, tag):
-        """both heads in one launch where the narrow-dense kernels serve the heads' width"""
-        if self.A <= G.SMALL_N:
-            return G.small_dense_forward_multi(self.ctx, [(self.q_head, x_q), (self.pi_head, x_pi)], tag=tag)
-        return self.q_head.forward(self.ctx, x_q, tag=tag), self.pi_head.forward(self.ctx, x_pi, tag=tag)
-
-    def predict(self, obs, B, tag="predict"):
-        """both heads of the ONLINE network -> (Q [B, A], logits [B, A]) as buffers"""
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag)
-        q, z = self._heads_forward(acts[-1], acts[-1], tag)
+    def predict(self, obs, B, tag="predict", use_target=False):
+        """both heads of the online network, or of the average (target) one -> (Q [B, A], logits [B, A]) as buffers"""
+        w = self.target if use_target else None
+        feat = self.trunk_forward(obs, B, tag, w)[-1]
+        q, z = self._heads_forward([(l, feat) for l in self.heads], tag, w)
         return q.data.view(B, self.A), z.data.view(B, self.A)
 
     def average_policy_values(self, obs, B, tag="avg"):
         """the AVERAGE (target) network's policy logits [B, A]"""
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=self.target)
-        return self.pi_head.forward(self.ctx, acts[-1], tag=tag, weights=self.target).data.view(B, self.A)
+        feat = self.trunk_forward(obs, B, tag, self.target)[-1]
+        return self.pi_head.forward(self.ctx, feat, tag=tag, weights=self.target).data.view(B, self.A)
 
     def window_buffers(self, T):
         """the window's arrays the launch writes (or, given, reads): V, rho, rho_i, avg_policy, q_retrace, td_targets"""
@@ -1445,30 +1434,17 @@ class ACERNet(_WindowAccumulatingNet):
         else:
             w, avg_z, mode = given, None, mode | _rlx.ACER_TARGETS_GIVEN
         self.window = w
-        acts = self.torso.forward(ctx, self.obs_tensor(obs_rows, rows), tag="train")
-        feat = acts[-1]
-        feat.ensure_grad()
-        # each head writes its input gradient into a buffer of its own; they are added into feat.grad below
-        side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
-        side.grad = ctx.buffer(self.pi_head.name + "/input:grad", tuple(feat.data.shape), tag="train")
-        q, z = self._heads_forward(feat, side, "train")
+        acts = self.trunk_forward(obs_rows, rows, "train")
+        fork = self._fork(acts[-1], self.heads, "train")
+        q, z = outs = self._heads_forward(fork, "train")
         self.q_online, self.logits = q.data.view(rows, A), z.data.view(rows, A)    # what the launch reads (for the tests)
         self.lib.acer_window_loss(q.data, A, z.data, A, rows, avg_z, A, mu, A, actions, rewards, game_over, T, A,
                                   float(discount), self.truncation, self.max_kl, self.beta_entropy, self.q_loss_weight,
                                   mode, w["V"], w["rho"], A, w["rho_i"], w["avg_policy"], A, w["q_retrace"],
                                   self.bootstrap_value, w["td_targets"], A, q.ensure_grad(), A, z.ensure_grad(), A,
                                   self.scalars, self.status, ctx.stream)
-        if A <= G.SMALL_N and rows * A <= 1024:
-            G.small_dense_backward_multi(ctx, [(self.q_head, feat, q), (self.pi_head, side, z)])
-        else:
-            self.q_head.backward(ctx, feat, q)
-            self.pi_head.backward(ctx, side, z)
-        self.lib.axpby(feat.grad, 1.0, feat.grad, 1.0, side.grad, feat.grad.numel(), ctx.stream)
-        feat.grad_is_dz = feat.grad_is_dz and side.grad_is_dz
-        self.torso.backward(ctx, acts)
-        if not self.clip_by_global_norm():
-            self.grad_norm()
-        return self.loss
+        self._heads_backward(acts[-1], fork, outs)
+        return self._finish_window(acts)
 
     def train_window(self, *args, rate=None, **kw):
         """train_and_sync_networks (network_wrapper.py:156-177): the window's gradients replace the accumulation buffer
@@ -1494,9 +1470,7 @@ class PPOCriticNet(_NetBase):
 
     def __init__(self, device, obs_shape, activation="tanh", embedder="Medium", middleware="Medium", learning_rate=2.5e-4,
                  adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, seed=0):
-        self.obs_shape, self.image = tuple(obs_shape), len(obs_shape) == 3
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         self.v_head = G.Dense(self.params, "main/v_head/dense", feat, 1, None, 1, init=G.normalized_columns(1.0))
         self.modules = [self.torso, self.v_head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
@@ -1506,14 +1480,14 @@ class PPOCriticNet(_NetBase):
     def values(self, obs, B, use_target=False, tag="val"):
         """V(s) [B] (fill_advantages, ppo_agent.py:163)"""
         w = self.target if use_target else None
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        acts = self.trunk_forward(obs, B, tag, w)
         return self.v_head.forward(self.ctx, acts[-1], tag=tag, weights=w).data.view(-1)
 
     def forward_backward(self, obs, B, value_targets):
         """accumulate_gradients of one critic minibatch (:233): forward, MSE against the fp32 targets [B], backward;
         the loss in self.loss"""
         ctx = self.ctx
-        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+        acts = self.trunk_forward(obs, B, "train")
         v = self.v_head.forward(ctx, acts[-1], tag="train")
         self.lib.regression_loss(v.data, 1, value_targets, 1, None, B, 1, 0, 1.0, 1.0, v.ensure_grad(), 1, self.loss,
                                  ctx.stream)
@@ -1538,7 +1512,7 @@ class PPOActorNet(_NetBase):
                  learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, beta_entropy=0.01,
                  target_kl_divergence=0.01, initial_kl_coefficient=1.0, high_kl_penalty_coefficient=1000.0,
                  use_kl_regularization=True, seed=0, continuous=False):
-        self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, int(n_actions)
+        self.A = int(n_actions)
         self.continuous = bool(continuous)
         limit = 32 if self.continuous else 18
         if not 1 <= self.A <= limit:
@@ -1546,8 +1520,7 @@ class PPOActorNet(_NetBase):
                              % (limit, "action dimensions" if self.continuous else "actions", self.A))
         self.beta, self.use_kl = float(beta_entropy), bool(use_kl_regularization)
         self.target_kl, self.high_kl = float(target_kl_divergence), float(high_kl_penalty_coefficient)
-        self.params = G.FlatParams()
-        self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
         if self.continuous:
             self.pi_head = G.Dense(self.params, "main/ppo_head/policy_mean", feat, self.A, None, 1,
                                    init=G.normalized_columns(0.01))
@@ -1565,7 +1538,7 @@ class PPOActorNet(_NetBase):
     def policy_probs(self, obs, B, use_target=False, tag="act", out=None):
         """softmax(policy_fc(tower(obs))) [B, A]; the target weights are the old policy"""
         w = self.target if use_target else None
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        acts = self.trunk_forward(obs, B, tag, w)
         logits = self.pi_head.forward(self.ctx, acts[-1], tag=tag, weights=w)
         probs = out if out is not None else self.ctx.buffer("probs", (B, self.A), tag=tag)
         self.lib.softmax(logits.data, self.A, B, self.A, probs, self.A, self.ctx.stream)
@@ -1574,7 +1547,7 @@ class PPOActorNet(_NetBase):
     def policy_mean_std(self, obs, B, use_target=False, tag="act", out_mean=None, out_std=None):
         """[policy_mean, policy_std] [B, A] each (ppo_head.py:138-144): std = exp(log_std) tiled over the batch"""
         w = self.target if use_target else None
-        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        acts = self.trunk_forward(obs, B, tag, w)
         mean = self.pi_head.forward(self.ctx, acts[-1], tag=tag, weights=w).data.view(B, self.A)
         std = out_std if out_std is not None else self.ctx.buffer("policy_std", (B, self.A), tag=tag)
         self.lib.exp_rows(self.params.w("main/ppo_head/policy_log_std", 0, w), std, B, self.A, self.ctx.stream)
@@ -1588,7 +1561,7 @@ class PPOActorNet(_NetBase):
         old_policy: the old probabilities [B, A], or (old_mean, old_std).  accumulate: add the minibatch's fetches onto
         epoch_sums."""
         ctx = self.ctx
-        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+        acts = self.trunk_forward(obs, B, "train")
         z = self.pi_head.forward(ctx, acts[-1], tag="train")
         acc = self.epoch_sums if accumulate else None
         if self.continuous:

@@ -280,6 +280,57 @@ def test_network_update_equals_the_composed_oracle(dev):
     assert torch.isfinite(net.params.weights).all()
 
 
+@pytest.mark.parametrize("A,T", [(16, 63),      # 64 rows, rows * A = 1024: both heads in one launch, forward and backward
+                                 (16, 64),      # 65 rows, rows * A = 1040: one launch forward, launches of their own backward
+                                 (17, 5)])      # wider than the narrow-dense kernels serve: launches of their own both ways
+def test_one_window_update_equals_the_composed_oracle_at_the_head_forks_branch_boundaries(dev, A, T):
+    """test_network_update_equals_the_composed_oracle with ONE window (the bootstrap row present) and one Adam step, at
+    the shapes where the heads' launches change form — the same oracle, restatement and tolerances."""
+    import torch
+    from coach_amd.nn.networks import ActorCriticNet
+    from oracle import nn as N
+    rng = np.random.RandomState(11)
+    lr, beta, lam = 5e-4, 0.01, 0.96
+    net = ActorCriticNet(dev, (4,), A, learning_rate=lr, optimizer_epsilon=1e-4, beta_entropy=beta, seed=3)
+    o = _oracle_for(net, (4,), lr, 1e-4)
+    w0 = net.params.weights.clone()
+    obs = rng.randn(T + 1, 4).astype(np.float32)
+    actions = rng.randint(0, A, size=T)
+    rewards = rng.uniform(-1, 2, size=T).astype(np.float32)
+    tgt = torch.zeros(T, dtype=torch.float64, device=dev)
+    adv = torch.zeros(T, dtype=torch.float64, device=dev)
+    loss = net.accumulate_window(_t(obs, dev), T, True, _t(actions.astype(np.int32), dev), tgt, adv, _t(rewards, dev),
+                                 _t(np.array([0], np.uint8), dev), 0.99, lam, R.A_VALUE, False)
+    feat = o.tower.forward(N.prep_obs(obs, False))
+    z, v = o.head.forward(feat).astype(np.float32), o.v_head.forward(feat).astype(np.float32)[:, 0]
+    r = R.window_loss(v, z, actions, rewards, False, 0.99, lam, R.A_VALUE, False, beta)
+    o.tower.backward(o.head.backward(r["dlogits"]) + o.v_head.backward(r["dV"][:, None]))
+    shards = [o.snapshot_grads()]
+    print("\n  A %d T %d: V max abs diff %.3e, loss %.6f / %.6f, norm %.6f / %.6f" % (
+        A, T, float(np.abs(net.values.cpu().numpy() - v).max()), float(loss.item()), r["loss"], float(net.norm.item()),
+        o.global_norm()))
+    np.testing.assert_allclose(net.values.cpu().numpy(), v, **OUT)
+    np.testing.assert_allclose(tgt.cpu().numpy(), r["targets"], **OUT)
+    np.testing.assert_allclose(adv.cpu().numpy(), r["advantages"], rtol=1e-4, atol=4e-6)
+    np.testing.assert_allclose(float(loss.item()), r["loss"], **LOSS)
+    np.testing.assert_allclose(float(net.value_loss.item()), r["value_loss"], **LOSS)
+    np.testing.assert_allclose(float(net.policy_loss.item()), r["policy_loss"], **LOSS)
+    np.testing.assert_allclose(float(net.entropy.item()), r["entropy"], **LOSS)
+    np.testing.assert_allclose(float(net.norm.item()), o.global_norm(), **LOSS)
+    assert o.global_norm() < 40.0                                    # (nothing is clipped in this test)
+    assert torch.equal(net.accumulated, net.params.grads) and net.accumulated.abs().sum() > 0
+    assert torch.equal(net.params.weights, w0)                       # nothing is applied while accumulating
+    net.apply_accumulated()
+    o.apply_summed_gradients(shards, 1, False)
+    assert not net.accumulated.any() and not torch.equal(net.params.weights, w0)
+    net.check_status()
+    w = net.params.named_arrays()
+    wo = {k.replace("main/q_head/dense", "main/policy_values_head/fc"): v for k, v in o.weights().items()}
+    assert set(wo) == set(w)
+    for name, towers in wo.items():
+        np.testing.assert_allclose(w[name][0], towers[0], err_msg=name, **WEIGHTS)
+
+
 def test_acting_runs_the_policy_head_alone_and_wide_heads_take_the_separate_launches(dev):
     """policy_values equals predict's logits; A = 18 is wider than the narrow-dense helper serves, so both heads run as
     launches of their own — the same window gives the restatement's losses either way"""

@@ -180,6 +180,32 @@ def test_network_update_equals_the_composed_restatement(dev, updates, clip):
     net.check_status()
 
 
+@pytest.mark.parametrize("A,B", [(5, 68),       # l_vector is 15 wide, B * 15 = 1020: the three layers in one launch both ways
+                                 (5, 69),       # B * 15 = 1035: l_vector's backward pass is a launch of its own
+                                 (6, 8)])       # l_vector is 21 wide: a launch of its own both ways
+def test_one_update_equals_the_composed_restatement_at_the_head_forks_branch_boundaries(dev, A, B):
+    """test_network_update_equals_the_composed_restatement with one unclipped update, at the shapes where the head
+    layers' launches change form."""
+    import torch
+    from coach_amd.nn.networks import NAFNet
+    scale = np.linspace(1.0, 2.0, A).astype(np.float32)
+    net = NAFNet(dev, (17,), A, scale, embedder=[200], middleware=[200], seed=3)
+    assert net.l_layer.N == A * (A + 1) // 2
+    o = ComposedNAF(net.params.named_arrays(), scale)
+    (obs, nxt, act, rew, go), = _batches(1, B=B, A=A)
+    loss = net.learn_from_batch(_t(obs, dev), _t(nxt, dev), B, _t(act, dev), _t(rew, dev), _t(go.astype(np.uint8), dev),
+                                0.99)
+    ref = o.learn(obs, nxt, act, rew, go, 0.99)
+    wd, wo = net.params.named_arrays(), o.weights()
+    print("\n  A %d B %d: loss %.6f / %.6f, weights max abs diff %.3e" % (
+        A, B, float(loss.item()), ref, max(float(np.abs(wd[n][0] - w).max()) for n, w in wo.items())))
+    np.testing.assert_allclose(float(loss.item()), ref, **LOSS)
+    for name, w in wo.items():
+        np.testing.assert_allclose(wd[name][0], w, err_msg=name, **WEIGHTS)
+    assert torch.isfinite(net.params.weights).all()
+    net.check_status()
+
+
 def _agent(dev, n_env=1, use_graphs=None, L=5, batch=16, seed=5):
     from coach_amd.agents.naf_agent import NAFAgent, NAFAgentParameters
     from coach_amd.environments.synthetic_vector_environment import (
