@@ -88,6 +88,7 @@ class DQNAgent(VectorOffPolicyAgent):
         self.networks = {"main": self.NET(self.device, obs_shape, self.A, *args, **kwargs,
                                           **dqn_net_kwargs(net, self.ap.seed or 0))}
         self._key_network_noise()
+        self._check_action_probabilities(net)
         self.memory = self._make_memory(action_dim=None)
         self._check_memory()
         self.exploration_policy = self._make_exploration_policy()
@@ -138,11 +139,65 @@ class DQNAgent(VectorOffPolicyAgent):
         cls = ParameterNoise if self.parameter_noise else EGreedy
         return cls(self.A, self.n_env, self.device, self.ap.exploration)
 
+    # ----------------------------------------------------------- all_action_probabilities (off-policy evaluation)
+    store_action_probabilities = False        # (class defaults: a subclass with a constructor of its own never stores them)
+    ope_manager = ope_estimation = ope_signals = None      # set by the Batch RL graph manager / run_off_policy_evaluation
+
+    def _check_action_probabilities(self, net):
+        """network_wrappers['main'].should_get_softmax_probabilities (value_optimization_agent.py:90-102): every stored
+        transition carries what the reference stores as all_action_probabilities — the uniform vector for a random step,
+        softmax(Q(s) / softmax_temperature) for a greedy one (rlx_behaviour_probabilities).  The choice of actions and the
+        host draws are untouched: the launch reads the Q values and the staged draw the choice was made on."""
+        self.store_action_probabilities = bool(getattr(net, "should_get_softmax_probabilities", False))
+        if not self.store_action_probabilities:
+            return
+        from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
+        from ..off_policy_evaluators.ope_manager import check_plain_q_head
+        check_plain_q_head(self, net)
+        if self.parameter_noise:
+            raise ValueError("should_get_softmax_probabilities is not served with the ParameterNoise exploration policy")
+        if type(self.ap.memory) is not EpisodicExperienceReplayParameters:
+            raise ValueError("should_get_softmax_probabilities needs an EpisodicExperienceReplay: it is the memory that "
+                             "keeps the action-probabilities column")
+        self.softmax_temperature = float(getattr(net, "softmax_temperature", 1))
+        self._behaviour_probs = torch.zeros(self.n_env, self.A, dtype=torch.float32, device=self.device)
+
+    def _behaviour_probabilities(self, u, eps, force_uniform=False):
+        if self.store_action_probabilities and self.phase != RunPhase.TEST:      # evaluation steps are not stored
+            self.lib.behaviour_probabilities(None if force_uniform else self._q_act, self.A, u, float(eps),
+                                             int(force_uniform), self.softmax_temperature, self.n_env, self.A,
+                                             self._behaviour_probs, self.A, _rlx.current_stream())
+
+    def _store_extra_host(self, dones_host, record):
+        extra = super()._store_extra_host(dones_host, record)
+        if record and self.store_action_probabilities:
+            extra["action_probabilities"] = self._behaviour_probs
+        return extra
+
+    def run_off_policy_evaluation(self):
+        """ValueOptimizationAgent.run_off_policy_evaluation (value_optimization_agent.py:133-171) -> OpeEstimation; the
+        five values are kept in self.ope_estimation and, by the reference's signal names, in self.ope_signals."""
+        assert self.ope_manager
+        pre = getattr(self.ap, "pre_network_filter", None)
+        if pre is not None and len(getattr(pre, "_reward_filters", ())) != 0:
+            raise ValueError("Defining a pre-network reward filter when OPEs are calculated will result in a mismatch "
+                             "between q values (which are scaled), and actual rewards, which are not. It is advisable "
+                             "to use an input_filter, if possible, instead, which will filter the transitions directly "
+                             "in the replay buffer, affecting both the q_values and the rewards themselves. ")
+        from ..off_policy_evaluators.ope_manager import SIGNAL_NAMES
+        wrapper = self.ap.network_wrappers['main']
+        est = self.ope_manager.evaluate(self.memory, wrapper.batch_size, self.ap.algorithm.discount,
+                                        self.networks['main'], getattr(wrapper, 'softmax_temperature', 1))
+        self.ope_estimation = est
+        self.ope_signals = dict(zip(SIGNAL_NAMES, est))
+        return est
+
     # --------------------------------------------------------------------------------- acting
     def random_actions(self):
         """spaces.DiscreteActionSpace.sample (spaces.py:406-407): np.random.choice(actions) per env."""
         a = np.array([np.random.choice(self.A) for _ in range(self.n_env)], dtype=np.int32)
         self.actions.copy_(self._to_device("rand_act", a, torch.int32))
+        self._behaviour_probabilities(None, 0.0, force_uniform=True)
         return self.actions
 
     def choose_action(self, states):
@@ -157,10 +212,12 @@ class DQNAgent(VectorOffPolicyAgent):
             # small MLP, a few envs: Q(s) and the epsilon-greedy choice are ONE launch
             eps, d = self.exploration_policy.stage(draws)
             net.q_act(states, self.n_env, d["u"], d["ra"], d["tie"], eps, self._q_buf(), self.actions)
+            self._behaviour_probabilities(d["u"], eps)           # (the launch left Q(s) in the buffer)
             return self.actions
         self._run(("q", self.n_env), lambda: self._q_forward(states))
         eps, d = self.exploration_policy.stage(draws)
         self._select_actions(d["u"], d["ra"], d["tie"], eps)
+        self._behaviour_probabilities(d["u"], eps)
         return self.actions
 
     def _q_buf(self):
@@ -234,7 +291,8 @@ class DQNAgent(VectorOffPolicyAgent):
         from ..memories.non_episodic.experience_replay import ExperienceReplay
         # (ParameterNoise: the record's epsilon-greedy draws do not exist; act() + train() run as they are)
         return (self.use_graphs and self.dist is None and self.phase == RunPhase.TRAIN and not self.image
-                and not self.parameter_noise and type(self.memory) is ExperienceReplay and self.signal_stats is None
+                and not self.parameter_noise and not self.store_action_probabilities
+                and type(self.memory) is ExperienceReplay and self.signal_stats is None
                 and self.debug_draws is None and self.debug_losses is None
                 and hasattr(self.env, "launch_step") and hasattr(self.env, "host_tick"))
 

@@ -355,7 +355,9 @@ class VectorOffPolicyAgent(GraphRunner):
             return EpisodicExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling,
                                             n_step=getattr(mp, "n_step", -1), discount=self.ap.algorithm.discount,
                                             max_episode_length=self.L,
-                                            train_to_eval_ratio=getattr(mp, "train_to_eval_ratio", 1), **kw)
+                                            train_to_eval_ratio=getattr(mp, "train_to_eval_ratio", 1),
+                                            action_probabilities=self.A if getattr(self, "store_action_probabilities",
+                                                                                   False) else 0, **kw)
         if getattr(self, "MASK_COLUMN", False):
             kw["mask_column"] = True
         return ExperienceReplay(mp.max_size, mp.allow_duplicates_in_batch_sampling, **kw)

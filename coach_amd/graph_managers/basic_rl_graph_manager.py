@@ -226,9 +226,14 @@ class BasicRLGraphManager(object):
         self.total_steps_counters[RunPhase.TEST] += self.environment.total_steps - before
         self.logger.write(**{"Episode #": self._episodes_logged, "Training Iter": self.agent.training_iteration,
                              "Epoch": 0, "In Heatup": 0, "Total steps": self.agent.total_steps_counter,
-                             "Evaluation Reward": reward, "Shaped Evaluation Reward": reward})
+                             "Evaluation Reward": reward, "Shaped Evaluation Reward": reward},
+                          **self._evaluation_row_extras())
         self._set_phase(RunPhase.TRAIN)
         return reward
+
+    def _evaluation_row_extras(self):
+        """more cells of the evaluation's CSV row, by column name (Batch RL: the off-policy estimates)"""
+        return {}
 
     # ---------------------------------------------------------------- golden-threshold harness
     def validation_status(self, win_size=10):

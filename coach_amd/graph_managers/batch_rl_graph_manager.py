@@ -8,8 +8,14 @@ training and evaluation episodes.  The trained agent never plays to learn: after
 evaluate against the environment".  Time is counted in epochs (TimeTypes.Epoch of the reference): the evaluation rows'
 'Episode #' is the epoch, so a preset's max_episodes_to_achieve_reward bounds epochs.
 
-Out of scope: the off-policy evaluators (IPS, DM, DR, WIS, sequential DR) with softmax_temperature /
-should_get_softmax_probabilities, load_memory_from_file_path, NEC as the trained agent, a checkpoint per epoch.
+Off-policy evaluation (:116,130,239,247-266) is switched by the attribute ``off_policy_evaluation`` (default False; set
+it before create_graph): both agents' main wrappers get should_get_softmax_probabilities, so that the memories keep the
+all_action_probabilities column; the evaluation set's static columns are gathered after improve_reward_model; after every
+epoch's training and before the evaluation against the environment, run_off_policy_evaluation() computes IPS, DM, DR,
+sequential DR and WIS (off_policy_evaluators/ope_manager.py), which go into that epoch's CSV row under the reference's
+signal names.  With the switch off nothing of this exists and the CSV is what it was.
+
+Out of scope: load_memory_from_file_path, NEC as the trained agent, a checkpoint per epoch.
 """
 from copy import deepcopy
 
@@ -39,6 +45,9 @@ class BatchRLGraphManager(BasicRLGraphManager):
             experience_generating_agent_params.memory.train_to_eval_ratio = train_to_eval_ratio
         self.epochs = 0
         self.dataset_training_steps = 0     # updates of the experience-generating agent
+        self.off_policy_evaluation = False  # set before create_graph: the five off-policy estimates after every epoch
+        self.per_row_direct_method = False  # the paper's direct method instead of the reference's (ope_manager.py)
+        self.ope_estimations = []           # one OpeEstimation per epoch
 
     def create_graph(self):                                                     # :96-154
         from ..agents.dqn_agent import DQNAgentParameters
@@ -56,6 +65,10 @@ class BatchRLGraphManager(BasicRLGraphManager):
         ap.is_batch_rl_training = True
         if 'reward_model' not in ap.network_wrappers:
             ap.network_wrappers['reward_model'] = deepcopy(ap.network_wrappers['main'])
+        if self.off_policy_evaluation:                                          # :116,130
+            ap.network_wrappers['main'].should_get_softmax_probabilities = True
+            if not self.is_collecting_random_dataset:
+                self.experience_generating_agent_params.network_wrappers['main'].should_get_softmax_probabilities = True
         resolve_reference_style(ap, self.env_params)
         self.environment = dynamic_import(self.env_params.path)(self.env_params, self.device, rank=rank)
         self.trained_agent = dynamic_import(ap.path)(ap, self.environment, self.device, dist=self.dist,
@@ -91,6 +104,11 @@ class BatchRLGraphManager(BasicRLGraphManager):
         trained.memory.freeze()
         trained.memory.prepare_evaluation_dataset()
         trained.improve_reward_model(self.reward_model_num_epochs)
+        if self.off_policy_evaluation:                                          # :247-266
+            from ..off_policy_evaluators.ope_manager import OpeManager
+            trained.ope_manager = OpeManager(per_row_direct_method=self.per_row_direct_method)
+            trained.ope_manager.gather_static_shared_stats(
+                trained.memory, trained.ap.network_wrappers['reward_model'].batch_size, trained.networks['reward_model'])
         end = self.epochs + self.schedule.improve_steps.num_steps
         while self.epochs < end:
             self._set_phase(RunPhase.TRAIN)
@@ -100,8 +118,16 @@ class BatchRLGraphManager(BasicRLGraphManager):
                 self.training_steps += trained.training_iteration - before
                 self.epochs += 1
             self._episodes_logged = self.epochs                                  # time is counted in epochs
+            if self.off_policy_evaluation:                                      # :239
+                self.ope_estimations.append(trained.run_off_policy_evaluation())
             self.evaluate(self.schedule.evaluation_steps)
             if should_stop is not None and should_stop():
                 break
         self.check_status()
         return self.logger.rows
+
+    def _evaluation_row_extras(self):
+        if not self.off_policy_evaluation or not self.ope_estimations:
+            return {}
+        from ..off_policy_evaluators.ope_manager import SIGNAL_NAMES
+        return dict(zip(SIGNAL_NAMES, self.ope_estimations[-1]))

@@ -49,7 +49,7 @@ class EpisodicExperienceReplayParameters(ExperienceReplayParameters):        # :
 class EpisodicExperienceReplay(ExperienceReplay):
     def __init__(self, max_size, allow_duplicates_in_batch_sampling=True, n_step=-1, discount=0.99,
                  max_episode_length=None, measurements_dim=None, future_measurements=None, train_to_eval_ratio=1,
-                 **device_kwargs):
+                 action_probabilities=0, **device_kwargs):
         """
         :param max_size: (MemoryGranularity.Transitions | Episodes, n)               (reference signature)
         :param n_step: steps summed into n_step_discounted_rewards (-1: to the episode end)   (reference signature)
@@ -62,6 +62,9 @@ class EpisodicExperienceReplay(ExperienceReplay):
                                  when an env's episode is stored (DFPAgent._update_measurements_targets,
                                  rlx_dfp_future_measurements); last_step: HandlingTargetsAfterEpisodeEnd.LastStep, else NAN
         :param train_to_eval_ratio: Batch RL: the share of the frozen dataset that is trained on          (reference signature)
+        :param action_probabilities: A > 0 — keep an fp32 column [rows][A] of what the reference stores as a transition's
+                                 info['all_action_probabilities'] (off-policy evaluation divides by it; store() then takes
+                                 the step's rows); absent (0) unless asked for
         """
         if not isinstance(n_step, int) or (n_step < 1 and n_step != -1):
             raise ValueError("n-step should be an integer with value >= 1, or set to -1 for always setting to "
@@ -97,6 +100,10 @@ class EpisodicExperienceReplay(ExperienceReplay):
             self.future_scale = torch.tensor([float(x) for x in scale], dtype=torch.float64, device=self.device)
             self.future_measurements = torch.zeros(self.rows, self.future_steps * self.M, dtype=torch.float32,
                                                    device=self.device)
+        self.action_probabilities = None
+        if action_probabilities:
+            self.action_probabilities = torch.zeros(self.rows, int(action_probabilities), dtype=torch.float32,
+                                                    device=self.device)
         self._order = np.zeros(transitions + 2 * self.Tmax + 1, dtype=np.int64)   # ring of listed rows
         self.train_to_eval_ratio = train_to_eval_ratio            # used in batch-rl (:69-75)
         self.last_training_set_episode_id = None
@@ -138,9 +145,11 @@ class EpisodicExperienceReplay(ExperienceReplay):
 
     # ------------------------------------------------------------------------------ rollout side
     def store(self, actions, rewards, game_overs, next_obs, reset_obs, record=True, dones=None, defer=False,
-              episode_end=False, dones_host=None, measurements=None):
+              episode_end=False, dones_host=None, measurements=None, action_probabilities=None):
         """measurements: the STATES' measurements of this step's transitions (device fp64 [n_env][M]); required where
         the memory keeps the column.
+        action_probabilities: the step's all_action_probabilities (device fp32 [n_env][A]); required where the memory keeps
+        the column.
         One vector step (Agent.observe_transition -> current_episode_buffer.insert, agent.py:956-962), then
         `store_episode` for every env whose episode ended (dones_host: host bool[n_env]; None = lockstep envs,
         all ended iff episode_end).  `defer` is irrelevant here: an episode becomes sampleable only when it is
@@ -170,6 +179,11 @@ class EpisodicExperienceReplay(ExperienceReplay):
                                  "without them")
             if measurements is not None:
                 pairs.append((measurements, self.measurements))
+            if (action_probabilities is None) != (self.action_probabilities is None):
+                raise ValueError("a memory with an action-probabilities column is stored with action_probabilities, one "
+                                 "without it without them")
+            if action_probabilities is not None:
+                pairs.append((action_probabilities, self.action_probabilities))
             self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, None, 0, row0, self.n_env,
                                   self.rows, self.n_env, self.status, s)
         self.lib.select_rows(game_overs, reset_obs, next_obs, self.cur_state, self.n_env, self.obs_dim * 4, s)
@@ -255,6 +269,9 @@ class EpisodicExperienceReplay(ExperienceReplay):
             if self.future_measurements is not None:
                 b["future_measurements"] = torch.empty(size, self.future_steps * self.M, dtype=torch.float32,
                                                        device=self.device)
+            if self.action_probabilities is not None:
+                b["action_probabilities"] = torch.empty(size, self.action_probabilities.shape[1], dtype=torch.float32,
+                                                        device=self.device)
         return b
 
     def _extra_gather_columns(self):
@@ -263,6 +280,8 @@ class EpisodicExperienceReplay(ExperienceReplay):
             cols.append((self.measurements, "measurements64"))
         if self.future_measurements is not None:
             cols.append((self.future_measurements, "future_measurements"))
+        if self.action_probabilities is not None:
+            cols.append((self.action_probabilities, "action_probabilities"))
         return cols
 
     def collate(self, drawn, size, rows_dev=None):
@@ -275,6 +294,8 @@ class EpisodicExperienceReplay(ExperienceReplay):
             states["measurements"] = b["measurements"]
         if self.future_measurements is not None:
             info["future_measurements"] = b["future_measurements"]
+        if self.action_probabilities is not None:
+            info["all_action_probabilities"] = b["action_probabilities"]
         return DeviceBatch(size, states, {"observation": b["next_state"]}, b["action"], b["reward"], b["game_over"],
                            info=info)
 

@@ -7,8 +7,11 @@ The DDQN-BCQ agent then learns from the frozen dataset (40 % of it is the traini
 discount .98, a target copy every 100 updates, lr 1e-4, MSE loss, L2 regularization 1e-4, the kNN action mask with its
 defaults, rewards rescaled by 1 / 200 (the trained agent's input filter serves the collecting agent too), 30
 reward-model epochs (lr 1e-4, no L2), greedy evaluation over 10 episodes after every epoch.  Its golden test: an evaluation reward of 150 within 50 epochs.  The level is CartPole-v0 on the device
-(coach_amd/environments/cartpole_vector_environment.py).  The reference preset's imitation-model wrapper and
-softmax_temperature belong to what stays out of scope and are not set.
+(coach_amd/environments/cartpole_vector_environment.py).  make(off_policy_evaluation=True) adds what the reference preset
+sets for its off-policy evaluators: softmax_temperature = 0.2 on the `main` and `reward_model` wrappers, and the graph
+manager's switch (IPS, DM, DR, sequential DR and WIS after every epoch, in that epoch's CSV row).  It is off by default:
+the module-level graph_manager is the experiment as it was.  The reference preset's imitation-model wrapper stays out of
+scope and is not set.
 """
 from copy import deepcopy
 
@@ -29,8 +32,10 @@ DATASET_SIZE = 10000
 
 
 def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, reward_model_num_epochs=30,
-         improve_epochs=10000000000, batch_size=128, evaluation_episodes=10, train_to_eval_ratio=0.4):
-    """seed: the environment's reset-state streams; agent_seed: both agents' host generators and initial weights"""
+         improve_epochs=10000000000, batch_size=128, evaluation_episodes=10, train_to_eval_ratio=0.4,
+         off_policy_evaluation=False):
+    """seed: the environment's reset-state streams; agent_seed: both agents' host generators and initial weights;
+    off_policy_evaluation: the five off-policy estimates after every epoch (softmax_temperature 0.2)"""
     sched = ScheduleParameters()
     sched.improve_steps = TrainingSteps(improve_epochs)
     sched.steps_between_evaluation_periods = TrainingSteps(1)
@@ -52,6 +57,9 @@ def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, 
     agent.network_wrappers['reward_model'] = deepcopy(main)
     agent.network_wrappers['reward_model'].learning_rate = 0.0001
     agent.network_wrappers['reward_model'].l2_regularization = 0
+    if off_policy_evaluation:
+        main.softmax_temperature = 0.2
+        agent.network_wrappers['reward_model'].softmax_temperature = 0.2
     agent.memory = EpisodicExperienceReplayParameters()
     agent.exploration.epsilon_schedule = LinearSchedule(0, 0, 10000)
     agent.exploration.evaluation_epsilon = 0
@@ -75,11 +83,14 @@ def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, 
     env = CartPoleVectorEnvironmentParameters(1, "CartPole-v0", seed=seed)
     validation = PresetValidationParameters(test=True, min_reward_threshold=150, max_episodes_to_achieve_reward=50,
                                             read_csv_tries=500)
-    return BatchRLGraphManager(agent_params=agent, experience_generating_agent_params=gen,
-                               experience_generating_schedule_params=gen_sched, env_params=env, schedule_params=sched,
-                               vis_params=VisualizationParameters(dump_signals_to_csv_every_x_episodes=1),
-                               preset_validation_params=validation, reward_model_num_epochs=reward_model_num_epochs,
-                               train_to_eval_ratio=train_to_eval_ratio)
+    manager = BatchRLGraphManager(agent_params=agent, experience_generating_agent_params=gen,
+                                  experience_generating_schedule_params=gen_sched, env_params=env, schedule_params=sched,
+                                  vis_params=VisualizationParameters(dump_signals_to_csv_every_x_episodes=1),
+                                  preset_validation_params=validation, reward_model_num_epochs=reward_model_num_epochs,
+                                  train_to_eval_ratio=train_to_eval_ratio)
+    if off_policy_evaluation:
+        manager.off_policy_evaluation = True
+    return manager
 
 
 graph_manager = make()

@@ -1669,6 +1669,72 @@ int rlx_bcq_masked_selector(const float *q_next_online, long long ld_q, const fl
 int rlx_reward_model_targets(const float *prediction, long long ld_p, const int *actions, const float *rewards, int batch,
                              int n_actions, float *targets, long long ld_t, int *status, void *stream);
 
+/* ------------------------------------------------- Batch RL: off-policy evaluation -- */
+/* (csrc/ope.hip; numpy restatement: tests/ope_ref.py.  Entry points ADDED under ABI version 11: no existing signature
+ * or structure changed.)  All three are capturable, deterministic (no floating-point atomics: the same bits on a second
+ * call), synchronise nothing with the host, serve 1 <= n_actions <= RLX_OPE_MAX_ACTIONS and accept padded leading
+ * dimensions.
+ *
+ * The fp32 softmax both sides share (heads/q_head.py:56-68, softmax(q / temperature)): z[k] = q[k] / (float)temperature;
+ * m = max z; e[k] = expf(z[k] - m); s = e[0] + e[1] + ... in action order from 0.f; p[k] = e[k] / s — every operation
+ * rounded to fp32 on its own.
+ *
+ * rlx_behaviour_probabilities: what the reference stores as all_action_probabilities while a dataset is collected
+ * (agents/value_optimization_agent.py:98-102, exploration_policies/e_greedy.py:84-101, spaces.py:458).  Per env e,
+ * probs_out[e][.] is the uniform vector 1.0f / (float)n_actions when force_uniform != 0 (random heat-up) or
+ * explore_uniforms[e] < epsilon (rlx_egreedy's comparison on the same staged draw), else the softmax above of
+ * q_values[e].  With force_uniform != 0, q_values and explore_uniforms may be null. */
+#define RLX_OPE_MAX_ACTIONS 18
+int rlx_behaviour_probabilities(const float *q_values, long long ld_q, const double *explore_uniforms, double epsilon,
+                                int force_uniform, double temperature, int n_env, int n_actions, float *probs_out,
+                                long long ld_out, void *stream);
+/* OpeManager._prepare_ope_shared_stats and the per-row terms of DoublyRobust.evaluate (off_policy_evaluators/
+ * ope_manager.py:49-101, bandits/doubly_robust.py:34-38), one lane per evaluation row j of n_rows.  pi_out[j][.] is the
+ * softmax above of q_values[j].  row_columns is fp64 [RLX_OPE_ROW_COLUMNS][n_rows] (plane c at row_columns + c * n_rows),
+ * every value computed in fp64 from fp32 values widened once, sums over the actions in action order from 0.0:
+ *   RHO      rho_j = pi[j][a_j] / mu[j][a_j]                 (mu = behaviour_probs; a zero there is not special-cased:
+ *                                                             the IEEE inf, or NaN of 0 / 0, propagates as in numpy)
+ *   V        v_j   = sum_a pi[j][a] * q[j][a]
+ *   Q_TAKEN  q[j][a_j]
+ *   IPS      rho_j * r_j
+ *   DM       sum_a pi[j][a] * reward_model[j / dm_row_divisor][a]
+ *   DR       rho_j * (r_j - reward_model[j][a_j])
+ * dm_row_divisor >= 1: 1 is the direct method of the paper; the reference multiplies every row of inference batch i by
+ * the reward model's output for dataset row i (ope_manager.py:80), which is dm_row_divisor = its batch size.
+ * An action outside [0, n_actions) sets status bit 1 and its row's six values are 0 (pi_out is still written). */
+#define RLX_OPE_ROW_COLUMNS 6
+#define RLX_OPE_COL_RHO 0
+#define RLX_OPE_COL_V 1
+#define RLX_OPE_COL_Q_TAKEN 2
+#define RLX_OPE_COL_IPS 3
+#define RLX_OPE_COL_DM 4
+#define RLX_OPE_COL_DR 5
+int rlx_ope_rows(const float *q_values, long long ld_q, const float *reward_model, long long ld_rm,
+                 long long dm_row_divisor, const int *actions, const float *rewards, const float *behaviour_probs,
+                 long long ld_mu, double temperature, long long n_rows, int n_actions, float *pi_out, long long ld_pi,
+                 double *row_columns, int *status, void *stream);
+/* The five estimates from rlx_ope_rows' columns (bandits/doubly_robust.py:34-38, rl/sequential_doubly_robust.py:40-51,
+ * rl/weighted_importance_sampling.py:41-55).  episode_offsets: device int32 [n_episodes + 1] into the evaluation rows
+ * (clamped to [0, n_rows]); rewards fp32 [n_rows]; returns fp64 [n_rows], of which the first row of every episode is
+ * read (its n_step_discounted_rewards).  episode_columns is fp64 [RLX_OPE_EPISODE_COLUMNS][n_episodes]:
+ *   SEQ_DR  the value at the episode's first row of acc_j = A_j + B_j * acc_{j+1}, acc past the last row = 0, with
+ *           B_j = discount * rho_j and A_j = v_j + rho_j * (r_j - q[j][a_j]) — as the composition of the rows' affine
+ *           maps, 64 rows per pass of one wave, the passes folded in row order
+ *   W       w_e = the product of rho_j over the episode (the same tree)
+ *   WR      w_e * returns[first row]   (0 for an episode without rows)
+ * out is fp64 [RLX_OPE_OUT]: {IPS = sum IPS_j / n, DM = sum DM_j / n, DR = sum DR_j / n + DM, sequential DR = sum
+ * SEQ_DR_e / E, WIS = sum WR_e / sum W_e or 0 when sum W_e == 0, sum W_e, E}; the six sums are fixed-shape fp64 trees.
+ * Two launches.  Where a rho is not finite the composed map may hold a NaN where the reference's row-by-row loop holds
+ * an infinity (inf * 0 inside the composition). */
+#define RLX_OPE_EPISODE_COLUMNS 3
+#define RLX_OPE_EP_SEQ_DR 0
+#define RLX_OPE_EP_W 1
+#define RLX_OPE_EP_WR 2
+#define RLX_OPE_OUT 7
+int rlx_ope_reduce(const int *episode_offsets, int n_episodes, long long n_rows, const double *row_columns,
+                   const float *rewards, const double *returns, double discount, double *episode_columns, double *out,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
