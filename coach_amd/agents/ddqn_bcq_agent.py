@@ -31,7 +31,7 @@ from ..exploration_policies.parameter_noise import ParameterNoiseParameters, net
 from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
 from ..nn.networks import DQNNet, dqn_net_kwargs
 from ..schedules import LinearSchedule
-from .dqn_agent import DQNAgent, DQNAgentParameters, DQNAlgorithmParameters
+from .dqn_agent import DQNAgent, DQNAgentParameters, DQNAlgorithmParameters, check_load_memory_from_file_path
 
 
 class NNImitationModelParameters(Parameters):            # ddqn_bcq_agent.py:31-38 (a parameter class only)
@@ -176,6 +176,7 @@ class DDQNBCQAgent(DQNAgent):
         if isinstance(ap.exploration, ParameterNoiseParameters) or network_is_noisy(ap.network_wrappers["main"]):
             raise ValueError("the ParameterNoise exploration policy (noisy dense layers) is not implemented for "
                              "DDQNBCQAgent")
+        dataset = check_load_memory_from_file_path(ap)
         if 'reward_model' not in ap.network_wrappers:
             ap.network_wrappers['reward_model'] = deepcopy(ap.network_wrappers['main'])
         super().__init__(ap, environment, device, dist, use_graphs)
@@ -194,6 +195,8 @@ class DDQNBCQAgent(DQNAgent):
         self.zero_rows_total = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._zero_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._bcq_buffers = {}
+        if dataset is not None:                        # agent.py:262-263: the memory starts as the file
+            self.load_memory_from_file()
 
     def _step_graph_ok(self):
         return False

@@ -192,6 +192,20 @@ class DQNAgent(VectorOffPolicyAgent):
         self.ope_signals = dict(zip(SIGNAL_NAMES, est))
         return est
 
+    # ------------------------------------------------------------- load_memory_from_file_path (agent.py:262-282)
+    def load_memory_from_file(self):
+        """Agent.load_memory_from_file: the memory starts as the CSV file the memory parameters name.  The agent's reward
+        filters (the flat fields its input filter was folded into) are applied by the ingest launch, as the acting path
+        applies them before it stores; the memory is left frozen.  An agent that keeps the action probabilities is
+        one that will be evaluated off-policy, and those estimators read the episodes' returns: it asks for them."""
+        dataset = check_load_memory_from_file_path(self.ap)
+        if not hasattr(self.memory, "load_csv"):
+            raise ValueError("load_memory_from_file_path needs an EpisodicExperienceReplay, not %s"
+                             % type(self.memory).__name__)
+        alg = self.ap.algorithm
+        return self.memory.load_csv(dataset, reward_filter=(float(alg.reward_rescale), alg.reward_clipping),
+                                    n_actions=self.A, n_step_returns=self.store_action_probabilities)
+
     # --------------------------------------------------------------------------------- acting
     def random_actions(self):
         """spaces.DiscreteActionSpace.sample (spaces.py:406-407): np.random.choice(actions) per env."""
@@ -420,6 +434,30 @@ class DQNAgent(VectorOffPolicyAgent):
             start = end
         loss = self._loss_signals()
         return loss if k else None
+
+
+def check_load_memory_from_file_path(ap):
+    """what an agent refuses about memory.load_memory_from_file_path before anything touches the device -> the
+    CsvDataset, or None when nothing is to be loaded (agent.py:272-282)"""
+    from ..core_types import CsvDataset, PickledReplayBuffer
+    dataset = getattr(ap.memory, "load_memory_from_file_path", None)
+    if not dataset:
+        return None
+    if isinstance(dataset, PickledReplayBuffer):
+        raise ValueError("Loading a pickled replay buffer ({}) is not served: a pickle of the reference's Episode "
+                         "objects is bound to its classes. Use a CsvDataset.".format(dataset.filepath))
+    if not isinstance(dataset, CsvDataset):
+        raise ValueError('Trying to load a replay buffer using an unsupported method - {}. '.format(dataset))
+    flt = getattr(ap, "input_filter", None)
+    if flt is not None and any(len(d) for d in getattr(flt, "_observation_filters", {}).values()):
+        raise ValueError("only reward filters of the input filter are applied to a loaded dataset: observation filters "
+                         "{} together with load_memory_from_file_path are not served"
+                         .format(sorted(flt._observation_filters)))
+    if getattr(ap.algorithm, "normalize_observations", False):
+        raise ValueError("observation normalization together with load_memory_from_file_path is not served")
+    from ..memories.episodic.csv_dataset import check_header
+    check_header(dataset.filepath, bool(getattr(ap.network_wrappers["main"], "should_get_softmax_probabilities", False)))
+    return dataset
 
 
 def __getattr__(name):

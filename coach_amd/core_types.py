@@ -50,6 +50,23 @@ class GradientClippingMethod(Enum):                      # core_types.py:690-693
     ClipByValue = 2
 
 
+class CsvDataset(object):                                 # core_types.py:922-925
+    """MemoryParameters.load_memory_from_file_path: a CSV file of logged transitions (memories/episodic/csv_dataset.py
+    states the schema); is_episodic: the last transition of every episode is a game over."""
+
+    def __init__(self, filepath, is_episodic=True):
+        self.filepath = filepath
+        self.is_episodic = is_episodic
+
+
+class PickledReplayBuffer(object):                        # core_types.py:928-930
+    """Named for presets that import it; refused when used: a pickle of the reference's Episode objects is bound to the
+    reference's classes."""
+
+    def __init__(self, filepath):
+        self.filepath = filepath
+
+
 class Transition(object):
     """core_types.py:236-340 — the object agents written against the reference store and receive
     (coach_amd/memories/reference_api.py); the device agents move columns instead and never build one."""

@@ -12,6 +12,7 @@
 // fp64 arithmetic in the reference's operation order; compiled with -ffp-contract=off so the
 // uint8 truncation and the running sums are bit-identical to numpy.  HBM-bound streaming kernels.
 #include "rlx_common.hpp"
+#include "reward_filter.hpp"
 
 namespace {
 
@@ -128,10 +129,7 @@ __global__ void reward_filter_kernel(const float *__restrict__ in, float *__rest
                                      int use_lo, double lo) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        double r = (double)in[i] * rescale;
-        if (use_hi) r = fmin(r, hi);
-        if (use_lo) r = fmax(r, lo);
-        out[i] = (float)r;
+        out[i] = rlx::reward_filter_value(in[i], rescale, use_hi, hi, use_lo, lo);
     }
 }
 

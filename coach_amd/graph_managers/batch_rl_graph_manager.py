@@ -15,7 +15,16 @@ epoch's training and before the evaluation against the environment, run_off_poli
 sequential DR and WIS (off_policy_evaluators/ope_manager.py), which go into that epoch's CSV row under the reference's
 signal names.  With the switch off nothing of this exists and the CSV is what it was.
 
-Out of scope: load_memory_from_file_path, NEC as the trained agent, a checkpoint per epoch.
+A dataset from a file (:97-104,141-154,174-177,234-241): when agent_params.memory.load_memory_from_file_path names a
+core_types.CsvDataset, the trained agent's memory starts as that file (one device ingest launch, agents/dqn_agent.py
+load_memory_from_file), and neither heat-up nor the experience-generating agent runs.  ``env_params=None`` together with
+a ``spaces_definition`` (a vector observation and a DiscreteActionSpace) then runs without a simulator: the agent is
+built on a stand-in (environments/dataset_environment.py) that cannot be stepped, every epoch's CSV row carries the
+off-policy estimates and an empty 'Evaluation Reward'.  With ``checkpoint_save_dir`` set, a checkpoint of the trained
+agent is saved after every epoch block (:234-236), named by the epoch.
+
+Out of scope: NEC as the trained agent, pickled replay buffers, image observations and continuous actions in
+files.
 """
 from copy import deepcopy
 
@@ -48,20 +57,30 @@ class BatchRLGraphManager(BasicRLGraphManager):
         self.off_policy_evaluation = False  # set before create_graph: the five off-policy estimates after every epoch
         self.per_row_direct_method = False  # the paper's direct method instead of the reference's (ope_manager.py)
         self.ope_estimations = []           # one OpeEstimation per epoch
+        self.checkpoint_save_dir = None     # a directory: a checkpoint of the trained agent after every epoch block
 
     def create_graph(self):                                                     # :96-154
         from ..agents.dqn_agent import DQNAgentParameters
         from ..compat import resolve_reference_style
         from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
+        from_file = getattr(self.agent_params.memory, "load_memory_from_file_path", None)
         if self.env_params is None:
-            raise ValueError("a BatchRLGraphManager without an environment needs load_memory_from_file_path, which is "
-                             "not served")
+            # (the reference only warns when there is neither, and then cannot train: :141-144)
+            if not from_file:
+                raise ValueError("A BatchRLGraph requires setting a dataset to load into the agent's memory or "
+                                 "alternatively using an environment to create a (random) dataset from.")
+            if self.spaces_definition is None:
+                raise ValueError("a BatchRLGraphManager without an environment needs a spaces_definition")
         if not isinstance(self.agent_params, DQNAgentParameters):
             raise ValueError("Only DQN variants are supported at this point (NEC as the trained agent is not served)")
         if not isinstance(self.agent_params.memory, EpisodicExperienceReplayParameters):
             raise ValueError("Only Episodic memories are supported in Batch RL")
         rank = self.dist.rank if self.dist is not None else 0
         ap = self.agent_params
+        if from_file and not self.is_collecting_random_dataset:
+            # the file fills the TRAINED agent's memory, so the split ratio the constructor handed to the collecting
+            # agent's memory belongs there (the reference leaves it at 1, and then has no evaluation set)
+            ap.memory.train_to_eval_ratio = self.experience_generating_agent_params.memory.train_to_eval_ratio
         ap.is_batch_rl_training = True
         if 'reward_model' not in ap.network_wrappers:
             ap.network_wrappers['reward_model'] = deepcopy(ap.network_wrappers['main'])
@@ -70,10 +89,14 @@ class BatchRLGraphManager(BasicRLGraphManager):
             if not self.is_collecting_random_dataset:
                 self.experience_generating_agent_params.network_wrappers['main'].should_get_softmax_probabilities = True
         resolve_reference_style(ap, self.env_params)
-        self.environment = dynamic_import(self.env_params.path)(self.env_params, self.device, rank=rank)
+        env_params = self.env_params
+        if env_params is None:
+            from ..environments.dataset_environment import DatasetEnvironmentParameters
+            env_params = DatasetEnvironmentParameters(self.spaces_definition)
+        self.environment = dynamic_import(env_params.path)(env_params, self.device, rank=rank)
         self.trained_agent = dynamic_import(ap.path)(ap, self.environment, self.device, dist=self.dist,
                                                      use_graphs=self.use_graphs)
-        if not self.is_collecting_random_dataset:
+        if not self.is_collecting_random_dataset and self.env_params is not None:
             gp = self.experience_generating_agent_params
             gp.input_filter = getattr(ap, "input_filter", None)                 # :133-134
             resolve_reference_style(gp, self.env_params)
@@ -85,7 +108,10 @@ class BatchRLGraphManager(BasicRLGraphManager):
     def improve(self, should_stop=None):                                        # :156-245
         self.verify_graph_was_created()
         trained = self.trained_agent
-        if self.is_collecting_random_dataset:
+        # with a dataset to load from, an environment is used for evaluating the policy only (:174-177)
+        if getattr(trained.ap.memory, "load_memory_from_file_path", None):
+            pass
+        elif self.is_collecting_random_dataset:
             self.heatup(self.schedule.heatup_steps)
         else:
             # the experience-generating agent's full improve() under its own schedule, then its memory changes hands
@@ -118,13 +144,26 @@ class BatchRLGraphManager(BasicRLGraphManager):
                 self.training_steps += trained.training_iteration - before
                 self.epochs += 1
             self._episodes_logged = self.epochs                                  # time is counted in epochs
+            if self.checkpoint_save_dir is not None:                            # :234-236
+                from ..checkpoint import save_checkpoint
+                save_checkpoint(trained, self.checkpoint_save_dir, self.epochs)
             if self.off_policy_evaluation:                                      # :239
                 self.ope_estimations.append(trained.run_off_policy_evaluation())
-            self.evaluate(self.schedule.evaluation_steps)
+            if self.env_params is not None:                                     # :241
+                self.evaluate(self.schedule.evaluation_steps)
+            else:
+                self.logger.write(**{"Episode #": self._episodes_logged, "Training Iter": trained.training_iteration,
+                                     "Epoch": 0, "In Heatup": 0, "Total steps": trained.total_steps_counter},
+                                  **self._evaluation_row_extras())
             if should_stop is not None and should_stop():
                 break
         self.check_status()
         return self.logger.rows
+
+    def run_preset_validation(self, *args, **kwargs):
+        if self.env_params is None:
+            raise ValueError("a preset's golden test needs evaluation rewards: this Batch RL graph has no environment")
+        return super().run_preset_validation(*args, **kwargs)
 
     def _evaluation_row_extras(self):
         if not self.off_policy_evaluation or not self.ope_estimations:

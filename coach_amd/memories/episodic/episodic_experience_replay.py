@@ -305,6 +305,105 @@ class EpisodicExperienceReplay(ExperienceReplay):
     def episode_lengths(self):
         return list(self._episodes)
 
+    # ------------------------------------------------------------------ Batch RL: a dataset from a file (:440-495)
+    def load_csv(self, csv_dataset, reward_filter=None, n_actions=None, n_step_returns=False):
+        """EpisodicExperienceReplay.load_csv: the file's episodes become the memory's contents.  The host parses the file
+        into flat tables once (csv_dataset.py), uploads them once, and one launch (rlx_dataset_ingest) writes the
+        transitions to physical rows 0 .. N - 1, which the listed-rows table names in order.
+        reward_filter: (rescale_factor, (clipping_low, clipping_high) or None) — the agent's reward filters, applied to the
+        fp32 reward by the arithmetic of rlx_reward_filter; None is no filter.
+        n_actions: A of the action space, for a memory without the action-probabilities column (one with it knows).
+        n_step_returns: n_step_discounted_rewards of the loaded rows is NaN unless this is set — no training path of the
+        Batch RL agents reads the column.  The off-policy evaluators do (weighted importance sampling reads every episode's
+        first row), so an agent that evaluates asks for it: one rlx_episode_nstep_returns launch per episode then fills the
+        column as the reference's store_episode does for an episode built by load_csv — Episode()'s own defaults, discount
+        0.99 and n_step -1, not the agent's — from the stored fp32 rewards.
+        Departures from the reference: the memory is left FROZEN (the reference freezes a few lines later, in improve());
+        a memory that already holds transitions refuses; a bad cell is a ValueError."""
+        self.assert_not_frozen()                                  # :447
+        from .csv_dataset import read_csv_dataset
+        if self.num_transitions() or self.open_transitions():
+            raise ValueError("load_csv fills an empty memory: this one holds {} transitions"
+                             .format(self.num_transitions() + self.open_transitions()))
+        if self.n_env != 1 or self.measurements is not None:
+            raise ValueError("load_csv serves a one-environment memory of observations, actions, rewards and action "
+                             "probabilities")
+        keeps = self.action_probabilities is not None
+        A = self.action_probabilities.shape[1] if keeps else n_actions
+        if A is None:
+            raise ValueError("load_csv into a memory without the action-probabilities column needs n_actions")
+        tables = read_csv_dataset(csv_dataset.filepath, int(A), keeps, observation_dim=self.obs_dim,
+                                  max_size=self.max_size)
+        N = tables.n_transitions
+        if N < 1:
+            raise ValueError("{}: no episode of at least 2 rows survives in the memory (max_size {})"
+                             .format(csv_dataset.filepath, self.max_size))
+        if N > self.rows:
+            raise ValueError("{}: {} transitions do not fit the memory's {} rows".format(csv_dataset.filepath, N, self.rows))
+        rescale, clip = (1.0, None) if reward_filter is None else reward_filter
+        lo, hi = clip if clip is not None else (0.0, 0.0)
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        features, action, reward = up(tables.features), up(tables.action), up(tables.reward)
+        probs = up(tables.probabilities) if tables.probabilities is not None else None
+        src, src_next, last = up(tables.src), up(tables.src_next), up(tables.last)
+        self.status.zero_()
+        self.lib.dataset_ingest(features, features.shape[1], action, reward, probs,
+                                probs.shape[1] if probs is not None else 0, tables.n_file_rows, self.obs_dim,
+                                int(A), src, src_next, last, N,
+                                int(bool(csv_dataset.is_episodic)), 0, self.rows, float(rescale), int(clip is not None),
+                                float(lo), float(hi), self.obs, self.next_obs, self.action, self.reward, self.game_over,
+                                self.action_probabilities, self.status, _rlx.current_stream())
+        self.n_step_discounted_rewards[:N].fill_(float("nan"))
+        bits = int(self.status.item())                            # (the sync also keeps the uploaded tables alive)
+        if bits:
+            self.status.zero_()
+            what = [text for bit, text in ((1, "an action outside the action space"),
+                                           (2, "a feature or reward that is not finite"),
+                                           (4, "a row index outside the file")) if bits & bit]
+            raise ValueError("{}: {} (status bits {})".format(csv_dataset.filepath, ", ".join(what), bits))
+        if N > self._order.size:
+            self._order = np.zeros(N, dtype=np.int64)
+        self._order[:N] = np.arange(N)
+        self._order_head, self._order_len = 0, N
+        self._episodes = deque(int(T) for T in tables.episode_lengths)
+        self._episode_first_step = deque(int(s) for s in np.cumsum([0] + list(tables.episode_lengths[:-1])))
+        self._gstep = N
+        self._ep_start[:] = N
+        if n_step_returns:                                        # Episode() of :468: discount 0.99, n_step -1
+            for first, T in zip(self._episode_first_step, self._episodes):
+                self.lib.episode_nstep_returns(self.reward, self.n_step_discounted_rewards, None, first, T, 0, 1,
+                                               self.rows, 0.99, -1, _rlx.current_stream())
+        self.freeze()
+        return tables
+
+    def save_csv(self, path):
+        """the complete episodes, in logical order, in the schema load_csv reads (csv_dataset.py): an episode of T
+        transitions gives T + 1 rows, the last one carrying the final next state (action 0, reward 0, uniform
+        probabilities); a memory without the action-probabilities column writes no such column.  The rewards written are the STORED
+        ones: they have been through the agent's reward filters already, so a file written here is loaded without one.
+        Every float is written with repr(float(x)), so the fp32 values survive the round trip exactly."""
+        from .csv_dataset import write_csv_dataset
+        n = self.num_transitions_in_complete_episodes()
+        cols = {k: [] for k in ("obs", "next_obs", "action", "reward", "probabilities")}
+        chunk = 4096
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)
+            b = self.gather(self.physical_rows(np.arange(i, i + m)), m)
+            cols["obs"].append(b["state"].cpu().numpy().copy())
+            cols["next_obs"].append(b["next_state"].cpu().numpy().copy())
+            cols["action"].append(b["action"].cpu().numpy().copy())
+            cols["reward"].append(b["reward"].cpu().numpy().copy())
+            if self.action_probabilities is not None:
+                cols["probabilities"].append(b["action_probabilities"].cpu().numpy().copy())
+        host = {k: (np.concatenate(v) if v else None) for k, v in cols.items()}
+        episodes, first = [], 0
+        for T in self._episodes:
+            episodes.append({k: (None if v is None else v[first:first + T]) for k, v in host.items()})
+            first += T
+        write_csv_dataset(path, episodes,
+                          self.action_probabilities.shape[1] if self.action_probabilities is not None else None)
+
     # ------------------------------------------------------------------ Batch RL: a frozen dataset (:167-187, :497-546)
     def freeze(self):
         """no new transitions from here on: the memory is a dataset (batch-rl)"""

@@ -13,6 +13,7 @@ class MemoryGranularity(enum.Enum):
 class MemoryParameters(object):
     """Parameter holder resolved through `path`, like every rl_coach Parameters object."""
     max_size = None
+    load_memory_from_file_path = None        # a core_types.CsvDataset: the agent's memory starts as that file (memory.py:34)
 
     @property
     def path(self):

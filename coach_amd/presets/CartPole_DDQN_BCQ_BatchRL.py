@@ -11,14 +11,16 @@ reward-model epochs (lr 1e-4, no L2), greedy evaluation over 10 episodes after e
 sets for its off-policy evaluators: softmax_temperature = 0.2 on the `main` and `reward_model` wrappers, and the graph
 manager's switch (IPS, DM, DR, sequential DR and WIS after every epoch, in that epoch's CSV row).  It is off by default:
 the module-level graph_manager is the experiment as it was.  The reference preset's imitation-model wrapper stays out of
-scope and is not set.
+scope and is not set.  make(dataset=path) trains on a logged CSV file instead of collecting (there is no
+collecting agent then, and the environment only evaluates); with_environment=False runs without a simulator at all, from
+the spaces definition of CartPole: the epochs' rows then carry the off-policy estimates and no evaluation reward.
 """
 from copy import deepcopy
 
 from coach_amd.agents.ddqn_bcq_agent import DDQNBCQAgentParameters, KNNParameters
 from coach_amd.agents.dqn_agent import DQNAgentParameters
 from coach_amd.base_parameters import PresetValidationParameters, VisualizationParameters
-from coach_amd.core_types import EnvironmentEpisodes, EnvironmentSteps, TrainingSteps
+from coach_amd.core_types import CsvDataset, EnvironmentEpisodes, EnvironmentSteps, TrainingSteps
 from coach_amd.environments.cartpole_vector_environment import CartPoleVectorEnvironmentParameters
 from coach_amd.filters.filter import InputFilter
 from coach_amd.filters.reward import RewardRescaleFilter
@@ -27,15 +29,18 @@ from coach_amd.graph_managers.graph_manager import ScheduleParameters
 from coach_amd.memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
 from coach_amd.memories.memory import MemoryGranularity
 from coach_amd.schedules import LinearSchedule
+from coach_amd.spaces import DiscreteActionSpace, ObservationSpace, SpacesDefinition, StateSpace
 
 DATASET_SIZE = 10000
 
 
 def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, reward_model_num_epochs=30,
          improve_epochs=10000000000, batch_size=128, evaluation_episodes=10, train_to_eval_ratio=0.4,
-         off_policy_evaluation=False):
+         off_policy_evaluation=False, dataset=None, with_environment=True):
     """seed: the environment's reset-state streams; agent_seed: both agents' host generators and initial weights;
-    off_policy_evaluation: the five off-policy estimates after every epoch (softmax_temperature 0.2)"""
+    off_policy_evaluation: the five off-policy estimates after every epoch (softmax_temperature 0.2);
+    dataset: the path of a CSV file of logged transitions (core_types.CsvDataset) the trained agent's memory starts as;
+    with_environment: False — no simulator (needs a dataset)"""
     sched = ScheduleParameters()
     sched.improve_steps = TrainingSteps(improve_epochs)
     sched.steps_between_evaluation_periods = TrainingSteps(1)
@@ -61,6 +66,8 @@ def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, 
         main.softmax_temperature = 0.2
         agent.network_wrappers['reward_model'].softmax_temperature = 0.2
     agent.memory = EpisodicExperienceReplayParameters()
+    if dataset is not None:
+        agent.memory.load_memory_from_file_path = CsvDataset(dataset)
     agent.exploration.epsilon_schedule = LinearSchedule(0, 0, 10000)
     agent.exploration.evaluation_epsilon = 0
 
@@ -80,14 +87,18 @@ def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, 
     gen.memory.max_size = (MemoryGranularity.Transitions, dataset_size)
     gen.exploration.epsilon_schedule = LinearSchedule(1.0, 0.01, 10000)
 
-    env = CartPoleVectorEnvironmentParameters(1, "CartPole-v0", seed=seed)
+    env = CartPoleVectorEnvironmentParameters(1, "CartPole-v0", seed=seed) if with_environment else None
+    spaces = None if with_environment else SpacesDefinition(
+        state=StateSpace({'observation': ObservationSpace(4)}), goal=None, action=DiscreteActionSpace(2))
     validation = PresetValidationParameters(test=True, min_reward_threshold=150, max_episodes_to_achieve_reward=50,
                                             read_csv_tries=500)
+    if dataset is not None:                  # nothing is collected: the file is the dataset
+        gen = gen_sched = None
     manager = BatchRLGraphManager(agent_params=agent, experience_generating_agent_params=gen,
                                   experience_generating_schedule_params=gen_sched, env_params=env, schedule_params=sched,
                                   vis_params=VisualizationParameters(dump_signals_to_csv_every_x_episodes=1),
                                   preset_validation_params=validation, reward_model_num_epochs=reward_model_num_epochs,
-                                  train_to_eval_ratio=train_to_eval_ratio)
+                                  train_to_eval_ratio=train_to_eval_ratio, spaces_definition=spaces)
     if off_policy_evaluation:
         manager.off_policy_evaluation = True
     return manager

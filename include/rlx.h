@@ -1735,6 +1735,31 @@ int rlx_ope_reduce(const int *episode_offsets, int n_episodes, long long n_rows,
                    const float *rewards, const double *returns, double discount, double *episode_columns, double *out,
                    void *stream);
 
+/* ------------------------------------------------- Batch RL: a logged dataset becomes replay rows -- */
+/* (csrc/dataset.hip; bit-exact numpy twin: tests/dataset_ref.py.  An entry point ADDED under ABI version 11.)
+ *
+ * The device half of EpisodicExperienceReplay.load_csv (memories/episodic/episodic_experience_replay.py:440-495).  The
+ * file's rows arrive as flat tables — features fp64 [n_rows][ld_features] (D used), actions int32 [n_rows], rewards fp64
+ * [n_rows], probabilities fp32 [n_rows][ld_probabilities] (A used) or NULL — and transition t of n_transitions takes its
+ * state, action, reward and probabilities from file row src[t], its next state from file row src_next[t].  It is written
+ * to row first_row + t of the memory's columns (mem_obs / mem_next_obs fp32 [mem_rows][D], mem_action int32, mem_reward
+ * fp32, mem_game_over u8, mem_probabilities fp32 [mem_rows][A] or NULL — NULL exactly when probabilities is):
+ *   obs, next_obs   (float)feature: rounded to fp32 once, to nearest even
+ *   reward          (float)reward, then rlx_reward_filter's arithmetic on that fp32 value (rescale_factor, has_clip,
+ *                   clipping_low, clipping_high as there: a bound of 0 is not applied)
+ *   game_over       last[t] != 0 && is_episodic
+ * status bits (rows that raise one are still written): 1 an action outside [0, A) (stored as 0); 2 a feature or a reward
+ * that is not finite as fp32; 4 a src / src_next outside [0, n_rows) (the cells it would have read are written as 0).
+ * 1 <= D <= 4096, 1 <= A <= 18, n_transitions >= 1, 0 <= first_row, first_row + n_transitions <= mem_rows,
+ * ld_features >= D, ld_probabilities >= A, n_rows < 2^31. */
+int rlx_dataset_ingest(const double *features, long long ld_features, const int *actions, const double *rewards,
+                       const float *probabilities, long long ld_probabilities, long long n_rows, int D, int A,
+                       const int *src, const int *src_next, const unsigned char *last, long long n_transitions,
+                       int is_episodic, long long first_row, long long mem_rows, double rescale_factor, int has_clip,
+                       double clipping_low, double clipping_high, float *mem_obs, float *mem_next_obs, int *mem_action,
+                       float *mem_reward, unsigned char *mem_game_over, float *mem_probabilities, int *status,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
