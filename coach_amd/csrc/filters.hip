@@ -82,7 +82,7 @@ __global__ void running_stats_push_kernel(const T *__restrict__ samples, long lo
     sum[j] = new_sum;
     sumsq[j] = new_sq;
     mean[j] = m;
-    stdv[j] = sqrt(fmax(var, epsilon));
+    stdv[j] = sqrt(var < epsilon ? epsilon : var);     // np.maximum(var, epsilon): a NaN variance stays NaN
 }
 
 __global__ void running_stats_count_kernel(double *count, double n) { *count += n; }
@@ -102,7 +102,7 @@ __global__ void running_stats_merge_kernel(const double *__restrict__ delta, int
         sum[j] = new_sum;
         sumsq[j] = new_sq;
         mean[j] = m;
-        stdv[j] = sqrt(fmax(var, epsilon));
+        stdv[j] = sqrt(var < epsilon ? epsilon : var);   // np.maximum: a NaN variance stays NaN
     }
     if (threadIdx.x == 0) *count = cnt;
 }
@@ -117,7 +117,8 @@ __global__ void running_stats_normalize_kernel(const T *__restrict__ x, long lon
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
         const int j = (int)(t % dim);
         double v = ((double)x[t] - mean[j]) / (stdv[j] + 1e-15);             // (:163)
-        v = fmin(fmax(v, clip_lo), clip_hi);                                 // np.clip (:164)
+        v = v < clip_lo ? clip_lo : v;                                       // np.clip (:164): minimum(maximum(v, lo),
+        v = v > clip_hi ? clip_hi : v;                                       // hi), which keeps a NaN
         if (out32) out32[t] = (float)v;
         if (out64) out64[t] = v;
     }

@@ -19,6 +19,7 @@
 // Compiled with -ffp-contract=off (see Makefile).
 #include "rlx_common.hpp"
 #include "episode_returns.hpp"
+#include "reward_filter.hpp"
 
 namespace {
 
@@ -279,10 +280,7 @@ __device__ __forceinline__ void observe_copy_rows(const unsigned char *__restric
 // observations through their own copy).  Uses ObserveArgs with dst_rows = null and the column pointers already at row0.
 __global__ void __launch_bounds__(1024) rollout_observe_kernel(const ObserveArgs a) {
     for (int e = threadIdx.x; e < a.n_env; e += blockDim.x) {
-        double r = (double)a.reward_in[e] * a.rescale;
-        if (a.use_hi) r = fmin(r, a.hi);
-        if (a.use_lo) r = fmax(r, a.lo);
-        a.reward_out[e] = (float)r;
+        a.reward_out[e] = rlx::reward_filter_value(a.reward_in[e], a.rescale, a.use_hi, a.hi, a.use_lo, a.lo);
     }
     __syncthreads();
     episode_stats_body(a.reward_out, a.done, a.ep_return, a.ep_len, a.n_env, a.acc, a.last_return, a.last_len);
@@ -294,10 +292,7 @@ __global__ void __launch_bounds__(1024) rollout_observe_kernel(const ObserveArgs
 
 __global__ void __launch_bounds__(1024) observe_step_kernel(const ObserveArgs a) {
     for (int e = threadIdx.x; e < a.n_env; e += blockDim.x) {
-        double r = (double)a.reward_in[e] * a.rescale;
-        if (a.use_hi) r = fmin(r, a.hi);
-        if (a.use_lo) r = fmax(r, a.lo);
-        a.reward_out[e] = (float)r;
+        a.reward_out[e] = rlx::reward_filter_value(a.reward_in[e], a.rescale, a.use_hi, a.hi, a.use_lo, a.lo);
     }
     __syncthreads();
     episode_stats_body(a.reward_out, a.done, a.ep_return, a.ep_len, a.n_env, a.acc, a.last_return, a.last_len);

@@ -29,9 +29,9 @@ class FakeAtariEmulator(object):
     """Deterministic stand-in for an ALE game: frames are a hash of (seed, episode, frame index), a life is lost every
     `life_every` frames, the game is over when no lives are left (or after `game_len` frames)."""
 
-    def __init__(self, seed, shape=(210, 160, 3), lives=3, life_every=37, game_len=400, n_actions=4):
+    def __init__(self, seed, shape=(210, 160, 3), lives=3, life_every=37, game_len=400, n_actions=4, meanings=None):
         self.seed, self.shape, self.n_lives, self.life_every, self.game_len = seed, shape, lives, life_every, game_len
-        self.n_actions = n_actions
+        self.n_actions, self.meanings = n_actions, meanings
         self.episode, self.t, self._lives = -1, 0, 0
 
     def _frame(self):
@@ -39,6 +39,8 @@ class FakeAtariEmulator(object):
         return rng.randint(0, 256, size=self.shape, dtype=np.uint8)
 
     def action_meanings(self):
+        if self.meanings is not None:                   # e.g. a game whose action 1 is not FIRE
+            return list(self.meanings)
         return ['NOOP', 'FIRE', 'RIGHT', 'LEFT'][:self.n_actions]
 
     def lives(self):
@@ -159,8 +161,10 @@ class EmulatorVectorEnvironment(object):
         self.dev_raw = torch.empty_like(self.host, device=device)
         self.maxed = torch.empty((2, self.n) + raw, dtype=torch.uint8, device=device)
         oh, ow = params.observation_shape
-        self.small = torch.empty((2, self.n, oh, ow, raw[2]), dtype=torch.uint8, device=device)
-        self.frames = torch.empty((2, self.n, oh, ow), dtype=torch.uint8, device=device)
+        # one allocation per half (next | reset): rlx_rgb_to_y_u8 reads and writes words, and the second half of one
+        # buffer would start at n * oh * ow bytes, which is 4-byte aligned at 84 x 84 but not at every size
+        self.small = [torch.empty((self.n, oh, ow, raw[2]), dtype=torch.uint8, device=device) for _ in range(2)]
+        self.frames = [torch.empty((self.n, oh, ow), dtype=torch.uint8, device=device) for _ in range(2)]
         self.obs = self.frames[0]                       # after reset_internal_state: the first observations
         self.next_obs, self.reset_obs = self.frames[0], self.frames[1]
         self.reward = torch.zeros(self.n, dtype=torch.float32, device=device)

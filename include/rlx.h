@@ -399,6 +399,12 @@ int rlx_resize_bilinear_u8(const unsigned char *in, unsigned char *out, int n, i
 int rlx_max_over_frames_u8(const unsigned char *frames, unsigned char *out, int n_env, int n_frames,
                            long long frame_bytes,
                            void *stream);   /* environments/gym_environment.py:148-175: np.max over the newest frames of a frame-skip step */
+/* NaN in the running statistics and the reward filter follows numpy / Python, like rlx_clip_by_value: a NaN stays a NaN.
+ * rlx_running_stats_push / _merge: np.sqrt(np.maximum(var, epsilon)) — a column that has seen a NaN has NaN sums, mean
+ * and std, the other columns are untouched.  rlx_running_stats_normalize: np.clip keeps a NaN input (and a NaN mean or
+ * std) NaN in out32 and out64.  rlx_reward_filter, and the same filter inside rlx_observe_step, rlx_rollout_observe_step
+ * and rlx_dataset_ingest: min(r, high) / max(r, low) take the bound only where the comparison holds, so a NaN reward is
+ * stored as NaN, never as a clipping bound; +-inf clips like any other value. */
 int rlx_running_stats_push(const void *samples, int samples_are_f64, long long n, int dim,
                            double *sum, double *sum_squares, double *count, double *mean,
                            double *std, double epsilon,

@@ -6,8 +6,12 @@ Follows rl_coach/environments/gym_environment.py:
   GymEnvironment._restart_environment_episode (:459-474) continue after a lost life, else reset; random no-ops, fire
   GymEnvironment._random_noop / _press_fire (:440-457)
 and Environment.step / reset_internal_state (environment.py:276-327,340-372).
-parity unpinned against gym / ALE themselves (not installable here): pinned to the wrapper code above by reading;
-the emulator behind it is any object with reset() / step(a) / lives() / action_meanings()."""
+Pinned to that code itself: tests/golden/frontend.npz holds traces of the reference's GymEnvironment and wrapper run over
+FakeAtariEmulator (tests/golden/make_golden_frontend.py: both phases, skip 4 / max 2, skip 3 / max 3, max over 1, 30 and
+0 no-op steps, no FIRE action, a time limit inside a skip), and tests/test_frontend_reference.py holds this class to every
+frame, reward, done flag, reset frame and host draw of them.  gym / ALE themselves stay unpinned (not installable here;
+the generator restates gym's Wrapper and TimeLimit).  The emulator behind it is any object with reset() / step(a) /
+lives() / action_meanings()."""
 import random
 
 import numpy as np

@@ -25,7 +25,11 @@ def test_oracle_rgb_to_y_uint8_matches_reference(golden):
 
 @pytest.mark.parametrize("H,W,C,out", [(210, 160, None, (84, 84)), (210, 160, 3, (84, 84)), (96, 96, None, (84, 84)),
                                        (50, 70, None, (84, 84)), (84, 84, None, (84, 84)), (480, 640, 3, (84, 84)),
-                                       (33, 47, None, (61, 29)), (250, 160, 1, (84, 84)), (1, 9, None, (3, 4))])
+                                       (33, 47, None, (61, 29)), (250, 160, 1, (84, 84)), (1, 9, None, (3, 4)),
+                                       # the geometries of the direct kernel test (tests/test_frontend_kernels.py)
+                                       (1, 1, 1, (1, 1)), (1, 1, 1, (3, 2)), (2, 2, 3, (7, 5)), (5, 7, 4, (5, 7)),
+                                       (2, 3, 1, (84, 84)), (1, 16, 3, (4, 4)), (33, 47, 2, (61, 29)),
+                                       (9, 1, 1, (4, 3)), (20, 30, 3, (84, 84))])
 def test_oracle_resize_equals_scipy_zoom_bit_for_bit(H, W, C, out):
     """ObservationRescaleToSizeFilter's skimage.transform.resize(obs, shape, anti_aliasing=False, preserve_range=True)
     (observation_rescale_to_size_filter.py:62-79; order 1, mode 'reflect').  scikit-image (>= 0.19) executes exactly
