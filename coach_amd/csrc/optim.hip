@@ -458,6 +458,7 @@ int rlx_adam_tf1_step(float *weights, const float *grads, float *m, float *v, lo
     RLX_REQUIRE(!norm_out || workspace, "rlx_adam_tf1_step: the gradient norm needs a workspace");
     RLX_REQUIRE(n_acc == 0 || (acc_src && acc_dst && n_acc > 0 && n_acc <= 64),
                 "rlx_adam_tf1_step: bad signal accumulation arguments");
+    RLX_REQUIRE(n_acc == 0 || norm_out, "rlx_adam_tf1_step: signal sums ride with the norm finish (give norm_out)");
     RLX_REQUIRE((((uintptr_t)weights | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v | (uintptr_t)target) & 15) == 0,
                 "rlx_adam_tf1_step: buffers must be 16-byte aligned");
     int blocks = rlx::grid_for(n / 4 + 1, kBlock, 1024);
@@ -500,8 +501,6 @@ int rlx_adam_tf1_step(float *weights, const float *grads, float *m, float *v, lo
         RLX_LAUNCH((adam_finish_norm_kernel), 1, kBlock, 0, s, state, beta1, beta2, workspace, blocks, norm_out, acc_src,
                                                      acc_dst, n_acc);
         RLX_LAUNCH_CHECK();
-    } else if (n_acc > 0) {
-        RLX_REQUIRE(false, "rlx_adam_tf1_step: signal sums ride with the norm finish (give norm_out)");
     }
     return RLX_OK;
 }

@@ -27,15 +27,28 @@ constexpr int kScanBlock = 256;
 constexpr int kItems = 4;
 constexpr int kTile = kScanBlock * kItems;
 
+// `cut`: the map holds a game_over and ignores its argument.  a == 0 alone does not say so: 0 * inf is NaN, and with it a
+// non-finite reward or value of a LATER episode would reach every earlier step, where the reference, which works through
+// one episode at a time, never looks past the episode's end.  A cut map takes 0.0 for whatever follows it, as the reference
+// starts an episode's recurrence from 0.0.  A discount of 0 is not a cut: there the reference itself computes
+// r + 0 * inf = NaN inside an episode, and so does this kernel.  For a finite x, b + 0 * x and b + 0.0 are the same bits
+// (unless b is -0.0 and x negative: the reference's start from 0.0 gives +0.0 there, as the flag does), so nothing changes
+// for finite inputs.
 struct Affine {
     double a, b;   // x -> b + a * x
+    int cut;
 };
+
+__device__ __forceinline__ double apply(const Affine f, const double x) {
+    return f.cut ? f.b + 0.0 : f.b + f.a * x;
+}
 
 // later ∘ earlier  (apply `earlier` first)
 __device__ __forceinline__ Affine compose(const Affine later, const Affine earlier) {
     Affine r;
     r.a = later.a * earlier.a;
-    r.b = later.b + later.a * earlier.b;
+    r.b = apply(later, earlier.b);
+    r.cut = later.cut | earlier.cut;
     return r;
 }
 
@@ -44,8 +57,9 @@ __device__ __forceinline__ Affine wave_inclusive_scan(Affine v, int lane) {
     for (int d = 1; d < 64; d <<= 1) {
         double pa = __shfl_up(v.a, d, 64);
         double pb = __shfl_up(v.b, d, 64);
+        int pc = __shfl_up(v.cut, d, 64);
         if (lane >= d) {
-            Affine e{pa, pb};
+            Affine e{pa, pb, pc};
             v = compose(v, e);
         }
     }
@@ -76,11 +90,11 @@ reverse_scan_kernel(const float *__restrict__ rewards, const float *__restrict__
 
     for (long long tile0 = 0; tile0 < seq_len; tile0 += kTile) {
         Affine el[kItems];
-        Affine local{1.0, 0.0};
+        Affine local{1.0, 0.0, 0};
 #pragma unroll
         for (int k = 0; k < kItems; ++k) {
             const long long j = tile0 + (long long)tid * kItems + k;
-            Affine f{1.0, 0.0};                       // identity for the padding past the end
+            Affine f{1.0, 0.0, 0};                     // identity for the padding past the end
             if (j < seq_len) {
                 const long long t = seq_len - 1 - j;
                 const bool done = dones[t] != 0;
@@ -95,6 +109,7 @@ reverse_scan_kernel(const float *__restrict__ rewards, const float *__restrict__
                     f.b = r;
                 }
                 f.a = done ? 0.0 : coef;
+                f.cut = done;
             }
             el[k] = f;
             local = compose(f, local);
@@ -103,19 +118,20 @@ reverse_scan_kernel(const float *__restrict__ rewards, const float *__restrict__
         Affine incl = wave_inclusive_scan(local, lane);
         if (lane == 63) wave_tot[wid] = incl;
         __syncthreads();
-        Affine prefix{1.0, 0.0};                       // everything before this thread in the tile
+        Affine prefix{1.0, 0.0, 0};                    // everything before this thread in the tile
         for (int w = 0; w < wid; ++w) prefix = compose(wave_tot[w], prefix);
         {
             double pa = __shfl_up(incl.a, 1, 64), pb = __shfl_up(incl.b, 1, 64);
-            if (lane > 0) prefix = compose(Affine{pa, pb}, prefix);
+            int pc = __shfl_up(incl.cut, 1, 64);
+            if (lane > 0) prefix = compose(Affine{pa, pb, pc}, prefix);
         }
         const double carry = carry_s;                  // value at the element just before the tile
-        double x = prefix.b + prefix.a * carry;
+        double x = apply(prefix, carry);
 #pragma unroll
         for (int k = 0; k < kItems; ++k) {
             const long long j = tile0 + (long long)tid * kItems + k;
             if (j < seq_len) {
-                x = el[k].b + el[k].a * x;
+                x = apply(el[k], x);
                 const long long t = seq_len - 1 - j;
                 out64[t] = x;
                 if (out32) out32[t] = (float)(mode == 0 ? x + (double)values[t] : x);

@@ -266,7 +266,12 @@ int rlx_imgreplay_gather_columns(const unsigned char *ring, const int *t_fpos, c
 
 /* ------------------------------------- returns / GAE / episode stats (K8 / K12) -- */
 /* n_seq independent trajectories of seq_len steps, contiguous; game_overs cut episodes inside a
- * trajectory.  fp64 arithmetic like the reference; `values` are V(s_t) as predicted (fp32). */
+ * trajectory.  fp64 arithmetic like the reference; `values` are V(s_t) as predicted (fp32).
+ * Isolation rule: an episode is computed from its own steps only, as in the reference, which takes one episode at a
+ * time.  Nothing behind a game_over reaches the steps before it: a reward or value of +-inf / NaN makes the outputs of
+ * ITS episode non-finite (from that step back to the episode's first step) and of no other; bootstrap_values[q] is read
+ * only where trajectory q ends without a game_over.  A discount of 0 is not a game_over: inside an episode r + 0 * inf is
+ * NaN here as it is in the reference. */
 int rlx_gae(const float *rewards, const float *values, const unsigned char *game_overs,
             const float *bootstrap_values, int n_seq, long long seq_len, double discount,
             double gae_lambda, double *advantages, float *value_targets,

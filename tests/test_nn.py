@@ -296,8 +296,9 @@ def test_hip_adam_mix_norm_vs_oracle(rlx, dev):
     for step in range(4):
         rlx.adam_tf1(wd, gd, m, v, n, 3e-4, 0.9, 0.999, 1e-5, st, 0.5, 0)
         opt.step(wo, g, 0.5)
-    np.testing.assert_allclose(wd.cpu().numpy(), wo, rtol=1e-5, atol=1e-7)
-    np.testing.assert_allclose(st.cpu().numpy(), [opt.b1p, opt.b2p], rtol=1e-6)
+    # optim.hip is built without contraction: the oracle's fp32 operations one for one (tests/test_optim_kernels.py)
+    for got, want in ((wd, wo), (m, opt.m), (v, opt.v), (st, np.array([opt.b1p, opt.b2p], dtype=np.float32))):
+        assert np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32))
     norm = torch.empty(1, dtype=torch.float32, device=dev)
     ws = torch.empty(4096, dtype=torch.float32, device=dev)
     rlx.global_norm(gd, n, norm, ws, 4096, 0)
