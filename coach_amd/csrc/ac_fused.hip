@@ -206,9 +206,9 @@ __global__ void __launch_bounds__(T) td3_forward2_kernel(const Td3Dev p) {
                 for (int q = 1; q < kSplit; ++q) z += zp[(size_t)q * A];
                 const float mu = p.actor_scale * tanhf(z + p.awt[am.o_b3 + col]);
                 if (p.noise) {
-                    const double nz = fmin(fmax(p.noise[(size_t)i * A + col], -p.noise_clip), p.noise_clip);
+                    const double nz = rlx::np_clip(p.noise[(size_t)i * A + col], -p.noise_clip, p.noise_clip);
                     double xv = (double)mu + nz;
-                    xv = fmin(fmax(xv, (double)p.low[col]), (double)p.high[col]);          // spaces.py:379 np.clip
+                    xv = rlx::np_clip(xv, (double)p.low[col], (double)p.high[col]);        // spaces.py:379 np.clip
                     v = (float)xv;
                 } else {
                     v = mu;
@@ -265,9 +265,9 @@ __global__ void __launch_bounds__(T) td3_critic_backward_kernel(const Td3Dev p) 
             const float qn = qt[0] <= qt[1] ? qt[0] : qt[1];                      // output #2: min over the streams (:168)
             const double qd = (double)qn;
             double t;
-            if (p.nonzero_terminal) t = (double)p.rewards[i] + p.discount * qd;
+            if (p.nonzero_terminal) t = (double)p.rewards[i] + (double)((float)p.discount * qn);   // fp32 product (:173)
             else t = (double)p.rewards[i] + (1.0 - (p.dones[i] ? 1.0 : 0.0)) * p.discount * qd;     // :171-180
-            if (p.has_clip) t = fmin(fmax(t, p.clip_lo), p.clip_hi);
+            if (p.has_clip) t = rlx::np_clip(t, p.clip_lo, p.clip_hi);
             const float y = (float)t;
             if (s == 0 && c == 0) {
                 p.td_targets[i] = y;

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(kBootThreads) bootstrapped_dqn_head_loss_kerne
         int best = 0;
         float bv = qs[0];
         for (int k = 1; k < A; ++k)
-            if (qs[k] > bv) { bv = qs[k]; best = k; }            // np.argmax: first maximum
+            rlx::np_argmax_step(qs[k], k, bv, best);             // np.argmax: first maximum, first NaN
         float term = 0.f, g = 0.f, tdt = 0.f;
         if (valid) {
             const float qa = q_s[h * P + act];

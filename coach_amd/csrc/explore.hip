@@ -119,7 +119,7 @@ __global__ void gaussian_action_kernel(const float *__restrict__ mean, const flo
     const int a = t % act_dim;
     const double sd = std_full ? (double)std_full[t] : (double)std_dim[a];
     double v = (double)mean[t] + sd * z[t];
-    if (low) v = fmin(fmax(v, (double)low[a]), (double)high[a]);
+    if (low) v = rlx::np_clip(v, (double)low[a], (double)high[a]);      // np.clip: a NaN stays NaN
     out[t] = (float)v;
 }
 

@@ -87,7 +87,7 @@ __device__ __forceinline__ long long batch_off(int batch, int inner, long long s
 }
 
 __device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == RLX_ACT_RELU) return v <= 0.f ? 0.f : v;       // np.maximum(v, 0): a NaN stays NaN (v > 0 ? v : 0 made it 0)
     if (act == RLX_ACT_TANH) return tanhf(v);
     return v;
 }

@@ -125,10 +125,10 @@ __global__ void __launch_bounds__(kMaxBlock) ac_critic_losses_kernel(const AcCri
         const double q = (double)qn;
         double t;
         if (a.nonzero_terminal_discount)
-            t = (double)a.rewards[i] + a.discount * q;
+            t = (double)a.rewards[i] + (double)((float)a.discount * qn);     // an fp32 product: see ac_targets_kernel
         else
             t = (double)a.rewards[i] + (1.0 - (a.dones[i] ? 1.0 : 0.0)) * a.discount * q;
-        if (a.has_clip) t = fmin(fmax(t, a.clip_lo), a.clip_hi);
+        if (a.has_clip) t = rlx::np_clip(t, a.clip_lo, a.clip_hi);
         const float y = (float)t;
         y_s[i] = y;
         a.td_targets[i] = y;

@@ -314,7 +314,7 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
             int best = 0;
             float bv = q_sel[0];
             for (int a = 1; a < A; ++a)
-                if (q_sel[a] > bv) { bv = q_sel[a]; best = a; }
+                rlx::np_argmax_step(q_sel[a], a, bv, best);
             const int act = p.actions[b];
             if (act < 0 || act >= A) {
                 atomicOr(p.status, 1);

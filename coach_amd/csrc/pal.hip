@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(1024) mixed_target_head_loss_kernel(const Mixe
         int best = 0;
         float bv = qs[0], vn = qn[0];
         for (int k = 1; k < A; ++k) {
-            if (qs[k] > bv) { bv = qs[k]; best = k; }             // np.argmax: first maximum
+            rlx::np_argmax_step(qs[k], k, bv, best);              // np.argmax: first maximum, first NaN
             vn = fmaxf(vn, qn[k]);                                // np.max of the target's values on s'
         }
         const int act = a.actions[i];

@@ -52,6 +52,23 @@ inline void launch(const char *name, F kernel, dim3 grid, dim3 block, unsigned s
         kernel<<<grid, block, shmem, s>>>(args...);
     }
 }
+
+// np.clip(x, lo, hi) = np.minimum(np.maximum(x, lo), hi) as numpy evaluates it: x is kept where it is a NaN or strictly
+// inside the bound, the bound is taken otherwise -- a NaN x stays NaN (fmin / fmax return the bound and hide a diverged
+// network behind a legal value) and a NaN bound comes through.  x inside [lo, hi] keeps its bits.
+__device__ __forceinline__ double np_clip(double x, double lo, double hi) {
+    x = (x > lo || x != x) ? x : lo;
+    return (x < hi || x != x) ? x : hi;
+}
+
+// One step of np.argmax over a row: the FIRST maximum wins and a NaN counts as the maximum, so the first NaN of a row
+// wins and nothing after it is looked at (argmax_rows_kernel, explore.hip).  bv / best: the running maximum and its index.
+__device__ __forceinline__ void np_argmax_step(float v, int a, float &bv, int &best) {
+    if (bv == bv && (v > bv || v != v)) {
+        bv = v;
+        best = a;
+    }
+}
 }  // namespace rlx
 
 #define RLX_REQUIRE(cond, ...)                      \

@@ -40,7 +40,7 @@ constexpr int kTileFloats = kMaxWidth * kTilePitch;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == RLX_ACT_RELU) return v <= 0.f ? 0.f : v;       // np.maximum(v, 0): a NaN stays NaN (v > 0 ? v : 0 made it 0)
     if (act == RLX_ACT_TANH) return tanhf(v);
     return v;
 }

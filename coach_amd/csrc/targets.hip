@@ -20,7 +20,7 @@ namespace {
 constexpr int kBlock = 256;
 
 // One thread per sample.  q_sel selects the greedy action (target net for DQN, online net for
-// DDQN); np.argmax returns the FIRST maximum.
+// DDQN); np.argmax returns the FIRST maximum, and a NaN counts as the maximum (rlx::np_argmax_step).
 __global__ void dqn_targets_kernel(const float *__restrict__ q_next, const float *__restrict__ q_sel,
                                    float *__restrict__ td_targets, const int *__restrict__ actions,
                                    const float *__restrict__ rewards,
@@ -32,13 +32,7 @@ __global__ void dqn_targets_kernel(const float *__restrict__ q_next, const float
     const float *qs = q_sel + (size_t)i * n_actions;
     int best = 0;
     float bv = qs[0];
-    for (int a = 1; a < n_actions; ++a) {
-        float v = qs[a];
-        if (v > bv) {
-            bv = v;
-            best = a;
-        }
-    }
+    for (int a = 1; a < n_actions; ++a) rlx::np_argmax_step(qs[a], a, bv, best);
     const int act = actions[i];
     if (act < 0 || act >= n_actions) {
         atomicOr(status, 1);
@@ -75,7 +69,7 @@ dqn_head_loss_kernel(const float *__restrict__ q, long long ld_q, const float *_
         int best = 0;
         float bv = qs[0];
         for (int a = 1; a < n_actions; ++a)
-            if (qs[a] > bv) { bv = qs[a]; best = a; }            // np.argmax: first maximum
+            rlx::np_argmax_step(qs[a], a, bv, best);             // np.argmax: first maximum, first NaN
         const int act = actions[i];
         if (act < 0 || act >= n_actions) {
             atomicOr(status, 1);
@@ -143,7 +137,7 @@ __global__ void __launch_bounds__(256) dqn_head_loss_bwd_kernel(const DqnHeadBwd
             int best = 0;
             float bv = qs[0];
             for (int k = 1; k < A; ++k)
-                if (qs[k] > bv) { bv = qs[k]; best = k; }              // np.argmax: first maximum
+                rlx::np_argmax_step(qs[k], k, bv, best);               // np.argmax: first maximum, first NaN
             const int act = a.actions[i];
             if (act < 0 || act >= A) {
                 if (writer) atomicOr(a.status, 1);
@@ -192,10 +186,13 @@ __global__ void ac_targets_kernel(const float *__restrict__ rewards,
     const double q = (double)q_next[(size_t)i * q_stride];
     double t;
     if (nonzero_terminal_discount)
-        t = (double)rewards[i] + discount * q;
+        // `discount * q_st_plus_1` (ddpg_agent.py:157, td3_agent.py:173): a python float times the fp32 network output
+        // is an fp32 product in numpy; only the sum with the float64 rewards is float64.  The other branch is float64
+        // throughout, because (1.0 - game_overs) is a float64 array.
+        t = (double)rewards[i] + (double)((float)discount * q_next[(size_t)i * q_stride]);
     else
         t = (double)rewards[i] + (1.0 - (dones[i] ? 1.0 : 0.0)) * discount * q;
-    if (has_clip) t = fmin(fmax(t, clip_lo), clip_hi);        // np.clip
+    if (has_clip) t = rlx::np_clip(t, clip_lo, clip_hi);      // np.clip: a NaN target stays NaN
     out[i] = (float)t;
 }
 
@@ -209,9 +206,9 @@ __global__ void td3_smooth_kernel(const float *__restrict__ next_actions,
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= batch * act_dim) return;
     const int a = t % act_dim;
-    double nz = fmin(fmax(noise[t], -noise_clip), noise_clip);
+    double nz = rlx::np_clip(noise[t], -noise_clip, noise_clip);
     double v = (double)next_actions[t] + nz;
-    v = fmin(fmax(v, (double)low[a]), (double)high[a]);       // spaces.py:379 np.clip
+    v = rlx::np_clip(v, (double)low[a], (double)high[a]);     // spaces.py:379 np.clip
     out[t] = (float)v;
 }
 
@@ -242,9 +239,9 @@ __global__ void ac_merge_inputs_kernel(const float *__restrict__ actions, const 
         } else if (!noise) {
             v = next_actions[(size_t)r * A + c];
         } else {
-            const double nz = fmin(fmax(noise[(size_t)r * A + c], -noise_clip), noise_clip);
+            const double nz = rlx::np_clip(noise[(size_t)r * A + c], -noise_clip, noise_clip);
             double x = (double)next_actions[(size_t)r * A + c] + nz;
-            x = fmin(fmax(x, (double)low[c]), (double)high[c]);
+            x = rlx::np_clip(x, (double)low[c], (double)high[c]);
             v = (float)x;
         }
         merged2[t] = v;
@@ -314,7 +311,7 @@ int rlx_dqn_head_loss(const float *q_online, long long ld_q, const float *q_next
     RLX_REQUIRE(q_online && q_next_target && actions && rewards && game_overs && dq && status,
                 "rlx_dqn_head_loss: null pointer");
     RLX_REQUIRE(batch > 0 && batch <= 1024 && n_actions > 0 && ld_q >= n_actions && ld_next >= n_actions &&
-                    ld_dq >= n_actions,
+                    ld_dq >= n_actions && (!td_targets || ld_targets >= n_actions),
                 "rlx_dqn_head_loss: bad sizes (batch=%d <= 1024, actions=%d)", batch, n_actions);
     if (!q_next_selector) q_next_selector = q_next_target;
     int threads = 64;

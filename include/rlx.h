@@ -342,7 +342,13 @@ int rlx_rollout_observe_step(const float *reward, float *filtered_reward, double
 /* td_targets holds Q_online(s,.) on entry (fp32 [batch, n_actions]); column actions[i] of row i is
  * replaced by r + (1-done)*discount*Q_target(s', argmax_a q_next_selector(s',a)); td_errors (fp64,
  * optional) receives |new_target - Q_online(s,a)|.  q_next_selector = NULL -> DQN (target net
- * selects, agents/dqn_agent.py:78-79), = Q_online(s',.) -> DDQN (agents/ddqn_agent.py:43). */
+ * selects, agents/dqn_agent.py:78-79), = Q_online(s',.) -> DDQN (agents/ddqn_agent.py:43).
+ * The NaN rules are numpy's.  Selection is np.argmax: the FIRST maximum wins and a NaN counts as the maximum, so the
+ * first NaN of a selector row is the greedy action (with the target net selecting, the target is then that NaN; with a
+ * separate selector it is Q_target at the NaN's column).  This holds for every Q-row selection that restates this
+ * arithmetic: rlx_dqn_head_loss, rlx_dqn_head_loss_backward, rlx_mlp_dqn_update, rlx_mixed_target_head_loss and
+ * rlx_bootstrapped_dqn_head_loss.  A row whose action is outside [0, n_actions) sets bit 0 of *status and is left
+ * unwritten (td_targets, td_errors). */
 int rlx_dqn_targets(const float *q_next_target, const float *q_next_selector, float *td_targets,
                     const int *actions, const float *rewards, const unsigned char *game_overs,
                     double discount, int batch, int n_actions, double *td_errors, int *status,
@@ -366,6 +372,14 @@ int rlx_dueling_combine(const float *state_value, const float *action_advantage,
                         int n_actions, float *q, void *stream);
 int rlx_dueling_combine_backward(const float *dq, int batch, int n_actions, float *dstate_value,
                                  float *daction_advantage, void *stream);
+/* td_targets[i] = fp32(r + (1 - done) * discount * q_next[i * q_stride]) in float64, or, with
+ * use_non_zero_discount_for_terminal_states, fp32(r + (double)((float)discount * q_next[i * q_stride])): the
+ * reference's `discount * q_st_plus_1` (ddpg_agent.py:157, td3_agent.py:173) is a python float times an fp32 array, which
+ * numpy evaluates as an fp32 product; only the sum with the rewards is float64.  game_overs is not used then.  The same
+ * holds for rlx_ac_critic_losses and the fused actor-critic updates.
+ * The clip is np.clip, here and in rlx_ac_critic_losses, rlx_td3_smooth_actions, rlx_ac_merge_inputs,
+ * rlx_gaussian_action and the fused actor-critic updates: a NaN target, noise draw or action stays NaN (C's fmin / fmax
+ * would return the bound and hide a diverged network behind a legal value); +-inf is clipped to the bound. */
 int rlx_ac_td_targets(const float *rewards, const unsigned char *game_overs, const float *q_next,
                       int q_stride, double discount, int use_non_zero_discount_for_terminal_states,
                       int has_clip, double clip_low, double clip_high, int batch,

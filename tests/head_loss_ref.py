@@ -299,8 +299,9 @@ def ppo_continuous_loss(mean, log_std, actions, advantages, old_mean, old_std, c
 def ac_critic_losses(q_next1, q_next2, rewards, game_overs, discount, q, loss_weight=1.0, clip=None,
                      use_non_zero_discount_for_terminal_states=False, td_targets=None):
     """The critic update of DDPG / TD3 / SAC (ddpg_agent.py:156-164, td3_agent.py:168-180): q_next = min of the two target
-    critics (q_next2 None: q_next1), y = r + (1 - done) * discount * q_next in float64 (done ignored with
-    use_non_zero_discount_for_terminal_states), optionally clipped to clip = (low, high), cast to fp32; per stream t the
+    critics (q_next2 None: q_next1), y = r + (1 - done) * discount * q_next in float64 (with
+    use_non_zero_discount_for_terminal_states: r + float64(fp32(discount) * q_next), the reference's fp32 product, done
+    ignored), optionally clipped to clip = (low, high), cast to fp32; per stream t the
     head's loss_weight * mean((q_t - y)^2) and its gradient; total = the sum of the stream losses.
     td_targets: evaluate the losses at these fp32 targets (the device's own) instead of at float32(y).
     -> dict(q_min [B] exact (a selection), y [B] float64 before the cast, y_units = |y| (one rounding, the cast),
@@ -310,7 +311,8 @@ def ac_critic_losses(q_next1, q_next2, rewards, game_overs, discount, q, loss_we
     qn = q1 if q_next2 is None else np.where(q1 <= np.asarray(q_next2, dtype=F32), q1, np.asarray(q_next2, dtype=F32))
     r, done = _f64(rewards), np.asarray(game_overs).astype(bool)
     if use_non_zero_discount_for_terminal_states:
-        y = r + F64(discount) * qn.astype(F64)
+        # `discount * q_st_plus_1` (ddpg_agent.py:157): a python float times the fp32 network output is an fp32 product
+        y = r + (F32(discount) * qn).astype(F64)
     else:
         y = r + (1.0 - done.astype(F64)) * F64(discount) * qn.astype(F64)
     if clip is not None:

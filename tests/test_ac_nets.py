@@ -313,6 +313,41 @@ def test_td3_update_matches_oracle(dev, paired, fused, monkeypatch):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("fused", [False, True])
+def test_td3_update_keeps_a_nan_noise_draw(dev, fused, monkeypatch):
+    """np.clip keeps a NaN (td3_agent.py:162-165): one NaN noise draw makes that row's smoothed action, its TD target, the
+    critic loss and -- through the batch sums of the backward pass -- the critic's weights NaN in the oracle, and the
+    device must follow (fmin / fmax turned the draw into -noise_clipping and the update went on with finite weights).
+    Two things carry the NaN: the clips (np.clip) and the relu of the dense layers behind them, which is the oracle's
+    np.maximum(z, 0) -- `v > 0 ? v : 0` turned the NaN row of the target critic's first layer into zeros."""
+    from coach_amd.agents.td3_agent import TD3Agent, TD3AgentParameters
+    monkeypatch.setattr(TD3Agent, "FUSED_UPDATE", fused)
+    D, A, B = 17, 6, 100
+    ag = _agent(dev, TD3Agent, TD3AgentParameters(), D, A, B)
+    assert (ag._fused() is not None) == fused
+    critic = ag.networks["critic"]
+    oa = O.ActorOracle(ag.networks["actor"].params.named_arrays(), 1.0, lr=1e-3)
+    oc = O.CriticOracle(critic.params.named_arrays(), streams=2, lr=1e-3)
+    rng = np.random.RandomState(4)
+    batch = _batch(rng, B, D, A)
+    noise = rng.normal(0, 0.2, (B, A))
+    noise[3, 2] = np.nan
+    with np.errstate(invalid="ignore"):
+        r = O.td3_update(oa, oc, batch, noise, 1, ag.low, ag.high)
+    ag.noise.copy_(_t(noise, dev))
+    ag._critic_device(_B(dev, batch))
+    want, got = np.asarray(r["targets"]).reshape(-1), ag.td_targets.cpu().numpy().reshape(-1)
+    row = np.arange(B) == 3
+    assert np.array_equal(np.isnan(want), row) and np.array_equal(np.isnan(got), row)
+    np.testing.assert_allclose(got[~row], want[~row], rtol=2e-4, atol=1e-5)
+    assert np.isnan(r["loss"]) and np.isnan(float(critic.loss[:2].sum()))
+    w = critic.params.named_arrays()
+    for name, towers in oc.weights().items():
+        for t, arr in towers.items():
+            assert np.isnan(arr).any() and np.isnan(w[name][t]).any(), "%s[%d]" % (name, t)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", [False, True])
 @pytest.mark.parametrize("resample,paired,dims", [(True, False, (23, 5, 64)), (False, False, (23, 5, 64)),
                                                   (True, True, (23, 5, 64)),
                                                   (True, False, (11, 3, 37)),         # ragged last row block

@@ -102,6 +102,26 @@ def test_all_bits_set_equals_dqn_head_loss_head_by_head_bit_for_bit(rlx, dev, B,
         assert total.tobytes() == d["loss"].tobytes()
 
 
+@pytest.mark.parametrize("huber", [True, False])
+def test_a_nan_in_a_selector_row_wins_that_heads_selection(rlx, dev, huber):
+    """np.argmax (bootstrapped_ref.update): the first NaN of a head's selector row is that head's greedy action.  The target
+    net is finite, so the targets stay finite and are read at the NaN's column"""
+    B, A, K = 37, 3, 4
+    rng = np.random.RandomState(5)
+    q, qn, qs = [(rng.randn(K, B, A) * 2).astype(np.float32) for _ in range(3)]
+    qs[0, 5], qs[1, 5], qs[3, 6], qs[2, 36] = [1, np.nan, 3], [np.nan, 3, np.nan], [2, 2, np.nan], [3, np.nan, np.nan]
+    actions, rewards, go = rng.randint(0, A, size=B), rng.randn(B).astype(np.float32), rng.rand(B) < 0.3
+    masks = np.ones((B, K), np.int64)
+    d = _launch(rlx, dev, q, qn, qs, actions, rewards, go, masks, huber)
+    u = R.update(q, qn, qs, actions, rewards, go, masks, 0.99, huber)
+    assert u["a_star"][5, 0] == 1 and u["a_star"][5, 1] == 0 and u["a_star"][6, 3] == 2 and u["a_star"][36, 2] == 1
+    assert d["status"] == 0 and np.array_equal(d["a_star"], u["a_star"])
+    taken = np.ascontiguousarray(u["td_targets"][:, np.arange(B), actions].T)
+    assert np.isfinite(taken).all() and np.array_equal(d["td"].view(np.uint32), taken.view(np.uint32))
+    np.testing.assert_allclose(d["dq"], u["dq"], **LOSS)
+    np.testing.assert_allclose(d["loss"], u["loss"], **LOSS)
+
+
 def test_loss_kernel_flags_an_action_out_of_range_and_refuses_large_shapes(rlx, dev):
     import torch
     from coach_amd._rlx import RlxError

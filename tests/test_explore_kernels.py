@@ -325,6 +325,36 @@ def test_gaussian_action(rlx, dev, n_env, D, per_sample, bounded):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("per_sample", [False, True])
+def test_gaussian_action_keeps_a_nan_mean(rlx, dev, per_sample):
+    """np.clip keeps a NaN (clip_action_to_space, spaces.py:379): a diverged actor's NaN mean, a NaN std and a NaN draw
+    come out as NaN and not as the lower bound; every other element keeps the bits of the run without them"""
+    n_env, D = 5, 3
+    rng = np.random.RandomState(per_sample)
+    mean = rng.randn(n_env, D).astype(F32)
+    std = rng.uniform(0.05, 2.0, (n_env, D) if per_sample else D).astype(F32)
+    z = rng.standard_normal((n_env, D))
+    low, high = -rng.uniform(0.5, 2.0, D).astype(F32), rng.uniform(0.5, 2.0, D).astype(F32)
+    clean = E.gaussian_action(mean, std, z, low, high).astype(F32)
+    mean[1, 2] = np.nan
+    z[3, 0] = np.nan
+    z[4, 1] = 40.0
+    want = E.gaussian_action(mean, std, z, low, high).astype(F32)
+    isnan = np.zeros((n_env, D), dtype=bool)
+    isnan[1, 2] = isnan[3, 0] = True
+    assert np.array_equal(np.isnan(want), isnan) and want[4, 1] == high[1]
+    out = _d(np.full((n_env, D), SENT, dtype=F32), dev)
+    rlx.gaussian_action(_d(mean, dev), None if per_sample else _d(std, dev), _d(std, dev) if per_sample else None, _d(z, dev),
+                        _d(low, dev), _d(high, dev), n_env, D, out, 0)
+    got = _h(out)
+    assert np.array_equal(np.isnan(got), isnan), got
+    assert np.array_equal(_bits(got[~isnan]), _bits(want[~isnan]))
+    keep = ~isnan
+    keep[4, 1] = False
+    assert np.array_equal(_bits(got[keep]), _bits(clean[keep]))
+
+
+@pytest.mark.gpu
 def test_gaussian_action_needs_both_bounds_or_neither(rlx, dev):
     x, z = _d(np.zeros((4, 2), dtype=F32), dev), _d(np.zeros((4, 2)), dev)
     std, bound = _d(np.ones(2, dtype=F32), dev), _d(np.ones(2, dtype=F32), dev)

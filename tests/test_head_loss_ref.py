@@ -158,7 +158,9 @@ def test_ac_critic_losses_matches_autograd(twin, clip, nonzero, T):
     r = R.ac_critic_losses(q1, q2 if twin else None, rew, done, 0.99, q, 0.5, clip, nonzero)
     qn = np.minimum(q1, q2) if twin else q1
     assert np.array_equal(r["q_min"], qn)
-    y = rew.astype(F64) + (1.0 if nonzero else 1.0 - done) * 0.99 * qn.astype(F64)
+    # the reference's own two statements (ddpg_agent.py:157 / :159-160) on its operand types: float64 rewards and game_overs,
+    # a python float discount, the fp32 network output -- numpy makes the first product fp32 and the second float64
+    y = rew.astype(F64) + 0.99 * qn if nonzero else rew.astype(F64) + (1.0 - done.astype(F64)) * 0.99 * qn
     y = y if clip is None else np.clip(y, *clip)
     np.testing.assert_allclose(r["y"], y, rtol=1e-15)
     if clip is not None:

@@ -478,3 +478,32 @@ def test_ac_critic_losses(rlx, dev, B, T, twin, want_min, has_clip, nonzero, lw)
     got_loss = _h(loss)
     _within(got_loss[:T], ref["loss"], ref["loss_units"], tag + " loss")
     _within(got_loss[T:], [ref["total"]], [ref["total_units"]], tag + " total")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nonzero", [False, True])
+def test_ac_critic_losses_keeps_a_nan_target(rlx, dev, nonzero):
+    """a diverged target critic: np.clip keeps the NaN (the reference's np.minimum(np.maximum())), so that row's target and
+    gradient and every loss are NaN and not clip_low; +-inf is clipped to the bound; the other rows keep their bits"""
+    B, T, clip = 65, 2, (-1.5, 1.5)
+    rng = np.random.RandomState(B + nonzero)
+    q1, q2 = (2 * rng.randn(B)).astype(F32), (2 * rng.randn(B)).astype(F32)
+    rew, done, q = rng.randn(B).astype(F32), (np.arange(B) % 3 == 0).astype(np.uint8), rng.randn(T, B).astype(F32)
+    done[[7, 20]] = 0
+    q1[7], q2[7], q2[20], q1[30], q2[30], q1[31], q2[31] = np.nan, np.nan, np.nan, np.inf, np.inf, -np.inf, -np.inf
+    done[[30, 31]] = 0
+    with np.errstate(invalid="ignore"):
+        want = R.ac_critic_losses(q1, q2, rew, done, 0.99, q, 1.0, clip, nonzero)
+    # q2[20] = NaN: q_min = q1 <= q2 ? q1 : q2 takes the NaN in the kernel and in the reference's np.where
+    isnan = np.zeros(B, dtype=bool)
+    isnan[[7, 20]] = True
+    assert np.array_equal(np.isnan(want["y"]), isnan) and want["y"][30] == clip[1] and want["y"][31] == clip[0]
+    y, dq, loss = _sent((B,), dev), _sent((T, B), dev), _sent((T + 1,), dev)
+    rlx.ac_critic_losses(_d(q1, dev), _d(q2, dev), _d(rew, dev), _d(done, dev), 0.99, int(nonzero), 1, clip[0], clip[1],
+                         _d(q, dev), T, B, 1.0, None, y, dq, loss, 0)
+    y_dev, dq_dev = _h(y), _h(dq)
+    assert np.array_equal(np.isnan(y_dev), isnan), y_dev
+    _within(y_dev[~isnan], want["y"][~isnan], (1 + 2.0 ** -20) * want["y_units"][~isnan], "finite targets")
+    _same_bits(y_dev[[30, 31]], np.array([clip[1], clip[0]], dtype=F32), "infinite targets are clipped")
+    assert np.array_equal(np.isnan(dq_dev), np.broadcast_to(isnan, (T, B)))
+    assert np.isnan(_h(loss)).all()

@@ -67,6 +67,40 @@ def test_fused_update_matches_layerwise_and_oracle(dev, dims, A, B, huber, ddqn,
     assert int(fused._fused["sync"].abs().sum().item()) == 0          # barrier words re-armed
 
 
+@pytest.mark.parametrize("ddqn", [False, True])
+def test_fused_update_selects_a_nan_of_the_target_net_like_the_layerwise_path(dev, ddqn):
+    """A NaN in one element (column 1) of the target tower's last bias: Q_target(s', 1) is NaN in every row.  DQN: np.argmax
+    takes the first NaN, so every row's target, every |TD error| and the loss are NaN -- a loop that asks `q > best` skips
+    the NaN and trains on with finite targets.  DDQN: the online net selects, and exactly the rows it sends to column 1
+    are NaN.  The one-launch update and the layer-by-layer path (rlx_dqn_head_loss_backward) agree on which values are
+    NaN, and to the usual accumulation noise on the others."""
+    import torch
+    dims, A, B = (8, 96, 96), 5, 20
+    fused, plain = _net(dev, dims, A, True, True), _net(dev, dims, A, True, False)
+    for net in (fused, plain):
+        name = [n for n in net.params.entries if n.endswith("bias")][-1]
+        bias = net.params.w(name, 0, buf=net.target)
+        assert tuple(bias.shape) == (A,), (name, bias.shape)
+        bias[1] = float("nan")
+    rng = np.random.RandomState(3)
+    dv = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x)).to(dev).to(dt)
+    s2 = dv(rng.randn(B, dims[0]).astype(np.float32), torch.float32)
+    args = (dv(rng.randn(B, dims[0]).astype(np.float32), torch.float32), s2, B, dv(rng.randint(0, A, B), torch.int32),
+            dv(rng.randn(B).astype(np.float32), torch.float32), dv(rng.rand(B) < 0.2, torch.uint8), 0.97)
+    to_column_1 = (plain.q_values(s2, B).data.view(B, A).argmax(1) == 1).cpu().numpy() if ddqn else np.ones(B, dtype=bool)
+    td, loss = {}, {}
+    for k, net in (("f", fused), ("p", plain)):
+        td[k] = torch.zeros(B, dtype=torch.float64, device=dev)
+        loss[k] = float(net.learn_from_batch(*args, td_errors=td[k], double_dqn=ddqn).item())
+        net.check_status()
+        td[k] = td[k].cpu().numpy()
+        assert np.array_equal(np.isnan(td[k]), to_column_1), (k, td[k])
+    assert np.isnan(loss["f"]) == np.isnan(loss["p"]) == bool(to_column_1.any())
+    np.testing.assert_allclose(td["f"][~to_column_1], td["p"][~to_column_1], rtol=1e-4, atol=2e-6)
+    if not ddqn:                                # every value is NaN: the two paths agree bit for bit in the only sense there is
+        assert np.isnan(td["f"]).all() and np.isnan(td["p"]).all() and np.isnan(loss["f"]) and np.isnan(loss["p"])
+
+
 def test_fused_update_is_reproducible(dev):
     """fixed summation orders: two runs from the same state give bit-identical weights."""
     import torch

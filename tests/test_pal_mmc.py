@@ -116,6 +116,25 @@ def test_kernel_gives_the_reference_agents_targets_on_the_golden_cases(rlx, dev,
     assert d["td"].tobytes() == c["targets_" + mode].tobytes()
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_a_nan_in_the_selector_row_wins_the_selection(rlx, dev, mode):
+    """np.argmax: the first NaN of the selector row is the greedy action.  The target net is finite here, so every output
+    is finite and the comparison stays on bits: the target is read at the NaN's column, not at the largest finite one."""
+    c = _random_case(37, 3, 11)
+    c["q_sel"][5] = [1.0, np.nan, 3.0]
+    c["q_sel"][6] = [np.nan, 3.0, np.nan]
+    c["q_sel"][7] = [2.0, 2.0, np.nan]
+    assert np.argmax(c["q_sel"][5:8], 1).tolist() == [1, 0, 2]
+    c["go"][5:8] = False
+    c["q_next"][5:8] = [10.0, 20.0, 30.0]
+    for huber in (True, False):
+        d = _check_against_the_restatement(rlx, dev, c, mode, huber, 0.0, 0.0)
+        taken = d["td"][np.arange(5, 8), c["actions"][5:8]]
+        want = (c["rewards"][5:8].astype(np.float64) + 0.99 * np.array([20.0, 10.0, 30.0])).astype(np.float32)
+        assert taken.tobytes() == want.tobytes()
+        _check_against_the_restatement(rlx, dev, c, mode, huber, 0.9, 0.1, ld=8)
+
+
 def test_kernel_at_more_than_one_wave_and_at_the_largest_batch(rlx, dev):
     """65 rows (a 128-leaf tree), 300 (512) and 1024 (the limit): the tree's other sizes"""
     for B in (65, 300, 1024):
