@@ -2352,23 +2352,30 @@ int rlx_gemm_workspace_floats(int M, int N, int K, int batch, long long *floats_
 }  // extern "C"
 
 namespace {
-// what rlx_gemm decided for one descriptor: everything a launch needs (gemm_impl in planning mode fills it instead
-// of launching; rlx_gemm_pair launches two plans as one grid)
+// a product is planned for a launch of its own, or as one member of a combined grid (pair, multi; what describe answers for)
+enum class PlanFor { Launch, Member };
+enum class Path { Thin32, Thin16, Generic, FastReg, FastRing, Big128, Big64 };
+inline bool is_thin(Path p) { return p <= Path::Thin16; }
+inline bool is_fast(Path p) { return p >= Path::FastReg; }      // the vector-load tiled kernels
+
+// what plan_gemm decided for one descriptor: everything a launch needs (launch_product issues it; the combined launchers
+// put the g / grid of several plans into one grid)
 struct GemmPlan {
-    bool tiled_fast;            // the fast tiled kernel with 64x64 tiles would run (else: thin / generic / folded paths)
-    bool thin, a_ck, b_cn;      // the thin kernel would run, with these operand layouts
-    bool t16;                   // ... on 16 x 16 output tiles (grid sized accordingly)
-    int kw;                     // 2 / 4: the fast kernel on 32 x 64 / 32 x 32 tiles with the slab split over the wave groups would run
+    rlx_gemm_desc d;            // the descriptor planned: the caller's, or (refolded) its batched equivalent
+    bool refolded;              // towers folded into N that no kernel can unfold here: d is one tower per batch index
+    Path path;                  // the kernel family; FastRing / Big*: launch_product falls back where no instance exists
+    int bm, bn, kw;             // workgroup tile; kw 2 / 4: the K slab split over the wave groups of a workgroup
+    int splits, kchunk;         // K chunks over workgroups (> 1: partials + a reduction), chunk length
+    bool ring;                  // operands may go through the LDS-DMA ring (decided here, read by every launcher)
+    bool a_vec_red, u8, b_vec_red, a_tab;
     GemmDev g;
     dim3 grid;
-    bool a_vec_red, u8, b_vec_red, a_tab;
-    int splits, M, N, batch;
-    bool allow_fold = false;    // in: towers folded into N may count as tiled_fast (the caller's kernel runs the fold epilogue)
-    // what a launch of this descriptor would be (rlx_gemm_describe): the vector-load tiled kernel or not, its tile, wave
-    // groups per K slab, K chunks over workgroups, chunk length, operands through the LDS-DMA ring or staged by registers
-    bool q_fast = false, q_ring = false;
-    int q_bm = 0, q_bn = 0, q_kw = 0, q_splits = 0, q_kchunk = 0;
 };
+// what a combined grid takes: the fast kernel on 64 x 64 tiles or with the in-workgroup K split (kw 2 / 4); towers folded
+// into N only where the caller's kernel runs the fold epilogue
+inline bool member_tiled(const GemmPlan &p, bool allow_fold) {
+    return !p.refolded && is_fast(p.path) && (p.kw > 1 || (p.bm == 64 && p.bn == 64)) && (!p.g.fold || allow_fold);
+}
 
 int launch_splitk_reduce(const GemmDev &g, int M, int N, int batch, int splits, hipStream_t s) {
     const long long mn = (long long)M * N;
@@ -2389,9 +2396,9 @@ int launch_splitk_reduce(const GemmDev &g, int M, int N, int batch, int splits, 
 // rlx_gemm_desc.row_heads: the reduction pass of a product split over K finishes whole rows and runs the narrow layers that
 // read them (splitk_reduce_rows_kernel).  Returns false when the combination is not the one that kernel reproduces bit
 // for bit (the caller then reduces as usual and rlx_gemm launches the heads behind it).
-thread_local bool tl_row_heads_done = false;
-thread_local const rlx_ppo_rows_desc *tl_ppo_rows = nullptr;      // rlx_ppo_fc_rows: the rows also get the Clipped-PPO epilogue
-bool launch_reduce_with_row_heads(const GemmDev &g, const rlx_gemm_desc &d, int splits, hipStream_t s) {
+// ppo_rows (rlx_ppo_fc_rows, else null): the rows also get the Clipped-PPO epilogue.
+bool launch_reduce_with_row_heads(const GemmDev &g, const rlx_gemm_desc &d, int splits,
+                                  const rlx_ppo_rows_desc *ppo_rows, hipStream_t s) {
     const long long mn = (long long)d.M * d.N;
     if (splits <= 16 || d.N % 4 != 0 || mn >= (1LL << 31) || !aligned16(g.ws) || g.fold || g.colsum ||
         d.N > kRowHeadsMaxN || d.batch > rlx_small::kMaxProblems || d.n_row_heads > d.batch)
@@ -2420,8 +2427,8 @@ bool launch_reduce_with_row_heads(const GemmDev &g, const rlx_gemm_desc &d, int 
     dim3 rgrid(d.M, d.batch);
     const int passes = (d.N / 4 + 63) / 64;                 // 1 .. 8
     PpoRowsDev r{};
-    if (tl_ppo_rows) {
-        const rlx_ppo_rows_desc &q = *tl_ppo_rows;
+    if (ppo_rows) {
+        const rlx_ppo_rows_desc &q = *ppo_rows;
         if (passes > 4 || nn < 4) return false;
         const rlx_small_dense_problem *hq[2] = {&q.value_head, &q.policy_head};
         for (int i = 0; i < 2; ++i) {
@@ -2463,24 +2470,17 @@ bool launch_reduce_with_row_heads(const GemmDev &g, const rlx_gemm_desc &d, int 
     return true;
 }
 
-// what a deferred reduction needs (rlx_gemm_defer): only a product with the plain-store epilogue and partials the
-// float4 reduce scheme can read qualifies; anything else is reduced at once (job->splits = 0)
-bool deferrable(const GemmDev &g, int M, int N) {
-    return !g.bias && !g.aux && !g.accumulate && g.act == RLX_ACT_NONE && N % 4 == 0 &&
-           (long long)M * N < (1LL << 31) && aligned16(g.ws);
-}
-void fill_job(rlx_splitk_job *job, const GemmDev &g, int M, int N, int batch, int splits) {
-    job->partials = g.ws; job->colsum_partials = g.colsum ? g.ws_colsum : nullptr;
-    job->C = g.c; job->colsum_out = g.colsum;
-    job->ldc = g.ldc; job->c_batch_stride = g.c_batch_stride; job->colsum_batch_stride = g.colsum_batch_stride;
-    job->M = M; job->N = N; job->batch = batch; job->splits = splits; job->n_fold = g.fold;
+inline dim3 tile_grid(const rlx_gemm_desc &d, int bm, int bn, int splits) {
+    return dim3((d.N + bn - 1) / bn, (d.M + bm - 1) / bm, d.batch * splits);
 }
 
-int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_splitk_job *defer = nullptr) {
-    if (plan) { plan->tiled_fast = plan->thin = plan->t16 = false; plan->kw = 1; }
-    if (defer) defer->splits = 0;
+// The one place a product's path is decided.  Pure host code: validates, selects, fills *p; launches nothing.
+// `where` changes two things, each marked below: the thin kernel's 16 x 16 tile threshold and the big wave tiles.
+int plan_gemm(const rlx_gemm_desc *d_host, PlanFor where, GemmPlan *p, bool refolded = false) {
     RLX_REQUIRE(d_host != nullptr, "rlx_gemm: null descriptor");
-    const rlx_gemm_desc &d = *d_host;
+    p->d = *d_host;
+    p->refolded = refolded;
+    const rlx_gemm_desc &d = p->d;
     RLX_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0 && d.batch > 0,
                 "rlx_gemm: bad shape M=%d N=%d K=%d batch=%d", d.M, d.N, d.K, d.batch);
     RLX_REQUIRE(d.A && d.B && d.C, "rlx_gemm: null operand");
@@ -2491,7 +2491,7 @@ int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_spl
     RLX_REQUIRE(d.activation >= 0 && d.activation <= 2 && d.deriv_kind >= 0 && d.deriv_kind <= 2,
                 "rlx_gemm: unknown activation");
 
-    GemmDev g;
+    GemmDev &g = p->g;
     g.xcd_mode = g_xcd_mode;
     g.M = d.M; g.N = d.N; g.K = d.K;
     g.a.base = d.A; g.a.tab_o = d.a_row_tab; g.a.tab_r = d.a_k_tab;
@@ -2515,6 +2515,7 @@ int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_spl
     // vector dimension of each operand: the index whose stride is 1 (tables: declared by caller)
     const bool a_vec_red = d.a_row_tab || d.a_k_tab ? (d.a_vec_along_k != 0) : (d.a_k_stride == 1);
     const bool b_vec_red = d.b_k_stride == 1 && d.b_n_stride != 1;
+    p->a_vec_red = a_vec_red; p->b_vec_red = b_vec_red;
     const int a_elem = d.a_is_u8 ? 1 : 4;
     if (d.a_row_tab || d.a_k_tab) {
         g.a.vec_ok = d.a_tab_vec_ok != 0;
@@ -2533,32 +2534,15 @@ int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_spl
     if (!d.a_row_tab && !d.a_k_tab && !d.a_is_u8 && d.n_fold <= 0 && d.K <= 1024) {
         const long long t64 = (long long)((d.M + 63) / 64) * ((d.N + 63) / 64) * d.batch;
         if (t64 <= kThinMaxTiles && (long long)d.N * d.K <= (1 << 18)) {      // MLP-sized weights only: the scalar loads lose on wide B
-            const bool a_ck = d.a_k_stride == 1, b_cn = d.b_n_stride == 1;
             // 32 x 32 tiles that leave most CUs idle -> 16 x 16 tiles (4x the workgroups, same reduction order)
             // (a launch of its own profits up to 256 tiles — dW 400x300x100, 130 tiles: 5.22 -> 3.81 us; as one half of a
             // dW + dX pair grid the same problem is better left on 32 x 32 tiles: 5.96 vs 6.6 us for the pair)
             const long long t32 = (long long)((d.M + 31) / 32) * ((d.N + 31) / 32) * d.batch;
-            const bool t16 = t32 <= (plan ? kThin16MaxTiles : kThin16SingleMaxTiles);
-            const int tile = t16 ? 16 : 32;
-            dim3 tgrid((d.N + tile - 1) / tile, (d.M + tile - 1) / tile, d.batch);
+            const bool t16 = t32 <= (where == PlanFor::Member ? kThin16MaxTiles : kThin16SingleMaxTiles);
             g.splits = 1; g.kchunk = d.K; g.ws = nullptr; g.vec_epi = 0; g.fold = 0;
-            if (plan) {
-                plan->thin = true; plan->a_ck = a_ck; plan->b_cn = b_cn; plan->t16 = t16;
-                plan->g = g; plan->grid = tgrid; plan->splits = 1;
-                return RLX_OK;
-            }
-            hipStream_t ts = rlx::as_stream(stream);
-            if (t16) {
-                if (a_ck && b_cn) RLX_LAUNCH((gemm_thin16_kernel<true, true>), tgrid, kThreads, 0, ts, g);
-                else if (a_ck) RLX_LAUNCH((gemm_thin16_kernel<true, false>), tgrid, kThreads, 0, ts, g);
-                else if (b_cn) RLX_LAUNCH((gemm_thin16_kernel<false, true>), tgrid, kThreads, 0, ts, g);
-                else RLX_LAUNCH((gemm_thin16_kernel<false, false>), tgrid, kThreads, 0, ts, g);
-            }
-            else if (a_ck && b_cn) RLX_LAUNCH((gemm_thin_kernel<true, true>), tgrid, kThreads, 0, ts, g);
-            else if (a_ck) RLX_LAUNCH((gemm_thin_kernel<true, false>), tgrid, kThreads, 0, ts, g);
-            else if (b_cn) RLX_LAUNCH((gemm_thin_kernel<false, true>), tgrid, kThreads, 0, ts, g);
-            else RLX_LAUNCH((gemm_thin_kernel<false, false>), tgrid, kThreads, 0, ts, g);
-            RLX_LAUNCH_CHECK();
+            p->path = t16 ? Path::Thin16 : Path::Thin32;
+            p->bm = p->bn = t16 ? 16 : 32; p->kw = 1; p->splits = 1; p->kchunk = d.K;
+            p->ring = p->a_tab = p->u8 = false; p->grid = tile_grid(d, p->bm, p->bn, 1);
             return RLX_OK;
         }
     }
@@ -2606,23 +2590,23 @@ int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_spl
     if (fast && a_tab && kchunk > kTabChunk) {
         // the fast kernel stages a chunk's im2col offsets in LDS; a longer chunk (no workspace to split K into) takes
         // the bounds-checked kernel
-        fast = false;
-        BM = narrow ? 128 : 64;
-        BN = narrow ? 32 : 64;
-        KW = 1;
+        fast = false; KW = 1;
+        BM = narrow ? 128 : 64; BN = narrow ? 32 : 64;
     }
-    // large products: 2 x 2 accumulator tiles per wave (gemm_dma_big_kernel) — fp32 operands on the ring, no K split
-    int big = 0;            // 1: 128 x 128 (64 x 64 per wave), 2: 128 x 64 (64 x 32 per wave)
-    if (fast && g_dma && g_big_tiles && !plan && !u8_in && !narrow && KW == 1 && splits == 1 && !g.fold &&
-        BM == 64 && BN == 64 && (!a_tab || kchunk <= kDmaTabChunk) && !(!a_vec_red) && !(a_tab && b_vec_red)) {
+    // operands through the LDS-DMA ring (else staged by registers): uint8 only in mode 2, never the 128 x 32 tiles, a
+    // table chunk the ring's LDS table holds.  Decided here only: describe and every launcher read it from the plan.
+    const bool ring = fast && g_dma && (g_dma >= 2 || !u8_in) && !narrow && (!a_tab || kchunk <= kDmaTabChunk);
+    // large products: 2 x 2 accumulator tiles per wave (gemm_dma_big_kernel) — fp32 operands on the ring, no K split.
+    // Only for a launch of its own: no combined grid has such a member (same sums as the 64 x 64 tiling, bit for bit).
+    int big = 0;           // 1: 128 x 128 (64 x 64 per wave), 2: 128 x 64 (64 x 32 per wave)
+    if (ring && g_big_tiles && where == PlanFor::Launch && !u8_in && KW == 1 && splits == 1 && !g.fold &&
+        BM == 64 && BN == 64 && a_vec_red && !(a_tab && b_vec_red)) {
         if (d.N >= 128 && tiles_of(128, 128) >= kBigMinTiles) { big = 1; BM = 128; BN = 128; }
         // (128 x 64 with 64 x 32 per wave for the N = 64 convolutions of the whole-dataset passes: neutral to slightly worse,
         // profiles/r05_ab_big_wave_tiles.txt — g_big_tiles == 2 keeps it reachable for A/Bs)
         else if (g_big_tiles == 2 && d.N <= 64 && tiles_of(128, 64) >= 2 * kBigMinTiles) { big = 2; BM = 128; BN = 64; }
     }
-    g.splits = splits;
-    g.kchunk = kchunk;
-    g.ws = d.workspace;
+    g.splits = splits; g.kchunk = kchunk; g.ws = d.workspace;
     if (splits > 1) g.ws_colsum = d.workspace + (size_t)d.M * d.N * d.batch * splits;
 
     g.vec_epi = d.N % 4 == 0 &&
@@ -2631,8 +2615,6 @@ int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_spl
                                (!d.bias || (aligned16(d.bias) && d.bias_batch_stride % 4 == 0 && d.bias_batch_stride2 % 4 == 0)) &&
                                (!d.deriv_aux || (aligned16(d.deriv_aux) && d.aux_ld % 4 == 0 &&
                                                  d.aux_batch_stride % 4 == 0))));
-    hipStream_t s = rlx::as_stream(stream);
-    dim3 grid((d.N + BN - 1) / BN, (d.M + BM - 1) / BM, d.batch * splits);
     if (g.fold) {
         // towers folded into N: only the fast kernel with 16-byte epilogue and the float4 reduce know the
         // column -> (tower, column) mapping; anything else runs the equivalent batched problem
@@ -2649,72 +2631,109 @@ int gemm_impl(const rlx_gemm_desc *d_host, void *stream, GemmPlan *plan, rlx_spl
             t.N = g.fold;
             t.n_fold = 0;
             t.a_batch_stride = 0;
-            if (plan) return RLX_OK;
-            return gemm_impl(&t, stream, nullptr, defer);
+            return plan_gemm(&t, where, p, true);       // (n_fold is 0 now: planned once more, as any batched product)
         }
     }
-    if (plan) {
-        plan->q_fast = fast; plan->q_bm = BM; plan->q_bn = BN; plan->q_kw = KW; plan->q_splits = splits; plan->q_kchunk = kchunk;
-        plan->q_ring = fast && g_dma && (g_dma >= 2 || !d.a_is_u8) && !narrow && (!a_tab || kchunk <= kDmaTabChunk);
-        if (fast && ((BM == 64 && BN == 64) || KW > 1) && (!g.fold || plan->allow_fold)) {
-            plan->tiled_fast = KW == 1;
-            plan->kw = KW;
-            plan->g = g;
-            plan->grid = grid;
-            plan->a_vec_red = a_vec_red; plan->u8 = d.a_is_u8 != 0; plan->b_vec_red = b_vec_red; plan->a_tab = a_tab;
-            plan->splits = splits; plan->M = d.M; plan->N = d.N; plan->batch = d.batch;
+    p->path = big == 1 ? Path::Big128 : big == 2 ? Path::Big64 : ring ? Path::FastRing : fast ? Path::FastReg : Path::Generic;
+    p->bm = BM; p->bn = BN; p->kw = KW; p->splits = splits; p->kchunk = kchunk;
+    p->ring = ring; p->u8 = u8_in; p->a_tab = a_tab;
+    p->grid = tile_grid(d, BM, BN, splits);
+    return RLX_OK;
+}
+
+// Issues exactly the product kernel the plan names.  Where the named family has no instance for the operand combination the
+// next one takes it: big -> ring -> register-staged -> generic (bounds-checked).
+int launch_product(const GemmPlan &p, hipStream_t s) {
+    GemmDev g = p.g;
+    dim3 grid = p.grid;
+    const bool narrow = p.bm == 128 && p.bn == 32;
+    if (is_thin(p.path)) {
+        const bool a_ck = p.a_vec_red, b_cn = !p.b_vec_red;     // A contiguous along K, B along N
+        if (p.path == Path::Thin16) {
+            if (a_ck && b_cn) RLX_LAUNCH((gemm_thin16_kernel<true, true>), grid, kThreads, 0, s, g);
+            else if (a_ck) RLX_LAUNCH((gemm_thin16_kernel<true, false>), grid, kThreads, 0, s, g);
+            else if (b_cn) RLX_LAUNCH((gemm_thin16_kernel<false, true>), grid, kThreads, 0, s, g);
+            else RLX_LAUNCH((gemm_thin16_kernel<false, false>), grid, kThreads, 0, s, g);
         }
+        else if (a_ck && b_cn) RLX_LAUNCH((gemm_thin_kernel<true, true>), grid, kThreads, 0, s, g);
+        else if (a_ck) RLX_LAUNCH((gemm_thin_kernel<true, false>), grid, kThreads, 0, s, g);
+        else if (b_cn) RLX_LAUNCH((gemm_thin_kernel<false, true>), grid, kThreads, 0, s, g);
+        else RLX_LAUNCH((gemm_thin_kernel<false, false>), grid, kThreads, 0, s, g);
+        RLX_LAUNCH_CHECK();
         return RLX_OK;
     }
+    const rlx_gemm_desc &d = p.d;
+    const bool fast = is_fast(p.path), big = p.path == Path::Big128 || p.path == Path::Big64;
     if (g_stamps.buf && fast) {
         const long long need = 4LL * grid.x * grid.y * grid.z;
         if (g_stamps.cursor + need <= g_stamps.capacity && g_stamps.ncalls < 512) {
             g.stamps = g_stamps.buf + g_stamps.cursor;
-            g_stamps.calls[g_stamps.ncalls++] = {d.M, d.N, d.K, d.batch, splits, (int)grid.x, (int)grid.y,
+            g_stamps.calls[g_stamps.ncalls++] = {d.M, d.N, d.K, d.batch, p.splits, (int)grid.x, (int)grid.y,
                                                  (int)grid.z, g_stamps.cursor};
             g_stamps.cursor += need;
         }
     }
-    int rc = -1;
-    if (big == 1) rc = launch_dma_big<128, 128, 2, 2>(g, a_vec_red, b_vec_red, a_tab, grid, s);
-    else if (big == 2) rc = launch_dma_big<128, 64, 2, 1>(g, a_vec_red, b_vec_red, a_tab, grid, s);
+    int rc = -1, tile = p.bm * p.bn;
+    if (p.path == Path::Big128) rc = launch_dma_big<128, 128, 2, 2>(g, p.a_vec_red, p.b_vec_red, p.a_tab, grid, s);
+    else if (p.path == Path::Big64) rc = launch_dma_big<128, 64, 2, 1>(g, p.a_vec_red, p.b_vec_red, p.a_tab, grid, s);
     if (rc != 0 && big) {                       // (no instance for this operand combination: back to 64 x 64)
-        big = 0; BM = BN = 64;
-        grid = dim3((d.N + BN - 1) / BN, (d.M + BM - 1) / BM, d.batch * splits);
+        tile = 64 * 64;
+        grid = tile_grid(d, 64, 64, p.splits);
     }
-    if (rc != 0 && fast && g_dma && (g_dma >= 2 || !d.a_is_u8) && !narrow && (!a_tab || kchunk <= kDmaTabChunk)) {
-        const bool u8 = d.a_is_u8 != 0;
-        if (KW == 2) rc = launch_dma<32, 64, 2>(g, a_vec_red, b_vec_red, a_tab, u8, grid, s);
-        else if (KW == 4) rc = launch_dma<32, 32, 4>(g, a_vec_red, b_vec_red, a_tab, u8, grid, s);
-        else rc = launch_dma<64, 64, 1>(g, a_vec_red, b_vec_red, a_tab, u8, grid, s);
+    if (rc != 0 && p.ring) {
+        if (p.kw == 2) rc = launch_dma<32, 64, 2>(g, p.a_vec_red, p.b_vec_red, p.a_tab, p.u8, grid, s);
+        else if (p.kw == 4) rc = launch_dma<32, 32, 4>(g, p.a_vec_red, p.b_vec_red, p.a_tab, p.u8, grid, s);
+        else rc = launch_dma<64, 64, 1>(g, p.a_vec_red, p.b_vec_red, p.a_tab, p.u8, grid, s);
     }
     if (fast && rc != 0) {
-        const bool u8 = d.a_is_u8 != 0;
-        if (narrow) rc = launch_fast<128, 32, 1, 1>(g, a_vec_red, u8, b_vec_red, a_tab, grid, s);
-        else if (KW == 2) rc = launch_fast<32, 64, 1, 1, 2>(g, a_vec_red, u8, b_vec_red, a_tab, grid, s);
-        else if (KW == 4) rc = launch_fast<32, 32, 1, 1, 4>(g, a_vec_red, u8, b_vec_red, a_tab, grid, s);
-        else rc = launch_fast<64, 64, 1, 1>(g, a_vec_red, u8, b_vec_red, a_tab, grid, s);
+        if (narrow) rc = launch_fast<128, 32, 1, 1>(g, p.a_vec_red, p.u8, p.b_vec_red, p.a_tab, grid, s);
+        else if (p.kw == 2) rc = launch_fast<32, 64, 1, 1, 2>(g, p.a_vec_red, p.u8, p.b_vec_red, p.a_tab, grid, s);
+        else if (p.kw == 4) rc = launch_fast<32, 32, 1, 1, 4>(g, p.a_vec_red, p.u8, p.b_vec_red, p.a_tab, grid, s);
+        else rc = launch_fast<64, 64, 1, 1>(g, p.a_vec_red, p.u8, p.b_vec_red, p.a_tab, grid, s);
     }
     if (rc != 0) {
-        RLX_REQUIRE(BM * BN == 4096, "rlx_gemm: internal tile selection error");
-        rc = narrow ? launch_variant<128, 32>(g, a_vec_red, d.a_is_u8 != 0, b_vec_red, grid, s)
-                    : launch_variant<64, 64>(g, a_vec_red, d.a_is_u8 != 0, b_vec_red, grid, s);
+        RLX_REQUIRE(tile == 4096, "rlx_gemm: internal tile selection error");
+        rc = narrow ? launch_variant<128, 32>(g, p.a_vec_red, p.u8, p.b_vec_red, grid, s)
+                    : launch_variant<64, 64>(g, p.a_vec_red, p.u8, p.b_vec_red, grid, s);
     }
     RLX_REQUIRE(rc == 0, "rlx_gemm: unsupported operand combination (uint8 A with transposed B)");
     RLX_LAUNCH_CHECK();
-    if (splits > 1) {
-        if (defer && deferrable(g, d.M, d.N)) {
-            fill_job(defer, g, d.M, d.N, d.batch, splits);
-            return RLX_OK;
-        }
-        if (d.row_heads && d.n_row_heads > 0 && launch_reduce_with_row_heads(g, d, splits, s)) {
-            tl_row_heads_done = true;
-            RLX_LAUNCH_CHECK();
-            return RLX_OK;
-        }
-        return launch_splitk_reduce(g, d.M, d.N, d.batch, splits, s);
-    }
     return RLX_OK;
+}
+
+// The one finishing step of a product that split K over workgroups: leave the reduction to the caller's job, let it finish
+// whole rows and run the narrow layers that read them (row_heads: the descriptor's, with the Clipped-PPO epilogue of
+// ppo_rows if given), or reduce plainly.  *heads_ran (if wanted) is set where the second happened.
+int finish_product(const GemmPlan &p, rlx_splitk_job *defer, bool row_heads, const rlx_ppo_rows_desc *ppo_rows,
+                   hipStream_t s, bool *heads_ran) {
+    if (p.splits <= 1) return RLX_OK;
+    const rlx_gemm_desc &d = p.d; const GemmDev &g = p.g;
+    // a deferred reduction (rlx_gemm_defer): only a product with the plain-store epilogue and partials the float4 reduce
+    // scheme can read qualifies; anything else is reduced at once (job->splits stays 0)
+    if (defer && !g.bias && !g.aux && !g.accumulate && g.act == RLX_ACT_NONE && d.N % 4 == 0 &&
+        (long long)d.M * d.N < (1LL << 31) && aligned16(g.ws)) {
+        defer->partials = g.ws; defer->colsum_partials = g.colsum ? g.ws_colsum : nullptr;
+        defer->C = g.c; defer->colsum_out = g.colsum;
+        defer->ldc = g.ldc; defer->c_batch_stride = g.c_batch_stride; defer->colsum_batch_stride = g.colsum_batch_stride;
+        defer->M = d.M; defer->N = d.N; defer->batch = d.batch; defer->splits = p.splits; defer->n_fold = g.fold;
+        return RLX_OK;
+    }
+    if (row_heads && d.row_heads && d.n_row_heads > 0 && launch_reduce_with_row_heads(p.g, d, p.splits, ppo_rows, s)) {
+        if (heads_ran) *heads_ran = true;
+        RLX_LAUNCH_CHECK();
+        return RLX_OK;
+    }
+    return launch_splitk_reduce(p.g, d.M, d.N, d.batch, p.splits, s);
+}
+
+// a launch of its own, start to end: plan, product, finishing step
+int gemm_single(const rlx_gemm_desc *d_host, rlx_splitk_job *defer, const rlx_ppo_rows_desc *rows, void *stream, bool *heads_ran) {
+    GemmPlan p;
+    hipStream_t s = rlx::as_stream(stream);
+    int rc = plan_gemm(d_host, PlanFor::Launch, &p);
+    if (rc == RLX_OK) rc = launch_product(p, s);
+    if (rc == RLX_OK) rc = finish_product(p, defer, true, rows, s, heads_ran);
+    return rc;
 }
 
 }  // namespace
@@ -2723,57 +2742,58 @@ extern "C" {
 
 int rlx_gemm_describe(const rlx_gemm_desc *desc, int *out8_host) {
     RLX_REQUIRE(desc && out8_host, "rlx_gemm_describe: null pointer");
-    GemmPlan plan{};
-    const int rc = gemm_impl(desc, nullptr, &plan, nullptr);
+    GemmPlan p;
+    const int rc = plan_gemm(desc, PlanFor::Member, &p);
     if (rc != RLX_OK) return rc;
-    out8_host[0] = plan.q_fast; out8_host[1] = plan.q_bm; out8_host[2] = plan.q_bn; out8_host[3] = plan.q_kw;
-    out8_host[4] = plan.q_splits; out8_host[5] = plan.q_kchunk; out8_host[6] = plan.q_ring; out8_host[7] = plan.thin;
+    for (int i = 0; i < 8; ++i) out8_host[i] = 0;
+    if (p.refolded) return RLX_OK;              // (its batched equivalent would run, not the product described: no answer)
+    if (is_thin(p.path)) { out8_host[7] = 1; return RLX_OK; }
+    out8_host[0] = is_fast(p.path); out8_host[1] = p.bm; out8_host[2] = p.bn; out8_host[3] = p.kw;
+    out8_host[4] = p.splits; out8_host[5] = p.kchunk; out8_host[6] = p.ring;
     return RLX_OK;
 }
 
 int rlx_gemm(const rlx_gemm_desc *d_host, void *stream) {
-    tl_row_heads_done = false;
-    const int rc = gemm_impl(d_host, stream, nullptr);
-    if (rc != RLX_OK || !d_host->row_heads || d_host->n_row_heads <= 0 || tl_row_heads_done) return rc;
+    bool heads_ran = false;
+    const int rc = gemm_single(d_host, nullptr, nullptr, stream, &heads_ran);
+    if (rc != RLX_OK || !d_host->row_heads || d_host->n_row_heads <= 0 || heads_ran) return rc;
     return rlx_dense_small_forward_multi(d_host->row_heads, d_host->n_row_heads, stream);   // not fused: behind the product
-}
-
-static int gemm_pair_impl(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc *input_grad, void *stream,
-                          rlx_splitk_job *defer);
-
-int rlx_gemm_pair(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc *input_grad, void *stream) {
-    return gemm_pair_impl(weight_grad, input_grad, stream, nullptr);
 }
 
 int rlx_gemm_defer(const rlx_gemm_desc *desc_host, rlx_splitk_job *job_host, void *stream) {
     RLX_REQUIRE(job_host != nullptr, "rlx_gemm_defer: null job");
-    return gemm_impl(desc_host, stream, nullptr, job_host);
+    job_host->splits = 0;
+    return gemm_single(desc_host, job_host, nullptr, stream, nullptr);
 }
 
-int rlx_gemm_pair_defer(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc *input_grad,
-                        rlx_splitk_job *weight_grad_job_host, void *stream) {
-    RLX_REQUIRE(weight_grad_job_host != nullptr, "rlx_gemm_pair_defer: null job");
-    return gemm_pair_impl(weight_grad, input_grad, stream, weight_grad_job_host);
-}
-
-int rlx_splitk_reduce_jobs(const rlx_splitk_job *jobs_host, int n_jobs, void *stream) {
+// the outstanding jobs among jobs_host, validated, and their grid: (x, y) covers the largest of them, z counts them
+static int collect_reduce_jobs(const rlx_splitk_job *jobs_host, int n_jobs, const char *who, ReduceJobs *jobs, dim3 *grid) {
     RLX_REQUIRE(jobs_host && n_jobs >= 0 && n_jobs <= RLX_MAX_SPLITK_JOBS,
-                "rlx_splitk_reduce_jobs: 0..%d jobs (got %d)", RLX_MAX_SPLITK_JOBS, n_jobs);
-    ReduceJobs jobs;
+                "%s: 0..%d jobs (got %d)", who, RLX_MAX_SPLITK_JOBS, n_jobs);
     int n = 0, gx = 1, gy = 1;
     for (int i = 0; i < n_jobs; ++i) {
         const rlx_splitk_job &j = jobs_host[i];
         if (j.splits <= 1) continue;
         RLX_REQUIRE(j.partials && j.C && j.M > 0 && j.N > 0 && j.N % 4 == 0 && j.batch > 0 &&
                     (long long)j.M * j.N < (1LL << 31) && aligned16(j.partials),
-                    "rlx_splitk_reduce_jobs: job %d is not a float4-reducible product", i);
-        jobs.job[n++] = j;
+                    "%s: job %d is not a float4-reducible product", who, i);
+        jobs->job[n++] = j;
         const int bx = (int)(((long long)j.M * j.N / 4 + 63) / 64);
         gx = bx > gx ? bx : gx;
         gy = j.batch > gy ? j.batch : gy;
     }
-    if (n == 0) return RLX_OK;
-    RLX_LAUNCH((splitk_reduce_jobs_kernel), dim3(gx, gy, n), 1024, 0, rlx::as_stream(stream), jobs);
+    *grid = dim3(gx, gy, n);
+    return RLX_OK;
+}
+
+int rlx_splitk_reduce_jobs(const rlx_splitk_job *jobs_host, int n_jobs, void *stream) {
+    RLX_REQUIRE(jobs_host && n_jobs >= 0 && n_jobs <= RLX_MAX_SPLITK_JOBS,
+                "rlx_splitk_reduce_jobs: 0..%d jobs (got %d)", RLX_MAX_SPLITK_JOBS, n_jobs);
+    ReduceJobs jobs;
+    dim3 grid;
+    const int rc = collect_reduce_jobs(jobs_host, n_jobs, "rlx_splitk_reduce_jobs", &jobs, &grid);
+    if (rc != RLX_OK || grid.z == 0) return rc;
+    RLX_LAUNCH((splitk_reduce_jobs_kernel), grid, 1024, 0, rlx::as_stream(stream), jobs);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }
@@ -2816,9 +2836,9 @@ int rlx_ppo_fc_rows_supported(const rlx_gemm_desc *fc, int n_actions) {
     if (!fc || fc->row_heads || fc->batch != 2 || fc->N % 4 != 0 || fc->N > 1024 || fc->M > 256 || n_actions < 2 ||
         n_actions > rlx_small::kMaxN || fc->ldc != fc->N || fc->n_fold > 0 || fc->colsum_out)
         return 0;
-    GemmPlan plan{};
-    if (gemm_impl(fc, nullptr, &plan, nullptr) != RLX_OK) return 0;
-    return plan.q_splits > 16 ? 1 : 0;
+    GemmPlan p;
+    if (plan_gemm(fc, PlanFor::Member, &p) != RLX_OK) return 0;
+    return p.splits > 16 ? 1 : 0;
 }
 
 int rlx_ppo_fc_rows(const rlx_gemm_desc *fc, const rlx_ppo_rows_desc *rows, void *stream) {
@@ -2831,12 +2851,10 @@ int rlx_ppo_fc_rows(const rlx_gemm_desc *fc, const rlx_ppo_rows_desc *rows, void
     rlx_gemm_desc d = *fc;
     d.row_heads = heads;
     d.n_row_heads = 2;
-    tl_row_heads_done = false;
-    tl_ppo_rows = rows;
-    const int rc = gemm_impl(&d, stream, nullptr);
-    tl_ppo_rows = nullptr;
+    bool heads_ran = false;
+    const int rc = gemm_single(&d, nullptr, rows, stream, &heads_ran);
     if (rc != RLX_OK) return rc;
-    RLX_REQUIRE(tl_row_heads_done, "rlx_ppo_fc_rows: the product did not take the row-finishing reduction");
+    RLX_REQUIRE(heads_ran, "rlx_ppo_fc_rows: the product did not take the row-finishing reduction");
     return RLX_OK;
 }
 
@@ -2860,24 +2878,14 @@ int rlx_splitk_reduce_jobs_ppo_tail(const rlx_splitk_job *jobs_host, int n_jobs,
     const int rc0 = ppo_rows_check(rows, "rlx_splitk_reduce_jobs_ppo_tail");
     if (rc0 != RLX_OK) return rc0;
     ReduceJobs jobs;
-    int n = 0, gx = 1, gy = 1;
-    for (int i = 0; i < n_jobs; ++i) {
-        const rlx_splitk_job &j = jobs_host[i];
-        if (j.splits <= 1) continue;
-        RLX_REQUIRE(j.partials && j.C && j.M > 0 && j.N > 0 && j.N % 4 == 0 && j.batch > 0 &&
-                    (long long)j.M * j.N < (1LL << 31) && aligned16(j.partials),
-                    "rlx_splitk_reduce_jobs_ppo_tail: job %d is not a float4-reducible product", i);
-        jobs.job[n++] = j;
-        const int bx = (int)(((long long)j.M * j.N / 4 + 63) / 64);
-        gx = bx > gx ? bx : gx;
-        gy = j.batch > gy ? j.batch : gy;
-    }
+    dim3 grid;
+    const int rc = collect_reduce_jobs(jobs_host, n_jobs, "rlx_splitk_reduce_jobs_ppo_tail", &jobs, &grid);
+    if (rc != RLX_OK) return rc;
+    const int n = (int)grid.z;
     if (n == 0) return rlx_ppo_heads_tail(rows, stream);
     const PpoTailDev t = ppo_tail_dev(*rows);
-    const int kb = (rows->value_head.K + rlx_small::kKL - 1) / rlx_small::kKL;
-    gx = kb > gx ? kb : gx;
-    gy = gy < 2 ? 2 : gy;
-    dim3 grid(gx, gy, n + 1);
+    const unsigned kb = (rows->value_head.K + rlx_small::kKL - 1) / rlx_small::kKL;
+    grid = dim3(kb > grid.x ? kb : grid.x, grid.y < 2 ? 2 : grid.y, n + 1);
     hipStream_t s = rlx::as_stream(stream);
     if (t.nn == 4) RLX_LAUNCH((splitk_reduce_jobs_tail_kernel<4>), grid, 1024, 0, s, jobs, n, t);
     else if (t.nn == 8) RLX_LAUNCH((splitk_reduce_jobs_tail_kernel<8>), grid, 1024, 0, s, jobs, n, t);
@@ -2890,42 +2898,35 @@ static int gemm_pair_impl(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc 
                           rlx_splitk_job *defer) {
     if (defer) defer->splits = 0;
     GemmPlan pw, px;
-    int rc = gemm_impl(weight_grad, stream, &pw);
+    int rc = plan_gemm(weight_grad, PlanFor::Member, &pw);
+    if (rc == RLX_OK) rc = plan_gemm(input_grad, PlanFor::Member, &px);
     if (rc != RLX_OK) return rc;
-    rc = gemm_impl(input_grad, stream, &px);
-    if (rc != RLX_OK) return rc;
-    const bool pairable = pw.tiled_fast && (px.tiled_fast || px.kw > 1) &&
-                          !pw.a_vec_red && !pw.u8 && !pw.b_vec_red &&                 // X^T dY
-                          px.a_vec_red && !px.u8 && px.b_vec_red && !px.a_tab &&       // dY W^T
-                          true;
-    if (pw.thin && px.thin && !pw.a_ck && pw.b_cn && px.a_ck && !px.b_cn) {
-        GemmPairDev p;
-        p.g[0] = pw.g; p.g[1] = px.g;
-        p.gx[0] = pw.grid.x; p.gy[0] = pw.grid.y; p.gx[1] = px.grid.x; p.gy[1] = px.grid.y;
-        p.n0 = (int)(pw.grid.x * pw.grid.y * pw.grid.z);
-        p.t16[0] = pw.t16; p.t16[1] = px.t16;
-        const unsigned total = (unsigned)p.n0 + px.grid.x * px.grid.y * px.grid.z;
-        RLX_LAUNCH((gemm_thin_pair_kernel), total, kThreads, 0, rlx::as_stream(stream), p);
-        RLX_LAUNCH_CHECK();
-        return RLX_OK;
-    }
+    const bool orient = !pw.a_vec_red && !pw.b_vec_red && px.a_vec_red && px.b_vec_red;       // X^T dY and dY W^T
+    const bool thin_pair = !pw.refolded && !px.refolded && is_thin(pw.path) && is_thin(px.path) && orient;
+    // (px has no tables: where pw may take the ring, px may too — pw.ring is the pair's)
+    const bool pairable = member_tiled(pw, false) && pw.kw == 1 && member_tiled(px, false) && orient &&
+                          !pw.u8 && !px.u8 && !px.a_tab;
     // both problems may split K: their partials must not share workspace memory
     const bool ws_clash = pw.splits > 1 && px.splits > 1 && pw.g.ws == px.g.ws;
-    if (!pairable || ws_clash) {
-        rc = gemm_impl(weight_grad, stream, nullptr, defer);
-        if (rc != RLX_OK) return rc;
-        return gemm_impl(input_grad, stream, nullptr);
+    if (!thin_pair && (!pairable || ws_clash)) {      // two launches of their own
+        rc = gemm_single(weight_grad, defer, nullptr, stream, nullptr);
+        return rc != RLX_OK ? rc : gemm_single(input_grad, nullptr, nullptr, stream, nullptr);
     }
     GemmPairDev p;
     p.g[0] = pw.g; p.g[1] = px.g;
     p.gx[0] = pw.grid.x; p.gy[0] = pw.grid.y; p.gx[1] = px.grid.x; p.gy[1] = px.grid.y;
     p.n0 = (int)(pw.grid.x * pw.grid.y * pw.grid.z);
-    p.t16[0] = p.t16[1] = 0;
+    p.t16[0] = thin_pair && pw.path == Path::Thin16; p.t16[1] = thin_pair && px.path == Path::Thin16;
     const unsigned total = (unsigned)p.n0 + px.grid.x * px.grid.y * px.grid.z;
     hipStream_t s = rlx::as_stream(stream);
+    if (thin_pair) {
+        RLX_LAUNCH((gemm_thin_pair_kernel), total, kThreads, 0, s, p);
+        RLX_LAUNCH_CHECK();
+        return RLX_OK;
+    }
 #define RLX_PAIR_CASE(AT, KWX)                                                                   \
     if (pw.a_tab == AT && px.kw == KWX) {                                                        \
-        if (g_dma && (!AT || pw.g.kchunk <= kDmaTabChunk))                                       \
+        if (pw.ring)                                                                             \
             RLX_LAUNCH((gemm_dma_pair_kernel<AT, KWX>), total, kThreads, 0, s, p);               \
         else RLX_LAUNCH((gemm_fast_pair_kernel<AT, KWX>), total, kThreads, 0, s, p);             \
     }
@@ -2933,16 +2934,18 @@ static int gemm_pair_impl(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc 
     RLX_PAIR_CASE(false, 1) RLX_PAIR_CASE(false, 2) RLX_PAIR_CASE(false, 4)
 #undef RLX_PAIR_CASE
     RLX_LAUNCH_CHECK();
-    if (pw.splits > 1) {
-        if (defer && deferrable(pw.g, pw.M, pw.N)) {
-            fill_job(defer, pw.g, pw.M, pw.N, pw.batch, pw.splits);
-        } else {
-            rc = launch_splitk_reduce(pw.g, pw.M, pw.N, pw.batch, pw.splits, s);
-            if (rc != RLX_OK) return rc;
-        }
-    }
-    if (px.splits > 1) return launch_splitk_reduce(px.g, px.M, px.N, px.batch, px.splits, s);
-    return RLX_OK;
+    rc = finish_product(pw, defer, false, nullptr, s, nullptr);
+    return rc != RLX_OK ? rc : finish_product(px, nullptr, false, nullptr, s, nullptr);
+}
+
+int rlx_gemm_pair(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc *input_grad, void *stream) {
+    return gemm_pair_impl(weight_grad, input_grad, stream, nullptr);
+}
+
+int rlx_gemm_pair_defer(const rlx_gemm_desc *weight_grad, const rlx_gemm_desc *input_grad,
+                        rlx_splitk_job *weight_grad_job_host, void *stream) {
+    RLX_REQUIRE(weight_grad_job_host != nullptr, "rlx_gemm_pair_defer: null job");
+    return gemm_pair_impl(weight_grad, input_grad, stream, weight_grad_job_host);
 }
 
 int rlx_gemm_multi_defer(const rlx_gemm_desc *descs_host, int n, rlx_splitk_job *jobs_host, void *stream) {
@@ -2951,20 +2954,19 @@ int rlx_gemm_multi_defer(const rlx_gemm_desc *descs_host, int n, rlx_splitk_job 
     bool multi = n >= 2 && g_dma != 0;
     for (int i = 0; i < n; ++i) {
         jobs_host[i].splits = 0;
-        pl[i].allow_fold = true;
-        const int rc = gemm_impl(&descs_host[i], stream, &pl[i]);
+        const int rc = plan_gemm(&descs_host[i], PlanFor::Member, &pl[i]);
         if (rc != RLX_OK) return rc;
-        // what the one-launch form takes: 64 x 64 tiles, A^T gathered through im2col tables (vector along the outer
-        // index), B along N; fp32 on the ring (its table chunk bound) or uint8 on the register-staged loop
-        multi = multi && pl[i].tiled_fast && !pl[i].a_vec_red && !pl[i].b_vec_red && pl[i].a_tab &&
-                (pl[i].u8 ? pl[i].g.kchunk <= kTabChunk : pl[i].g.kchunk <= kDmaTabChunk);
+        // what the one-launch form takes: 64 x 64 tiles (towers folded into N too), A^T gathered through im2col tables (vector
+        // along the outer index), B along N; fp32 on the ring, or uint8 on the register-staged loop (any fast table chunk)
+        multi = multi && member_tiled(pl[i], true) && pl[i].kw == 1 && !pl[i].a_vec_red && !pl[i].b_vec_red && pl[i].a_tab &&
+                (pl[i].u8 || pl[i].ring);
     }
     for (int i = 0; multi && i < n; ++i)
         for (int j = i + 1; j < n; ++j)
             if (pl[i].splits > 1 && pl[j].splits > 1 && pl[i].g.ws == pl[j].g.ws) multi = false;   // partials would collide
-    if (!multi) {
+    if (!multi) {                                     // launches of their own
         for (int i = 0; i < n; ++i) {
-            const int rc = gemm_impl(&descs_host[i], stream, nullptr, &jobs_host[i]);
+            const int rc = gemm_single(&descs_host[i], &jobs_host[i], nullptr, stream, nullptr);
             if (rc != RLX_OK) return rc;
         }
         return RLX_OK;
@@ -2983,13 +2985,8 @@ int rlx_gemm_multi_defer(const rlx_gemm_desc *descs_host, int n, rlx_splitk_job 
     RLX_LAUNCH((gemm_multi_dw_kernel), (unsigned)p.start[n], kThreads, 0, s, p);
     RLX_LAUNCH_CHECK();
     for (int i = 0; i < n; ++i) {
-        if (pl[i].splits <= 1) continue;
-        if (deferrable(pl[i].g, pl[i].M, pl[i].N)) {
-            fill_job(&jobs_host[i], pl[i].g, pl[i].M, pl[i].N, pl[i].batch, pl[i].splits);
-        } else {
-            const int rc = launch_splitk_reduce(pl[i].g, pl[i].M, pl[i].N, pl[i].batch, pl[i].splits, s);
-            if (rc != RLX_OK) return rc;
-        }
+        const int rc = finish_product(pl[i], &jobs_host[i], false, nullptr, s, nullptr);
+        if (rc != RLX_OK) return rc;
     }
     return RLX_OK;
 }

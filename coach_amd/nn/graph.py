@@ -180,7 +180,7 @@ def _fused_operands_aligned(args):
 
 
 def _tiled_wave_groups(M, N, batch):
-    """How rlx_gemm would tile an M x N x K product of `batch` towers (csrc/gemm.hip gemm_impl, with the LIVE thresholds of
+    """How rlx_gemm would tile an M x N x K product of `batch` towers (csrc/gemm.hip plan_gemm, with the LIVE thresholds of
     rlx_gemm_tuning: 192 / 192 unless an A/B tool changed them): 2 = 32 x 64 tiles with the K slab split over two wave
     groups, 4 = 32 x 32 tiles with four, 1 = anything else (64 x 64 tiles, narrow tiles, K split over workgroups)."""
     if N <= 32:

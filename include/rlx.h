@@ -522,7 +522,12 @@ int rlx_gemm_tuning_get(int *kw_below_tiles, int *kw_min_tiles, int *xcd_mode);
  * paths, the other fields are then meaningless), tile rows, tile columns, wave groups per K slab, K chunks over workgroups
  * (> 1: partials + a reduce launch), chunk length, operands through the LDS-DMA ring (0: staged by registers — the order
  * of the fp32 sum inside a slab differs, see rlx_gemm_pipeline), thin kernel}.  For callers that replace a launch by a
- * fused one ONLY where the sums stay bit-identical (rlx_conv123_forward). */
+ * fused one ONLY where the sums stay bit-identical (rlx_conv123_forward).  The answer is the plan of the product as one
+ * member of a combined grid (rlx_gemm_pair, rlx_gemm_multi_defer) — the summation order, which is what such callers ask
+ * about.  A launch of its own differs from it in two ways that leave every sum as it is: a product of at least 256 tiles
+ * of 128 x 128 runs on those (rlx_gemm_big_tiles: bit-identical to the 64 x 64 tiling reported here), and the thin kernel
+ * takes its 16 x 16 tiles up to twice as many 32 x 32 tiles.  All zeros: towers folded into N (n_fold) that have to run
+ * as the equivalent batched product. */
 int rlx_gemm_describe(const rlx_gemm_desc *desc, int *out8);
 /* Main loop of the fast tiled kernels: 1 (default) = operand slabs go global -> LDS by DMA into a ring of two buffers,
  * one barrier per slab, three workgroups per CU (csrc/gemm.hip gemm_dma_body); 0 = the register-staged two-set pipeline

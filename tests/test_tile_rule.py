@@ -1,5 +1,5 @@
 """Host logic of the fused-convolution path (no GPU): nn.graph._kw2_tiling mirrors rlx_gemm's tile rule (csrc/gemm.hip
-gemm_impl) with the library's LIVE thresholds — rlx_conv23_forward is taken exactly where the two tiled launches would run
+plan_gemm) with the library's LIVE thresholds — rlx_conv23_forward is taken exactly where the two tiled launches would run
 on 32 x 64 tiles with two wave groups per K slab (there its sums are bit-identical to theirs)."""
 import ctypes
 
