@@ -338,6 +338,15 @@ class VectorOffPolicyAgent(GraphRunner):
         kw = dict(device=self.device, n_env=self.n_env, observation_shape=ep.observation_shape,
                   stack=self.stack, action_dim=action_dim,
                   min_episode_length=getattr(ep, "min_episode_length", self.L))
+        if isinstance(mp, PrioritizedExperienceReplayParameters) and \
+                getattr(self.ap.algorithm, "store_transitions_only_when_episodes_are_terminated", False):
+            # whole episodes, processed for n-step targets when they end (agent.py:558-584), into the prioritized replay
+            from ..memories.non_episodic.nstep_prioritized_experience_replay import NStepPrioritizedExperienceReplay
+            alg = self.ap.algorithm
+            return NStepPrioritizedExperienceReplay(mp.max_size, mp.alpha, mp.beta, mp.epsilon,
+                                                    mp.allow_duplicates_in_batch_sampling,
+                                                    exact_pow=getattr(mp, "exact_pow", "device"), n_step=alg.n_step,
+                                                    discount=alg.discount, max_episode_length=self.L, **kw)
         if isinstance(mp, PrioritizedExperienceReplayParameters):
             return PrioritizedExperienceReplay(mp.max_size, mp.alpha, mp.beta, mp.epsilon,
                                                mp.allow_duplicates_in_batch_sampling,

@@ -67,6 +67,18 @@ class CategoricalQHeadParameters(HeadParameters):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
 
 
+class RainbowQHeadParameters(HeadParameters):
+    """RainbowQHeadParameters (head_parameters.py:215-222): a dueling head over atoms — a state-value stream
+    Dense(512, activation) -> Dense(atoms) and an action-advantage stream Dense(512, activation) -> Dense(A * atoms),
+    merged per atom, with a softmax over the atoms (heads/rainbow_q_head.py:38-70).  The merge, the projection, the cross
+    entropy and the gradients of the two stream outputs come from rlx_rainbow_head_loss."""
+    head_type = "RainbowQHead"
+
+    def __init__(self, activation_function='relu', name='rainbow_q_head_params',
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
 class NAFHeadParameters(HeadParameters):
     """NAFHeadParameters (head_parameters.py:152-159): three Dense layers on the middleware's output — V (1),
     mu_unscaled (A, this activation, then times the action space's max_abs_range) and l_vector (A(A+1)/2), read as a

@@ -22,7 +22,7 @@ def _tensors_of(obj, names):
 
 _MEMORY_TENSORS = ["ring", "fpos", "epoff", "t_fpos", "t_epoff", "cur_state", "obs", "next_obs", "action",
                    "reward", "game_over", "mask", "sum_tree", "min_tree", "max_tree", "max_priority",
-                   "n_step_discounted_rewards", "act_value", "act_probs",
+                   "n_step_discounted_rewards", "should_bootstrap_next_state", "act_value", "act_probs",
                    "measurements", "future_measurements"]      # DFP: the states' measurements and their future targets
 _MEMORY_SCALARS = ["cursor", "count", "pending", "committed_total", "steps", "_open", "_list_len",
                    "next_leaf_idx_to_write", "_frames_total", "_episode_steps", "_step_frames",

@@ -24,6 +24,8 @@ _FOLDED = {
     # the backend's layer classes (Dense, Conv2d, NoisyNetDense): presets name them in schemes
     "architectures.tensorflow_components.layers": "architectures.layers",
     "architectures.tensorflow_components": "architectures",     # (the parent package of the line above; longer entries first)
+    # Rainbow DQN lives in agents/rainbow_agent.py (agents/rainbow_dqn_agent.py keeps a refusing class of the same name)
+    "agents.rainbow_dqn_agent": "agents.rainbow_agent",
 }
 
 

@@ -14,7 +14,7 @@
 // (an fp64 exp rounded once is the correctly rounded fp32 exp but for double-rounding cases of probability ~2^-29).
 // The Q value of an action is fp64: q = sum_{j ascending} (double)p_j * z_j, z the host's np.linspace (numpy's dot may
 // associate differently: a few ulp).  Compiled with -ffp-contract=off so the fp64 arithmetic rounds like numpy.
-#include "distributional_head.hpp"
+#include "categorical_head.hpp"
 
 namespace {
 
@@ -22,36 +22,8 @@ constexpr int kC51Threads = rlx::kDistLossThreads;
 constexpr int kC51MaxAtoms = rlx::kDistLossThreads;   // one thread per atom
 constexpr int kC51MaxActions = rlx::kDistMaxActions;
 
-// Softmax of `rows` rows of N values held in LDS, in place.  mx[r] / sum[r] keep each row's maximum and fp32 sum of
-// exponentials.  The serial parts (maximum, sum in atom order) are one thread per row; the exponentials and the
-// divisions are spread over the workgroup.  Ends with a barrier.
-template <int THREADS>
-__device__ __forceinline__ void softmax_rows(float *x, float *mx, float *sum, int rows, int N, int t) {
-    if (t < rows) {
-        const float *r = x + t * N;
-        float m = r[0];
-        for (int j = 1; j < N; ++j) m = fmaxf(m, r[j]);
-        mx[t] = m;
-    }
-    __syncthreads();
-    for (int c = t; c < rows * N; c += THREADS) x[c] = (float)exp((double)(x[c] - mx[c / N]));
-    __syncthreads();
-    if (t < rows) {
-        const float *r = x + t * N;
-        float s = 0.f;
-        for (int j = 0; j < N; ++j) s += r[j];
-        sum[t] = s;
-    }
-    __syncthreads();
-    for (int c = t; c < rows * N; c += THREADS) x[c] = x[c] / sum[c / N];
-    __syncthreads();
-}
-
-__device__ __forceinline__ double expectation(const float *p, const double *z, int N) {
-    double q = 0.0;
-    for (int j = 0; j < N; ++j) q += (double)p[j] * z[j];
-    return q;
-}
+using rlx::expectation;
+using rlx::softmax_rows;
 
 struct C51Args {
     const float *logits;        // online output on s [B, ld_logits]
@@ -116,30 +88,14 @@ __global__ void __launch_bounds__(kC51Threads) c51_head_loss_kernel(const C51Arg
     __syncthreads();
 
     // the projection (categorical_dqn_agent.py:141-149), fp64.  Thread j forms atom j's two contributions ...
-    if (t < N) {
-        const double z0 = z_s[0], zl = z_s[N - 1];
-        const double tz = fmax(fmin((double)a.rewards[b] + (1.0 - (a.game_overs[b] ? 1.0 : 0.0)) * a.discount * z_s[t],
-                                    zl), z0);
-        const double bj = (tz - z0) / (z_s[1] - z0);
-        const double lo = floor(bj), up = ceil(bj);
-        const double p = (double)pn[best_s * N + t];
-        l_s[t] = (int)lo;
-        u_s[t] = (int)up;
-        wl_s[t] = p * (up - bj);      // both are 0 when bj is an integer: that atom's mass is dropped, as in the reference
-        wu_s[t] = p * (bj - lo);
-    }
+    if (t < N)
+        rlx::project_scatter(z_s, N, t, (double)a.rewards[b], (1.0 - (a.game_overs[b] ? 1.0 : 0.0)) * a.discount,
+                             (double)pn[best_s * N + t], l_s, u_s, wl_s, wu_s);
     __syncthreads();
-    // ... and thread k, which owns output atom k, adds them in the reference's order: j ascending, the l-term then the
-    // u-term.  No atomics: m is bit-identical to the Python loop.  Rounded to fp32 once (the fp32 target array).
-    // On a support whose (z_{N-1} - z_0) / (z_1 - z_0) rounds above N - 1 (linspace(-10, 10, 256); not the default 51
-    // atoms) an atom clipped at v_max has u == N, where the reference raises IndexError: no thread owns that atom, so
-    // the contribution (weight bj - l, a rounding error) is left out and nothing is written out of bounds.
+    // ... and thread k, which owns output atom k, adds them in the reference's order (categorical_head.hpp); rounded to
+    // fp32 once (the fp32 target array).
     if (t < N) {
-        double acc = 0.0;
-        for (int j = 0; j < N; ++j) {
-            if (l_s[j] == t) acc += wl_s[j];
-            if (u_s[j] == t) acc += wu_s[j];
-        }
+        const double acc = rlx::project_gather(N, t, l_s, u_s, wl_s, wu_s);
         m_s[t] = (float)acc;
         if (a.m_out) a.m_out[(size_t)b * N + t] = (float)acc;
     }
@@ -177,8 +133,8 @@ __global__ void __launch_bounds__(kC51Threads) c51_head_loss_kernel(const C51Arg
     if (t == 0) a.loss[0] = red[0];
 }
 
-// One wave per env: the softmax of each action's logits in LDS, lanes a < A form the fp64 expectations, lane 0 makes
-// the epsilon-greedy choice on them (distributional_head.hpp).
+// One wave per env: categorical_act_q (categorical_head.hpp) forms the fp64 expectations, lane 0 makes the
+// epsilon-greedy choice on them (distributional_head.hpp).
 __global__ void __launch_bounds__(64) categorical_egreedy_kernel(const float *__restrict__ logits, long long ld,
                                                                  const double *__restrict__ z, int n_atoms,
                                                                  const double *__restrict__ explore_u,
@@ -186,21 +142,9 @@ __global__ void __launch_bounds__(64) categorical_egreedy_kernel(const float *__
                                                                  const double *__restrict__ tie_rand, double epsilon,
                                                                  int n_actions, double *__restrict__ q_out,
                                                                  int *__restrict__ actions) {
-    __shared__ float p_s[kC51MaxActions * kC51MaxAtoms];
-    __shared__ double z_s[kC51MaxAtoms];
-    __shared__ float mx_s[kC51MaxActions], sum_s[kC51MaxActions];
     __shared__ double q[kC51MaxActions];
-    const int e = blockIdx.x, t = threadIdx.x, N = n_atoms, A = n_actions;
-    const float *x = logits + (size_t)e * ld;
-    for (int c = t; c < A * N; c += 64) p_s[c] = x[c];
-    for (int j = t; j < N; j += 64) z_s[j] = z[j];
-    __syncthreads();
-    softmax_rows<64>(p_s, mx_s, sum_s, A, N, t);
-    if (t < A) {
-        q[t] = expectation(p_s + t * N, z_s, N);
-        if (q_out) q_out[(size_t)e * A + t] = q[t];
-    }
-    __syncthreads();
+    const int e = blockIdx.x, t = threadIdx.x, A = n_actions;
+    rlx::categorical_act_q<false>(nullptr, logits + (size_t)e * ld, z, n_atoms, A, e, t, q_out, q);
     if (t == 0)
         actions[e] = rlx::egreedy_choice_f64(q, A, explore_u[e], random_act[e], tie_rand + (size_t)e * A, epsilon);
 }
@@ -210,21 +154,9 @@ __global__ void __launch_bounds__(64) categorical_egreedy_kernel(const float *__
 __global__ void __launch_bounds__(64) categorical_argmax_kernel(const float *__restrict__ logits, long long ld,
                                                                 const double *__restrict__ z, int n_atoms, int n_actions,
                                                                 double *__restrict__ q_out, int *__restrict__ actions) {
-    __shared__ float p_s[kC51MaxActions * kC51MaxAtoms];
-    __shared__ double z_s[kC51MaxAtoms];
-    __shared__ float mx_s[kC51MaxActions], sum_s[kC51MaxActions];
     __shared__ double q[kC51MaxActions];
-    const int e = blockIdx.x, t = threadIdx.x, N = n_atoms, A = n_actions;
-    const float *x = logits + (size_t)e * ld;
-    for (int c = t; c < A * N; c += 64) p_s[c] = x[c];
-    for (int j = t; j < N; j += 64) z_s[j] = z[j];
-    __syncthreads();
-    softmax_rows<64>(p_s, mx_s, sum_s, A, N, t);
-    if (t < A) {
-        q[t] = expectation(p_s + t * N, z_s, N);
-        if (q_out) q_out[(size_t)e * A + t] = q[t];
-    }
-    __syncthreads();
+    const int e = blockIdx.x, t = threadIdx.x, A = n_actions;
+    rlx::categorical_act_q<false>(nullptr, logits + (size_t)e * ld, z, n_atoms, A, e, t, q_out, q);
     if (t == 0) actions[e] = rlx::first_argmax_f64(q, A);
 }
 

@@ -73,9 +73,7 @@ class ExperienceReplay(Memory):
         self.device, self.n_env = device, int(n_env)
         self.allow_duplicates_in_batch_sampling = allow_duplicates_in_batch_sampling
         cap = int(max_size[1])
-        if cap <= 0 or cap % self.n_env:
-            raise ValueError("replay capacity %d must be a positive multiple of the %d lockstep envs"
-                             % (cap, self.n_env))
+        self._check_capacity(cap)
         self.cap = cap
         # physical rows: the capacity plus one vector step that is written but not visible yet
         rows = self.rows = self._physical_rows(cap, self.n_env)
@@ -127,6 +125,13 @@ class ExperienceReplay(Memory):
         self._frames_total = 0
         self._step_frames = np.zeros(rows // self.n_env, dtype=np.int64)
         self._episode_steps = 0
+
+    def _check_capacity(self, cap):
+        """a vector step appends n_env rows: the capacity is a multiple of it (a subclass that appends whole episodes
+        of single envs asks only for a positive one)"""
+        if cap <= 0 or cap % self.n_env:
+            raise ValueError("replay capacity %d must be a positive multiple of the %d lockstep envs"
+                             % (cap, self.n_env))
 
     def _physical_rows(self, cap, n_env):
         return cap + n_env

@@ -937,6 +937,90 @@ class C51Net(DistributionalDQNNet):
                                target_actions_out, action_losses_out, self.ctx.stream)
 
 
+class RainbowNet(_OwnHeadLossDQNNet):
+    """RainbowDQNNetworkParameters (agents/rainbow_dqn_agent.py:32-36): the DQN torso under a RainbowQHead
+    (heads/rainbow_q_head.py:38-70) — a state-value stream Dense(feat, 512, act) -> Dense(512, atoms) and an
+    action-advantage stream Dense(feat, 512, act) -> Dense(512, A * atoms), four layers of their own (NoisyDense when the
+    network is noisy: each draws its own noise).  The merge per atom, the softmaxes, the Double-DQN target action, the
+    n-step projection, the cross entropy and the gradients of the two stream outputs come from rlx_rainbow_head_loss
+    (csrc/rainbow.hip); acting reduces the two stream outputs with rlx_rainbow_argmax / rlx_rainbow_egreedy."""
+
+    def __init__(self, device, obs_shape, n_actions, atoms, v_min=-10.0, v_max=10.0, **kw):
+        kw.pop("replace_mse_with_huber_loss", None)
+        kw.pop("dueling", None)
+        self._head_shape = (int(n_actions), int(atoms), kw.get("head_activation", "relu"))
+        super().__init__(device, obs_shape, n_actions * atoms, dueling=False, **kw)
+        self.A, self.N, self.AN = n_actions, int(atoms), n_actions * int(atoms)
+        self.loss_ws = torch.zeros(256, dtype=torch.float32, device=device)      # per-row loss partials
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+        # the support, as the reference agent and head build it (fp64 on the host), uploaded once
+        self.z_values = np.linspace(v_min, v_max, self.N)
+        self.z = torch.from_numpy(self.z_values).to(device)
+
+    def _q_head_layer(self, feat, units):
+        """the head's four layers, in forward order (the constructor keeps them as one module: `q_head`)"""
+        A, N, act = self._head_shape
+        Dense = G.NoisyDense if self.noisy else G.Dense
+        hn = "main/rainbow_q_values_head"
+        self.v_fc = Dense(self.params, hn + "/state_value/fc1", feat, 512, act)
+        self.v_out = Dense(self.params, hn + "/state_value/fc2", 512, N, None)
+        self.a_fc = Dense(self.params, hn + "/action_advantage/fc1", feat, 512, act)
+        self.a_out = Dense(self.params, hn + "/action_advantage/fc2", 512, A * N, None)
+        return G.Sequential([self.v_fc, self.v_out, self.a_fc, self.a_out])
+
+    def _streams_forward(self, feat, tag, weights=None):
+        ctx = self.ctx
+        hv = self.v_fc.forward(ctx, feat, tag=tag, weights=weights)
+        ha = self.a_fc.forward(ctx, feat, tag=tag, weights=weights)
+        return hv, ha, self.v_out.forward(ctx, hv, tag=tag, weights=weights), \
+            self.a_out.forward(ctx, ha, tag=tag, weights=weights)
+
+    def head_streams(self, obs, B, use_target=False, tag="q", noise_pass="act"):
+        """-> (v, x): the two streams' Dense outputs, Tensors whose .data are [1, B, atoms] and [1, B, A * atoms]; every
+        pass of a noisy network samples its own noise (noise_pass)."""
+        w = self.target if use_target else None
+        self.sample_noise(tag, noise_pass)
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=w)
+        return self._streams_forward(acts[-1], tag, w)[2:]
+
+    def q_values(self, *args, **kw):
+        raise NotImplementedError("RainbowNet has no Q-value output: head_streams and the rlx_rainbow_* reductions")
+
+    def learn_from_batch(self, obs, next_obs, B, actions, n_step_returns, bootstrap, discount_n, grad_scale=1.0,
+                         sync=None, per_errors=None, m_out=None, target_actions_out=None, action_losses_out=None,
+                         merged_logits_out=None, dlogits_out=None):
+        """RainbowDQNAgent.learn_from_batch (agents/rainbow_dqn_agent.py:88-137), all on device: the online network on
+        s' (the Double-DQN choice), the target network on s', the online network on s, rlx_rainbow_head_loss, the
+        backward pass through the four head layers into the torso, clip, Adam.  n_step_returns fp64 [B], bootstrap u8 [B]:
+        the replay's two n-step columns; discount_n: the host's discount ** n_step."""
+        ctx, N, AN = self.ctx, self.N, self.AN
+        vn, xn = self.head_streams(next_obs, B, tag="next_o", noise_pass="online_next")
+        vt, xt = self.head_streams(next_obs, B, use_target=True, tag="next_t", noise_pass="target")
+        self.sample_noise("train", "online")
+        acts = self.torso.forward(ctx, self.obs_tensor(obs, B), tag="train")
+        feat = acts[-1]
+        hv, ha, v, x = self._streams_forward(feat, "train")
+        self.lib.rainbow_head_loss(v.data, N, x.data, AN, vt.data, N, xt.data, AN, vn.data, N, xn.data, AN, self.z,
+                                   actions, n_step_returns, bootstrap, float(discount_n), N, self.A, B, 1.0,
+                                   v.ensure_grad(), N, x.ensure_grad(), AN, per_errors, self.loss_ws, self.ticket,
+                                   self.loss, self.status, m_out, target_actions_out, action_losses_out,
+                                   merged_logits_out, dlogits_out, ctx.stream)
+        self.v_out.backward(ctx, hv, v)
+        self.a_out.backward(ctx, ha, x)
+        # the two streams' input gradients (each already times act'(feat)) add up in feat.grad
+        side = G.Tensor(feat.data, feat.rows, feat.cols, 1, act=feat.act)
+        side.grad = ctx.buffer("main/rainbow_q_values_head/side:grad", tuple(feat.data.shape))
+        self.v_fc.backward(ctx, feat, hv)
+        self.a_fc.backward(ctx, side, ha)
+        g = feat.grad
+        self.lib.axpby(g, 1.0, g, 1.0, side.grad, g.numel(), ctx.stream)
+        if self.head_gradient_rescale != 1.0:         # rescale_gradient_from_head_by_factor
+            self.lib.axpby(g, self.head_gradient_rescale, g, 0.0, None, g.numel(), ctx.stream)
+        self.torso.backward(ctx, acts)
+        self._apply_update(grad_scale, sync)
+        return self.loss
+
+
 class _HeadCopiesDense(G.Dense):
     """Dense(feat, copies * units) whose column block h is copy h of a head's Dense(feat, units): every block is
     initialised as that layer of its own would be — glorot uniform with fan-out `units`, one draw per copy, in copy

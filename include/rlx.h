@@ -1024,6 +1024,61 @@ int rlx_categorical_egreedy(const float *logits, long long ld, const double *z, 
                             const double *tie_break_uniforms, double epsilon, int n_env, int n_actions, double *q_out,
                             int *actions, void *stream);
 
+/* ---------------------------------------------------------------------------- Rainbow DQN -- */
+/* RainbowDQNAgent.learn_from_batch + the RainbowQHead's loss and gradient (agents/rainbow_dqn_agent.py:88-137,
+ * heads/rainbow_q_head.py:43-70) in ONE launch, one workgroup per batch row.  The head has two Dense outputs: the
+ * state-value stream v [batch][N] and the action-advantage stream x [batch][A*N] (column a*N + j = atom j of action a),
+ * each with its own leading dimension, on three passes: the online network on s (v, x), the target network on s'
+ * (*_next_target) and the online network on s' (*_next_online).
+ * Merge, fp32, per atom j, in rlx_dueling_combine's order (csrc/dfp_merge.hpp): s = 0.f, then += x[a][j] for a
+ * ascending; mean = s / (float)A; y[a][j] = v[j] + (x[a][j] - mean).  (The reference framework's own reduce_mean order is not pinned.)
+ * Softmax over the atoms of every action and the fp64 expectations are rlx_c51_head_loss's.  Per row: a* = the first
+ * maximum of the ONLINE network's expectations on s' (Double DQN); the projection of the TARGET network's distribution
+ * on s' at a*, for j = 0 .. N-1 in this order, fp64: tz = fmax(fmin(R + (boot * discount_n) * z_j, z_{N-1}), z_0) with
+ * R = n_step_returns[b], boot = bootstrap[b] (should_bootstrap_next_state; game_over is not read) and discount_n the
+ * host's discount ** n_step; bj, l, u, m and the dropped mass as in rlx_c51_head_loss; m rounded to fp32 once.
+ * Labels: m for the taken action, the online softmax itself for the others; loss = the sum over batch and actions of the
+ * softmax cross entropies, summed in a fixed order (row_partials: [batch] floats of workspace; ticket: one
+ * zero-initialised word, left at zero).  dy[b][a_b][j] = grad_scale * (p_j - m_j), exactly 0 on the other actions; dy goes
+ * back through the merge in rlx_dueling_combine_backward's arithmetic per atom: s = 0.f, then += dy[a][j] for a ascending;
+ * dv[b][j] = s; dx[b][a*N + j] = dy[a][j] - s / (float)A.  per_errors [batch] fp64 (optional): the taken action's cross
+ * entropy (0 for an invalid action), the row's new priority; importance weights are not an input (the head's loss_type
+ * is empty).  status |= 1 for an action outside [0, A): that row gets a zero gradient.  m_out [batch][N],
+ * target_actions_out [batch], action_losses_out [batch][A], merged_logits_out [batch][A*N] (y of the online network on
+ * s) and dlogits_out [batch][A*N] (dy) are optional (null).  2 <= N <= 256, A <= 18, batch <= 256. */
+int rlx_rainbow_head_loss(const float *v, long long ld_v, const float *x, long long ld_x, const float *v_next_target,
+                          long long ld_v_next_target, const float *x_next_target, long long ld_x_next_target,
+                          const float *v_next_online, long long ld_v_next_online, const float *x_next_online,
+                          long long ld_x_next_online, const double *z, const int *actions,
+                          const double *n_step_returns, const unsigned char *bootstrap, double discount_n, int n_atoms,
+                          int n_actions, int batch, float grad_scale, float *dv, long long ld_dv, float *dx,
+                          long long ld_dx, double *per_errors, float *row_partials, unsigned int *ticket,
+                          float *loss_scalar, int *status, float *m_out, int *target_actions_out,
+                          float *action_losses_out, float *merged_logits_out, float *dlogits_out, void *stream);
+/* The head's acting reductions: the merge above, then what rlx_categorical_egreedy / rlx_categorical_argmax do on the
+ * merged logits (one body, csrc/categorical_head.hpp): softmax, fp64 expectations, the epsilon-greedy choice with the
+ * fp64 isclose tie test, or the first maximum.  v: [n_env][ld_v], x: [n_env][ld_x]; the draws as rlx_egreedy takes them;
+ * q_out [n_env][A] fp64 is optional (null).  2 <= N <= 256, A <= 18. */
+int rlx_rainbow_egreedy(const float *v, long long ld_v, const float *x, long long ld_x, const double *z, int n_atoms,
+                        const double *explore_uniforms, const int *random_actions, const double *tie_break_uniforms,
+                        double epsilon, int n_env, int n_actions, double *q_out, int *actions, void *stream);
+int rlx_rainbow_argmax(const float *v, long long ld_v, const float *x, long long ld_x, const double *z, int n_atoms,
+                       int n_env, int n_actions, double *q_out, int *actions, void *stream);
+/* A finished episode's way into an n-step agent's replay (Episode.update_transitions_rewards_and_bootstrap_data,
+ * core_types.py:803-820, and the store loop of agents/agent.py:571-574) in ONE launch.  Source: env's staged episode of
+ * `length` = T rows, row k of columns laid out [n_env][stage_len] (observations obs_dim floats, actions action_words
+ * 32-bit words per row).  Destination: T consecutive rows of a struct-of-arrays ring starting at dst0, modulo ring_rows.
+ * With c = min(n_step, T), row k gets obs, action, reward and game_over of step k unchanged;
+ * n_step_discounted_rewards = what rlx_episode_nstep_returns gives for the same rewards (one body,
+ * csrc/episode_returns.hpp: bit-identical); if k + c < T: next_obs = obs of step k + c and
+ * should_bootstrap_next_state = 1, else next_obs = next_obs of step T - 1 and the flag is 0. */
+int rlx_nstep_episode_store(const float *staged_obs, const float *staged_next_obs, const int *staged_actions,
+                            const float *staged_rewards, const unsigned char *staged_game_overs, int env, int n_env,
+                            int stage_len, int length, int n_step, double discount, int obs_dim, int action_words,
+                            float *obs, float *next_obs, int *actions, float *rewards, unsigned char *game_overs,
+                            double *n_step_discounted_rewards, unsigned char *should_bootstrap_next_state,
+                            long long dst0, long long ring_rows, void *stream);
+
 /* ------------------------------------------------------------ Direct Future Prediction (DFP) -- */
 /* The MeasurementsPredictionHead (heads/measurements_prediction_head.py:39-62) works on two Dense outputs: expectation
  * [rows][K] and action_stream [rows][A*K] (column a*K + k), K = n_steps * n_measurements (step s, measurement m is column
