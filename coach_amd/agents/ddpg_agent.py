@@ -103,7 +103,7 @@ class DDPGAgent(BoxActionAgent):
         self.batch_size = cn.batch_size
         scale = float(np.maximum(np.abs(self.low), np.abs(self.high)).max())     # max_abs_range
         seed = self.ap.seed or 0
-        actor = ActorNet(self.device, self.obs_dim, self.A, scale, an.observation_embedder_scheme,
+        actor = ActorNet(self.device, self.obs_dim, self._actor_outputs(), scale, an.observation_embedder_scheme,
                          an.middleware_scheme, an.activation_function, an.learning_rate,
                          an.adam_optimizer_beta1, an.adam_optimizer_beta2, an.optimizer_epsilon, seed,
                          batchnorm=bool(getattr(an, "batchnorm", False)))
@@ -113,7 +113,7 @@ class DDPGAgent(BoxActionAgent):
                            cn.adam_optimizer_beta2, cn.optimizer_epsilon, seed + 1,
                            batchnorm=bool(getattr(cn, "batchnorm", False)))
         self.networks = OrderedDict([("actor", actor), ("critic", critic)])
-        self.memory = self._make_memory(action_dim=self.A)
+        self.memory = self._make_memory(action_dim=self._replay_action_dim())
         self.exploration_policy = self._make_exploration()
         dev, B = self.device, self.batch_size
         self.actions = torch.zeros(self.n_env, self.A, dtype=torch.float32, device=dev)
@@ -122,6 +122,18 @@ class DDPGAgent(BoxActionAgent):
         self.td_targets = torch.zeros(B, dtype=torch.float32, device=dev)
         self.neg_action_grad = torch.zeros(B, self.A, dtype=torch.float32, device=dev)
         self._finish_init()
+
+    def _actor_outputs(self):
+        """outputs of the actor's head: the action's dimensions (Wolpertinger: the action embedding's width)"""
+        return self.A
+
+    def _replay_action_dim(self):
+        """the replay's action column: fp32 [A] (Wolpertinger: None — the discrete action, an int32)"""
+        return self.A
+
+    def _batch_actions(self, b):
+        """the batch's actions as the critic takes them, fp32 [B][A]"""
+        return b.actions()
 
     # --------------------------------------------------------------------------------- acting
     def choose_action(self, states):
@@ -162,7 +174,7 @@ class DDPGAgent(BoxActionAgent):
         _, c_saved = critic.forward(s, actions_mean, B, tag="agrad")
         critic.action_gradient(c_saved, B, self.neg_action_grad, scale=-1.0)
         # critic.train_and_sync_networks (:179-180)
-        _, c_saved = critic.forward(s, b.actions(), B, tag="train")
+        _, c_saved = critic.forward(s, self._batch_actions(b), B, tag="train")
         critic.train_backward(c_saved, self.td_targets, B)
         self._sync(critic)
         critic.apply_gradients(self._grad_scale("critic"), with_norm=True, mix_rate=mix)

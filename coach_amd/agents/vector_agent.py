@@ -473,7 +473,7 @@ class VectorOffPolicyAgent(GraphRunner):
             actions = self.random_actions()                                    # agent.py:838-840
         else:
             actions = self.choose_action(states)
-        next_obs, reset_obs, reward, game_over = self.env.step(actions)
+        next_obs, reset_obs, reward, game_over = self.env.step(self._env_actions(actions))
         has_clip = alg.reward_clipping is not None
         lo, hi = alg.reward_clipping if has_clip else (0.0, 0.0)
         self.lib.reward_filter(reward, self.filtered_reward, self.n_env, alg.reward_rescale,
@@ -490,6 +490,11 @@ class VectorOffPolicyAgent(GraphRunner):
                           defer=not all_ended, episode_end=any_ended, dones_host=dones_host,
                           **self._store_extra_host(dones_host, record))
         return self._after_step_host(dones_host, ended, any_ended, all_ended, record)
+
+    def _env_actions(self, actions):
+        """what the environment receives for the agent's `actions` (the replay stores `actions` themselves): the
+        actions, unless an output filter stands between the two (Wolpertinger's BoxDiscretization)."""
+        return actions
 
     def _observe_previous_host(self, record):
         """host draws an agent's observe() makes when the previous step's response is observed (Bootstrapped DQN's

@@ -90,6 +90,20 @@ class NAFHeadParameters(HeadParameters):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
 
 
+class WolpertingerActorHeadParameters(HeadParameters):
+    """WolpertingerActorHeadParameters (head_parameters.py:111-119): one Dense layer of action_embedding_width outputs
+    ('actor_action_embedding'), optional batch normalisation, this activation, then times the filtered box space's
+    max_abs_range (heads/wolpertinger_actor_head.py:43-56) — the DDPG actor head with the embedding width for its
+    action count, which is what ActorNet builds.  The class default of `batchnorm` is the reference's (True); the agent's
+    network parameters pass use_batchnorm."""
+    head_type = "WolpertingerActorHead"
+
+    def __init__(self, activation_function='tanh', name='policy_head_params', batchnorm=True,
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+        self.batchnorm = batchnorm
+
+
 class PolicyHeadParameters(HeadParameters):
     """PolicyHeadParameters (head_parameters.py:162-169): for a discrete action space one Dense layer of A policy values
     ('fc') under a softmax (heads/policy_head.py:89-100; the activation is the continuous branch's, which has no device

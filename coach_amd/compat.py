@@ -21,6 +21,7 @@ import sys
 # reference module path (below rl_coach.) -> module below coach_amd. holding the same names
 _FOLDED = {
     "filters.reward": "filters.reward", "filters.observation": "filters.observation",
+    "filters.action": "filters.action",
     # the backend's layer classes (Dense, Conv2d, NoisyNetDense): presets name them in schemes
     "architectures.tensorflow_components.layers": "architectures.layers",
     "architectures.tensorflow_components": "architectures",     # (the parent package of the line above; longer entries first)

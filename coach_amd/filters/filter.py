@@ -42,13 +42,21 @@ class NoInputFilter(InputFilter):                        # filter.py:353-358
 
 
 class OutputFilter(object):                              # filter.py:96-110
-    """actions pass from the agent to the environment unchanged: action filters have no device implementation"""
+    """actions pass from the agent to the environment unchanged, or through exactly one BoxDiscretization
+    (filters/action.py: the agent acts in the discretised space, the environment receives the box point); every other
+    action filter, and a chain of several, has no device implementation"""
 
     def __init__(self, action_filters=None, is_a_reference_filter=False):
-        if action_filters:
-            raise ValueError("action filters {} have no device implementation".format(list(action_filters)))
-        self._action_filters = OrderedDict()
+        from .action import BoxDiscretization
+        filters = OrderedDict(action_filters or {})
+        if filters and not (len(filters) == 1 and isinstance(next(iter(filters.values())), BoxDiscretization)):
+            raise ValueError("action filters {} have no device implementation".format(list(filters)))
+        self._action_filters = filters
         self.i_am_a_reference_filter = is_a_reference_filter
+
+    @property
+    def action_filters(self):
+        return self._action_filters
 
 
 class NoOutputFilter(OutputFilter):                      # filter.py:245-250

@@ -1845,6 +1845,49 @@ int rlx_dataset_ingest(const double *features, long long ld_features, const int 
                        float *mem_reward, unsigned char *mem_game_over, float *mem_probabilities, int *status,
                        void *stream);
 
+/* ------------------------------------------ Wolpertinger: exact k-NN action lookup, critic re-ranking -- */
+/* (csrc/wolpertinger.hip; bit-exact numpy twin: tests/wolpertinger_ref.py.  Entry points ADDED under ABI version 11.)
+ *
+ * rlx_knn_topk: AnnoyDictionary.query as WolpertingerAgent.choose_action uses it (agents/wolpertinger_agent.py:92-100),
+ * exact instead of approximate.  For every query row the k keys of smallest squared Euclidean distance:
+ * idx_out int32 [n_queries][k] and, where dist2_out is not NULL, the squared distances fp32 [n_queries][k], both
+ * ascending in the pair (squared distance, key index): equal distances go to the lower index, a NaN distance sorts
+ * behind +inf, by index, and is written as the quiet NaN 0x7fc00000.  The squared distance is rlx_nn_min_distance's:
+ * acc = 0, then for w = 0 .. width-1 in order t = q[w] - key[w], acc = acc + t * t, each operation rounded to fp32 on
+ * its own, no FMA; never |q|^2 + |k|^2 - 2 q.k — a query that IS a key has distance exactly 0.
+ * Deterministic: every pair is one 64-bit word (distance bits, index) ordered as an unsigned integer; the keys are
+ * split over workgroups in chunks of RLX_KNN_KEY_CHUNK, each leaving its k smallest words in `scratch`, and merge passes
+ * over RLX_KNN_KEY_CHUNK / k lists at a time follow until one list is left: 1 + ceil(log_{CHUNK / k}(chunks)) launches,
+ * no atomics, no allocation, no synchronisation (capturable).  queries [n_queries][ld_q], keys [n_keys][ld_k]: 16-byte
+ * loads where base and leading dimension allow them (and across four keys of a width-1, ld_k = 1 table), scalar loads
+ * otherwise.  scratch: device memory, 8-byte aligned, of at least rlx_knn_topk_scratch_bytes(...) bytes (0 when the keys
+ * fit one chunk: scratch may then be NULL); its contents mean nothing between calls.
+ * 1 <= k <= 64, k <= n_keys <= 2^31 - 1, 1 <= width <= 64, ld_q, ld_k >= width, 1 <= n_queries <= 65535. */
+#define RLX_KNN_KEY_CHUNK 2048
+int rlx_knn_topk_scratch_bytes(int n_queries, long long n_keys, int k, long long *bytes_out);
+int rlx_knn_topk(const float *queries, long long ld_q, int n_queries, int width, const float *keys, long long ld_k,
+                 long long n_keys, int k, int *idx_out, float *dist2_out, void *scratch, long long scratch_bytes,
+                 void *stream);
+/* The critic's two inputs for the n_env * k candidates (agents/wolpertinger_agent.py:103-105: np.tile of the observation,
+ * nn_action_embeddings): row e * k + j of obs_out [n_env * k][ld_obs_out] is observations[e][0 .. obs_dim), row e * k + j
+ * of action_out [n_env * k][ld_action_out] is keys[idx[e][j]][0 .. width) (zeros for an index outside [0, n_keys)).
+ * A launch of its own, after rlx_knn_topk's last pass.  k <= 64, width <= 64. */
+int rlx_wolpertinger_candidates(const int *idx, const float *keys, long long ld_k, long long n_keys, int width,
+                                const float *observations, long long ld_obs, int obs_dim, int n_env, int k,
+                                float *obs_out, long long ld_obs_out, float *action_out, long long ld_action_out,
+                                void *stream);
+/* action_out[e] = idx[e][np.argmax_j q[(e * k + j) * q_stride]] (agents/wolpertinger_agent.py:106-107; the first
+ * maximum, and a NaN counts as the maximum: the first NaN wins) and env_action_out[e][0 .. action_dim) =
+ * target_actions[action_out[e]][0 .. action_dim), BoxDiscretization's filter (zeros for an action outside
+ * [0, n_actions)).  q_stride: elements between two candidates' Q values.  k <= 64. */
+int rlx_wolpertinger_select(const float *q, long long q_stride, const int *idx, int n_env, int k,
+                            const float *target_actions, long long ld_t, long long n_actions, int action_dim,
+                            int *action_out, float *env_action_out, long long ld_env, void *stream);
+/* WolpertingerAgent.learn_from_batch's conversion (agents/wolpertinger_agent.py:77-83): out[b][0 .. action_dim) =
+ * target_actions[actions[b]][0 .. action_dim).  status bit 1: an action outside [0, n_actions); its row is zero. */
+int rlx_discrete_to_box(const int *actions, int batch, const float *target_actions, long long ld_t, long long n_actions,
+                        int action_dim, float *out, long long ld_out, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
