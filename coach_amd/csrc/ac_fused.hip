@@ -35,7 +35,8 @@
 namespace {
 
 using namespace rlx_chain;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using rlx::f32x16;
+using rlx::mfma_row;
 
 struct Mlp3 {
     long long o_w1, o_b1, o_w2, o_b2, o_w3, o_b3;
@@ -455,8 +456,6 @@ struct DwArgs {
 };
 #define RLX_DW_STAMP(slot) do { if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0) a.stamps[(slot)] = (long long)__builtin_readcyclecounter(); } while (0)
 
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
 // A workgroup owns a 64 x 64 block of one layer's dW (4 waves, a 32 x 32 MFMA tile each).  Both operands of the block —
 // 64 feature columns of the layer's input and 64 columns of its output gradient, all batch rows — are staged in LDS by
 // 16-byte coalesced loads first: fed straight from memory an MFMA step costs two 4-byte loads per lane, 200 load
@@ -720,11 +719,6 @@ struct DwBuilder {
 };
 
 inline bool wide_ok(int n) { return n >= 64 && n <= kMaxWidth && (n % 4) == 0; }
-
-template <typename K>
-inline hipError_t set_lds(K kernel, size_t bytes = kChainLdsBytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 struct Td3Ws {
     long long zT, xm, h1c, h2c, qp, qTp, dq, dh2, dh1p, loss_part, xa, h1a, h2a, za, ya, h1q, dh1qp, dz3, dh2a, dh1ap, norm_part,
@@ -1410,13 +1404,9 @@ int rlx_td3_fused_critic_update(const rlx_td3_fused_desc *d_host, int write_grad
     RLX_REQUIRE(write_grads ? d.critic.grads != nullptr
                             : (d.critic.adam_m && d.critic.adam_v && d.critic.adam_state && d.critic.ticket),
                 "rlx_td3_fused_critic_update: null optimiser pointer");
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(set_lds(td3_forward1_kernel, kFwdLdsBytes));
-        RLX_HIP(set_lds(td3_forward2_kernel, kFwdLdsBytes));
-        RLX_HIP(set_lds(td3_critic_backward_kernel));
-        configured = true;
-    }
+    RLX_HIP(rlx::allow_lds<td3_forward1_kernel>(kFwdLdsBytes));
+    RLX_HIP(rlx::allow_lds<td3_forward2_kernel>(kFwdLdsBytes));
+    RLX_HIP(rlx::allow_lds<td3_critic_backward_kernel>(kChainLdsBytes));
     const Td3Dev p = td3_dev(d);
     hipStream_t st = rlx::as_stream(stream);
     RLX_LAUNCH((td3_forward1_kernel), 3 * kSplit * p.nrb, T, kFwdLdsBytes, st, p);
@@ -1453,13 +1443,9 @@ int rlx_td3_fused_actor_update(const rlx_td3_fused_desc *d_host, int write_grads
     RLX_REQUIRE(write_grads ? d.actor.grads != nullptr
                             : (d.actor.adam_m && d.actor.adam_v && d.actor.adam_state && d.actor.ticket),
                 "rlx_td3_fused_actor_update: null optimiser pointer");
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(set_lds(td3_actor_forward_kernel, kFwdLdsBytes));
-        RLX_HIP(set_lds(td3_actor_q_kernel));
-        RLX_HIP(set_lds(td3_actor_backward_kernel));
-        configured = true;
-    }
+    RLX_HIP(rlx::allow_lds<td3_actor_forward_kernel>(kFwdLdsBytes));
+    RLX_HIP(rlx::allow_lds<td3_actor_q_kernel>(kChainLdsBytes));
+    RLX_HIP(rlx::allow_lds<td3_actor_backward_kernel>(kChainLdsBytes));
     const Td3Dev p = td3_dev(d);
     hipStream_t st = rlx::as_stream(stream);
     RLX_LAUNCH((td3_actor_forward_kernel), kSplit * p.nrb, T, kFwdLdsBytes, st, p);
@@ -1508,15 +1494,11 @@ int rlx_sac_fused_update(const rlx_sac_fused_desc *d_host, int write_grads, void
     RLX_REQUIRE(d.policy.ticket != nullptr, "rlx_sac_fused_update: null ticket");
     const SacWs w = sac_layout(d);
     RLX_REQUIRE(d.workspace_floats >= w.total, "rlx_sac_fused_update: workspace of %lld floats, need %lld", d.workspace_floats, w.total);
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(set_lds(sac_layer1_kernel, kSacFwdLds));
-        RLX_HIP(set_lds(sac_layer2_kernel, kSacFwdLds));
-        RLX_HIP(set_lds(sac_q_pi_kernel, kSacFwdLds));
-        RLX_HIP(set_lds(sac_q_grad_kernel, kSacBwdLds));
-        RLX_HIP(set_lds(sac_backward_kernel, kSacBwdLds));
-        configured = true;
-    }
+    RLX_HIP(rlx::allow_lds<sac_layer1_kernel>(kSacFwdLds));
+    RLX_HIP(rlx::allow_lds<sac_layer2_kernel>(kSacFwdLds));
+    RLX_HIP(rlx::allow_lds<sac_q_pi_kernel>(kSacFwdLds));
+    RLX_HIP(rlx::allow_lds<sac_q_grad_kernel>(kSacBwdLds));
+    RLX_HIP(rlx::allow_lds<sac_backward_kernel>(kSacBwdLds));
     const SacDev p = sac_dev(d);
     hipStream_t st = rlx::as_stream(stream);
     RLX_LAUNCH((sac_layer1_kernel), 5 * kSplit * p.nrb, T, kSacFwdLds, st, p);

@@ -13,22 +13,11 @@
 //
 // B <= a few hundred rows, C <= a few hundred columns: one thread per column, rows in order (a fixed, reproducible
 // summation order; column-adjacent threads read adjacent floats).  A few KB per launch — latency, not bandwidth.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
 constexpr int kBlock = 64;
-
-__device__ __forceinline__ float bn_act(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == RLX_ACT_TANH) return tanhf(v);
-    return v;
-}
-__device__ __forceinline__ float bn_act_deriv(float y, int act) {
-    if (act == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (act == RLX_ACT_TANH) return 1.f - y * y;
-    return 1.f;
-}
 
 __global__ void __launch_bounds__(kBlock) bn_forward_kernel(
     const float *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -55,7 +44,7 @@ __global__ void __launch_bounds__(kBlock) bn_forward_kernel(
     }
     const float inv = rsqrtf(var + eps) * gamma[c];
     const float shift = beta[c] - mean * inv;
-    for (int b = 0; b < B; ++b) y[(size_t)b * C + c] = bn_act(x[(size_t)b * C + c] * inv + shift, act);
+    for (int b = 0; b < B; ++b) y[(size_t)b * C + c] = rlx::act_apply(x[(size_t)b * C + c] * inv + shift, act);
 }
 
 __global__ void __launch_bounds__(kBlock) bn_backward_kernel(
@@ -68,7 +57,7 @@ __global__ void __launch_bounds__(kBlock) bn_backward_kernel(
     float sb = 0.f, sg = 0.f;
     for (int b = 0; b < B; ++b) {
         const size_t i = (size_t)b * C + c;
-        const float du = act ? dy[i] * bn_act_deriv(y[i], act) : dy[i];
+        const float du = act ? dy[i] * rlx::act_deriv_out(y[i], act) : dy[i];
         sb += du;
         sg += du * ((x[i] - mean) * r);
     }
@@ -79,7 +68,7 @@ __global__ void __launch_bounds__(kBlock) bn_backward_kernel(
     const float k = gamma[c] * r, mb = sb / (float)B, mg = sg / (float)B;
     for (int b = 0; b < B; ++b) {
         const size_t i = (size_t)b * C + c;
-        const float du = act ? dy[i] * bn_act_deriv(y[i], act) : dy[i];
+        const float du = act ? dy[i] * rlx::act_deriv_out(y[i], act) : dy[i];
         dx[i] = k * (du - mb - ((x[i] - mean) * r) * mg);
     }
 }

@@ -21,7 +21,7 @@
 // K split (rlx_gemm_describe: what coach_amd/nn/graph.py asks before taking this launch).  Every dcol element is one fp32
 // v_mfma_f32_32x32x2_f32 chain over K = 64: two slabs of 32, inside a slab step t multiplying k = 8 (t / 4) + t % 4
 // (half-wave 0) and that + 4 (half-wave 1) — the same instruction in the same order here.  The gathers add the taps of an
-// input position in col2im_kernel's order ((ky, kx) ascending, from 0.f) and multiply by act_deriv of the stored
+// input position in col2im_kernel's order ((ky, kx) ascending, from 0.f) and multiply by act_deriv_out of the stored
 // activation as it does.
 //
 // Work split: 32 x 32 tiles of dcol, job j = (column tile j / 2, row tile j % 2) on wave j % 8 — a wave keeps ONE row tile,
@@ -35,7 +35,7 @@
 // operands come straight from memory, so a second chain only adds registers.)
 // LDS 115 KB: column matrix 93 KB, dz3 9.5 KB, dz2 12 KB.
 // Bound: MFMA issue of one CU — 36 + 32 jobs of 32 MFMAs on 4 SIMDs = 34.8 k cycles = 16 us — plus two gather passes.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 #include <type_traits>
 // the prioritized replay's priority update as a rider (see conv32_input_grad_kernel's RIDER): glibc's pow with every fusion
 // explicit — no contraction inside these two headers, whatever this file is compiled with
@@ -46,8 +46,9 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rlx::f32x4;
+using rlx::f32x16;
+using rlx::act_deriv_out;
 
 constexpr int kThreads = 512;
 constexpr int H1 = 20, W1 = 20, C1 = 32;             // conv1 activation = conv2 input
@@ -83,12 +84,6 @@ struct PerRider {                                    // rlx_per_update's argumen
     double alpha, eps;
     int cap, levels, n;
 };
-
-__device__ __forceinline__ float act_deriv(float y, int kind) {      // gemm.hip's: through the activation's OUTPUT
-    if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (kind == RLX_ACT_TANH) return 1.f - y * y;
-    return 1.f;
-}
 
 // TAIL16: the second row tile of both products (positions 32 .. 34 of 35, 32 .. 44 of 45) as a 16-row tile on
 // v_mfma_f32_16x16x4_f32 — a tail job is 16 rows x 32 columns = TWO independent 16 x 16 accumulator chains (the two column
@@ -328,8 +323,8 @@ __global__ void __launch_bounds__(kThreads, 2) conv32_input_grad_kernel(const Co
 #pragma unroll
             for (int q = 0; q < K3 * K3; ++q)
                 if (tok[q]) { s.x += tv[q].x; s.y += tv[q].y; s.z += tv[q].z; s.w += tv[q].w; }
-            s.x *= act_deriv(y2v[it].x, a.act); s.y *= act_deriv(y2v[it].y, a.act);
-            s.z *= act_deriv(y2v[it].z, a.act); s.w *= act_deriv(y2v[it].w, a.act);
+            s.x *= act_deriv_out(y2v[it].x, a.act); s.y *= act_deriv_out(y2v[it].y, a.act);
+            s.z *= act_deriv_out(y2v[it].z, a.act); s.w *= act_deriv_out(y2v[it].w, a.act);
             *reinterpret_cast<float4 *>(dz2s + pl * PZ + c4) = s;
             if (iy >= own2_lo && iy < own2_hi) *reinterpret_cast<float4 *>(dz2 + (size_t)item * 4) = s;
         }
@@ -363,8 +358,8 @@ __global__ void __launch_bounds__(kThreads, 2) conv32_input_grad_kernel(const Co
 #pragma unroll
             for (int q = 0; q < kT * kT; ++q)
                 if (tok[q]) { s.x += tv[q].x; s.y += tv[q].y; s.z += tv[q].z; s.w += tv[q].w; }
-            s.x *= act_deriv(y1v[it].x, a.act); s.y *= act_deriv(y1v[it].y, a.act);
-            s.z *= act_deriv(y1v[it].z, a.act); s.w *= act_deriv(y1v[it].w, a.act);
+            s.x *= act_deriv_out(y1v[it].x, a.act); s.y *= act_deriv_out(y1v[it].y, a.act);
+            s.z *= act_deriv_out(y1v[it].z, a.act); s.w *= act_deriv_out(y1v[it].w, a.act);
             *reinterpret_cast<float4 *>(dz1 + (size_t)item * 4) = s;
         }
     }

@@ -2,25 +2,16 @@
 // conv_dw_u8.hip (first layer, uint8 frames), conv_dw_f32.hip (inner layers, fp32 activations) — shared with
 // conv_dw_multi.hip, which runs all three layers of the Atari torso as ONE launch.  See those files for what each replaces.
 #pragma once
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 #include <type_traits>
 
 namespace rlx_convdw {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rlx::f32x4;
+using rlx::f32x16;
+using rlx::dma16;
 
 constexpr int kThreads = 256, kN = 64;
-
-// one 16-byte global -> LDS request per lane; lds_dst: wave-uniform LDS byte address of lane 0's 16 bytes (gemm.hip dma16)
-__device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-
 
 // ------------------------------------------------------------------------------------------------ first layer, uint8 frames
 struct DwU8 {

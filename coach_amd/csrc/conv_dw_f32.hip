@@ -73,14 +73,8 @@ int rlx_conv_dw_f32(const float *x, long long x_tower_stride, const float *dz, l
     RLX_REQUIRE((((uintptr_t)x | (uintptr_t)dz | (uintptr_t)workspace) & 15) == 0 && (x_tower_stride & 3) == 0 &&
                     (dz_tower_stride & 3) == 0,
                 "rlx_conv_dw_f32: misaligned operand");
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_f32_kernel<64, 3, 1, 9, 7>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_f32_kernel<32, 4, 2, 20, 9>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured = true;
-    }
+    RLX_HIP((rlx::allow_lds<conv_dw_f32_kernel<64, 3, 1, 9, 7>>(160 * 1024)));
+    RLX_HIP((rlx::allow_lds<conv_dw_f32_kernel<32, 4, 2, 20, 9>>(160 * 1024)));
     DwF32 a;
     a.x = x; a.x_ts = x_tower_stride; a.dz = dz; a.dz_ts = dz_tower_stride;
     a.part = workspace; a.cpart = db ? workspace + (size_t)towers * g.splits * g.K * kN : nullptr;

@@ -195,18 +195,10 @@ int conv_dw_multi_impl(const rlx_conv_dw_item *items, rlx_splitk_job *jobs, int 
         j.ldc = it.filters; j.c_batch_stride = it.dw_tower_stride; j.colsum_batch_stride = it.db_tower_stride;
         j.M = g.K; j.N = kN; j.batch = it.towers; j.splits = g.splits; j.n_fold = 0;
     }
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_multi_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_multi_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_multi_kernel<4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_multi_adam_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured = true;
-    }
+    RLX_HIP(rlx::allow_lds<conv_dw_multi_kernel<1>>(160 * 1024));
+    RLX_HIP(rlx::allow_lds<conv_dw_multi_kernel<2>>(160 * 1024));
+    RLX_HIP(rlx::allow_lds<conv_dw_multi_kernel<4>>(160 * 1024));
+    RLX_HIP(rlx::allow_lds<conv_dw_multi_adam_kernel>(160 * 1024));
     const unsigned grid = m.nb_u8 + m.nb_f[0] + m.nb_f[1];
     if (passes > 1) {
         // per-body LDS of the multi-pass forms

@@ -79,14 +79,8 @@ int rlx_conv_dw_u8(const unsigned char *frames, float a_div, const float *dz, lo
     RLX_REQUIRE((((uintptr_t)frames) & 3) == 0 && (((uintptr_t)dz) & 15) == 0 && (dz_tower_stride & 3) == 0 &&
                     (((uintptr_t)workspace) & 15) == 0,
                 "rlx_conv_dw_u8: misaligned operand");
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_u8_kernel<20, 16, 84>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw_u8_kernel<0, 0, 0>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured = true;
-    }
+    RLX_HIP((rlx::allow_lds<conv_dw_u8_kernel<20, 16, 84>>(160 * 1024)));
+    RLX_HIP((rlx::allow_lds<conv_dw_u8_kernel<0, 0, 0>>(160 * 1024)));
     DwU8 a;
     a.x = frames; a.dz = dz; a.dz_ts = dz_tower_stride;
     a.part = workspace; a.cpart = workspace + (size_t)B * g.K * kN;

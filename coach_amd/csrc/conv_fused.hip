@@ -42,13 +42,15 @@
 // 32 x 33 for the partial-tile exchange and the 16-byte epilogue.
 // Bound: MFMA issue of a CU (conv2: 8 wave-jobs of 128 MFMAs on 4 SIMDs = 6.8 us; conv3: 4 wave-jobs of 144 MFMAs =
 // 3.8 us) with the weight stream (275 KB per workgroup) underneath.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 #include <type_traits>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rlx::f32x4;
+using rlx::f32x16;
+using rlx::act_apply;
+using rlx::dma16;
 
 constexpr int kThreads = 512;
 constexpr int H1 = 20, W1 = 20, C1 = 32;             // conv1 output = conv2 input
@@ -91,21 +93,6 @@ struct ConvPairArgs {
     const float *b1; long long b1_ts;
     float a_div;                                     // frame byte / a_div = network input (observation rescaling, 255)
 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == RLX_ACT_TANH) return tanhf(v);
-    return v;
-}
-
-// one 16-byte global -> LDS request per lane; lds_dst: wave-uniform LDS byte address of lane 0's 16 bytes (gemm.hip dma16)
-__device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
 
 // kDepth: weight slabs in the ring; S: slabs per sync point (one wait + barrier + S requests per S slabs; kDepth >= 2 S)
 // KWG: wave groups per K slab of the TILED launches this one reproduces bit for bit — 2: 32 x 64 tiles, k-quads {0, 1} and
@@ -297,8 +284,8 @@ __global__ void __launch_bounds__(kThreads, 2) conv23_forward_kernel(const ConvP
                 const float *sp = patch + rl * 33 + c4;
                 float4 o = make_float4(sp[0], sp[1], sp[2], sp[3]);
                 o.x += bias1.x; o.y += bias1.y; o.z += bias1.z; o.w += bias1.w;
-                o.x = apply_act(o.x, a.act); o.y = apply_act(o.y, a.act);
-                o.z = apply_act(o.z, a.act); o.w = apply_act(o.w, a.act);
+                o.x = act_apply(o.x, a.act); o.y = act_apply(o.y, a.act);
+                o.z = act_apply(o.z, a.act); o.w = act_apply(o.w, a.act);
                 *reinterpret_cast<float4 *>(in1 + pos * P1 + c4) = o;
                 const int row = r1 + pos / W1;
                 if (row >= own1_lo && row < own1_hi) {
@@ -341,8 +328,8 @@ __global__ void __launch_bounds__(kThreads, 2) conv23_forward_kernel(const ConvP
                     const float *sp = patches + rl * 33 + c4;
                     float4 o = make_float4(sp[0], sp[1], sp[2], sp[3]);
                     o.x += bias1.x; o.y += bias1.y; o.z += bias1.z; o.w += bias1.w;
-                    o.x = apply_act(o.x, a.act); o.y = apply_act(o.y, a.act);
-                    o.z = apply_act(o.z, a.act); o.w = apply_act(o.w, a.act);
+                    o.x = act_apply(o.x, a.act); o.y = act_apply(o.y, a.act);
+                    o.z = act_apply(o.z, a.act); o.w = act_apply(o.w, a.act);
                     *reinterpret_cast<float4 *>(in1 + pos * P1 + c4) = o;
                     const int row = r1 + pos / W1;
                     if (row >= own1_lo && row < own1_hi) {
@@ -457,8 +444,8 @@ __global__ void __launch_bounds__(kThreads, 2) conv23_forward_kernel(const ConvP
                 const float *sp = tile + rl * 33 + c4;
                 float4 v = make_float4(sp[0], sp[1], sp[2], sp[3]);
                 v.x += bias2.x; v.y += bias2.y; v.z += bias2.z; v.w += bias2.w;
-                v.x = apply_act(v.x, a.act); v.y = apply_act(v.y, a.act);
-                v.z = apply_act(v.z, a.act); v.w = apply_act(v.w, a.act);
+                v.x = act_apply(v.x, a.act); v.y = act_apply(v.y, a.act);
+                v.z = act_apply(v.z, a.act); v.w = act_apply(v.w, a.act);
                 *reinterpret_cast<float4 *>(out2 + pos * P2 + wn * 32 + c4) = v;
                 const int row = r2 + pos / O2;                    // conv2 output row of this position
                 if (row >= own_lo && row < own_hi) {
@@ -557,8 +544,8 @@ __global__ void __launch_bounds__(kThreads, 2) conv23_forward_kernel(const ConvP
                 const float *sp = patches + tile * kPatchFloats + rl * 33 + c4;
                 float4 v = make_float4(sp[0], sp[1], sp[2], sp[3]);
                 v.x += bias3.x; v.y += bias3.y; v.z += bias3.z; v.w += bias3.w;
-                v.x = apply_act(v.x, a.act); v.y = apply_act(v.y, a.act);
-                v.z = apply_act(v.z, a.act); v.w = apply_act(v.w, a.act);
+                v.x = act_apply(v.x, a.act); v.y = act_apply(v.y, a.act);
+                v.z = act_apply(v.z, a.act); v.w = act_apply(v.w, a.act);
                 float *const y3 = a.y3 + (size_t)t * a.y3_ts + ((size_t)img * (O3 * O3) + (size_t)r3 * O3) * C3;
                 *reinterpret_cast<float4 *>(y3 + (size_t)rl * C3 + tile * 32 + c4) = v;
             }

@@ -1,27 +1,16 @@
 // Device bodies of the narrow dense layers (see dense_small.hip), shared with the fused Clipped-PPO heads
 // kernel (ppo_heads_fused.hip): one definition, one summation order.
 #pragma once
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace rlx_small {
 constexpr int kMaxN = 16;
 
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == RLX_ACT_TANH) return tanhf(v);
-#ifdef RLX_DENSE_SMALL_LEAKY      // dense_small.hip alone: every other file that includes this body compiles as before
-    if (act == RLX_ACT_LEAKY_RELU) return v > 0.f ? v : 0.2f * v;
+#ifdef RLX_DENSE_SMALL_LEAKY      // dense_small.hip alone: every other file that includes this body compiles without the branch
+constexpr bool kLeaky = true;
+#else
+constexpr bool kLeaky = false;
 #endif
-    return v;
-}
-__device__ __forceinline__ float act_deriv_out(float y, int kind) {
-    if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (kind == RLX_ACT_TANH) return 1.f - y * y;
-#ifdef RLX_DENSE_SMALL_LEAKY
-    if (kind == RLX_ACT_LEAKY_RELU) return y > 0.f ? 1.f : 0.2f;
-#endif
-    return 1.f;
-}
 
 struct SmallDense {
     const float *x; long long x_ts;        // [T][M][K] (x_ts = 0: shared input)
@@ -62,7 +51,7 @@ __device__ __forceinline__ void dense_small_fwd_row(const SmallDense &p, int row
         const int n = threadIdx.x;
         float v = ((part[0][n] + part[1][n]) + part[2][n]) + part[3][n];
         v += p.b ? p.b[(size_t)t * p.b_ts + n] : 0.f;
-        p.y[(size_t)t * p.y_ts + (size_t)row * p.N + n] = act_apply(v, p.act);
+        p.y[(size_t)t * p.y_ts + (size_t)row * p.N + n] = rlx::act_apply<kLeaky>(v, p.act);
     }
 }
 
@@ -108,7 +97,7 @@ __device__ __forceinline__ void dense_small_bwd_body(const SmallDenseBwd &p, int
         const float *dy = p.dy + (size_t)t * p.dy_ts;
         const float *yy = p.y ? p.y + (size_t)t * p.y_ts : nullptr;
         for (int i = threadIdx.x; i < p.M * p.N; i += 256)
-            dz[i] = dy[i] * (yy ? act_deriv_out(yy[i], p.act) : 1.f);
+            dz[i] = dy[i] * (yy ? rlx::act_deriv_out<kLeaky>(yy[i], p.act) : 1.f);
     }
     const bool live = k < p.K;
     const float *__restrict__ x = p.x + (size_t)t * p.x_ts;
@@ -150,7 +139,7 @@ __device__ __forceinline__ void dense_small_bwd_body(const SmallDenseBwd &p, int
                             acc[n] = fmaf(xv[u], d, acc[n]);
                             s = fmaf(d, wk[n], s);
                         }
-                    if (dx) dx[(size_t)mm * p.K + k] = p.lower_act ? s * act_deriv_out(xv[u], p.lower_act) : s;
+                    if (dx) dx[(size_t)mm * p.K + k] = p.lower_act ? s * rlx::act_deriv_out<kLeaky>(xv[u], p.lower_act) : s;
                 }
             }
         }

@@ -24,7 +24,7 @@
 // every weight gradient) is split along K over blockIdx.z into a workspace and reduced
 // deterministically by splitk_reduce_kernel, which also applies bias / activation.
 // blockIdx.z also carries a batch index (the two separate Clipped-PPO towers run as one launch).
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 #include "dense_small_body.hpp"
 #include "losses_body.hpp"
 #include "splitk_reduce_body.hpp"
@@ -32,8 +32,11 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rlx::f32x4;
+using rlx::f32x16;
+using rlx::act_apply;
+using rlx::act_deriv_out;
+using rlx::dma16;
 
 constexpr int BK = 32;
 constexpr int kThreads = 256;
@@ -84,18 +87,6 @@ struct GemmDev {
 __device__ __forceinline__ long long batch_off(int batch, int inner, long long stride, long long stride2) {
     const int bo = batch / inner;
     return (long long)bo * stride2 + (long long)(batch - bo * inner) * stride;
-}
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == RLX_ACT_RELU) return v <= 0.f ? 0.f : v;       // np.maximum(v, 0): a NaN stays NaN (v > 0 ? v : 0 made it 0)
-    if (act == RLX_ACT_TANH) return tanhf(v);
-    return v;
-}
-// derivative of the activation expressed through its OUTPUT y
-__device__ __forceinline__ float act_deriv(float y, int kind) {
-    if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (kind == RLX_ACT_TANH) return 1.f - y * y;
-    return 1.f;
 }
 
 // Loads 4 logically consecutive elements (along the vector dimension) of an operand tile.
@@ -280,8 +271,8 @@ __global__ void __launch_bounds__(kThreads) gemm_kernel(const GemmDev g) {
     for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
         if (row < g.M) {
-            float v = apply_act(acc[r] + bias, g.act);
-            if (aux) v *= act_deriv(aux[(size_t)row * g.aux_ld + col], g.deriv);
+            float v = act_apply(acc[r] + bias, g.act);
+            if (aux) v *= act_deriv_out(aux[(size_t)row * g.aux_ld + col], g.deriv);
             float *dst = &c[(size_t)row * g.ldc + col];
             *dst = g.accumulate ? *dst + v : v;
         }
@@ -463,12 +454,12 @@ __device__ __forceinline__ void fast_epilogue(const GemmDev &g, f32x16 (&acc)[TM
                         if (g.bias) {
                             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
                         }
-                        v.x = apply_act(v.x, g.act); v.y = apply_act(v.y, g.act);
-                        v.z = apply_act(v.z, g.act); v.w = apply_act(v.w, g.act);
+                        v.x = act_apply(v.x, g.act); v.y = act_apply(v.y, g.act);
+                        v.z = act_apply(v.z, g.act); v.w = act_apply(v.w, g.act);
                         if (aux) {
                             const float4 av = av4[it];
-                            v.x *= act_deriv(av.x, g.deriv); v.y *= act_deriv(av.y, g.deriv);
-                            v.z *= act_deriv(av.z, g.deriv); v.w *= act_deriv(av.w, g.deriv);
+                            v.x *= act_deriv_out(av.x, g.deriv); v.y *= act_deriv_out(av.y, g.deriv);
+                            v.z *= act_deriv_out(av.z, g.deriv); v.w *= act_deriv_out(av.w, g.deriv);
                         }
                         if (g.accumulate) {
                             const float4 ov = *reinterpret_cast<const float4 *>(dst);
@@ -496,8 +487,8 @@ __device__ __forceinline__ void fast_epilogue(const GemmDev &g, f32x16 (&acc)[TM
                 if (ws) {
                     ws[(size_t)row * g.N + col] = acc[i][j][r];
                 } else {
-                    float v = apply_act(acc[i][j][r] + bias, g.act);
-                    if (aux) v *= act_deriv(aux[(size_t)row * g.aux_ld + col], g.deriv);
+                    float v = act_apply(acc[i][j][r] + bias, g.act);
+                    if (aux) v *= act_deriv_out(aux[(size_t)row * g.aux_ld + col], g.deriv);
                     float *dst = &c[(size_t)row * g.ldc + col];
                     *dst = g.accumulate ? *dst + v : v;
                 }
@@ -944,16 +935,7 @@ struct DmaTile {
     static constexpr int kSmemFloats = kRingFloats > 4 * 32 * 33 ? kRingFloats : 4 * 32 * 33;   // >= the epilogue's staging
 };
 
-// one 16-byte global -> LDS request per lane; lds_dst: wave-uniform LDS byte address of lane 0's 16 bytes
-__device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-
-// the 4-byte request (uint8 operands: four consecutive bytes per lane; LDS byte = base + lane * 4)
+// rlx::dma16's 4-byte form (uint8 operands: four consecutive bytes per lane; LDS byte = base + lane * 4)
 __device__ __forceinline__ void dma4(const unsigned char *gsrc, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
@@ -1474,8 +1456,8 @@ __device__ __forceinline__ void gemm_thin_body(const GemmDev &g, const int bx, c
         if (col >= g.N) continue;
         const int o = rl * LD + c4 + j;
         float v = ((As[o] + As[32 * LD + o]) + As[2 * 32 * LD + o]) + As[3 * 32 * LD + o];
-        v = apply_act(v + e_bias[j], g.act);
-        if (g.aux) v *= act_deriv(e_aux[j], g.deriv);
+        v = act_apply(v + e_bias[j], g.act);
+        if (g.aux) v *= act_deriv_out(e_aux[j], g.deriv);
         c[col] = g.accumulate ? c[col] + v : v;
     }
 }
@@ -1571,8 +1553,8 @@ __device__ __forceinline__ void gemm_thin16_body(const GemmDev &g, const int bx,
     if (!live) return;
     const int o = rl * LD + cl;
     float v = ((As[o] + As[16 * LD + o]) + As[2 * 16 * LD + o]) + As[3 * 16 * LD + o];
-    v = apply_act(v + e_bias, g.act);
-    if (g.aux) v *= act_deriv(e_aux, g.deriv);
+    v = act_apply(v + e_bias, g.act);
+    if (g.aux) v *= act_deriv_out(e_aux, g.deriv);
     float *c = g.c + (size_t)batch * g.c_batch_stride + (size_t)row * g.ldc + col;
     *c = g.accumulate ? *c + v : v;
 }
@@ -1622,8 +1604,8 @@ __global__ void splitk_reduce_kernel(const GemmDev g) {
         float s = 0.f;
         for (int k = 0; k < g.splits; ++k) s += ws[(size_t)k * mn + i];   // fixed order
         const int row = (int)(i / g.N), col = (int)(i - (long long)row * g.N);
-        float v = apply_act(s + (bias ? bias[col] : 0.f), g.act);
-        if (aux) v *= act_deriv(aux[(size_t)row * g.aux_ld + col], g.deriv);
+        float v = act_apply(s + (bias ? bias[col] : 0.f), g.act);
+        if (aux) v *= act_deriv_out(aux[(size_t)row * g.aux_ld + col], g.deriv);
         float *dst = &c[(size_t)row * g.ldc + col];
         *dst = g.accumulate ? *dst + v : v;
     }
@@ -1701,8 +1683,8 @@ __global__ void __launch_bounds__(64 * SG) splitk_reduce4_kernel(const GemmDev g
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float t = apply_act(v[j] + eb[j], g.act);
-            if (g.aux) t *= act_deriv(ea[j], g.deriv);
+            float t = act_apply(v[j] + eb[j], g.act);
+            if (g.aux) t *= act_deriv_out(ea[j], g.deriv);
             v[j] = g.accumulate ? ec[j] + t : t;
         }
         if ((g.ldc & 3) == 0 && (((uintptr_t)c) & 15) == 0) {
@@ -1863,8 +1845,8 @@ __global__ void __launch_bounds__(1024) splitk_reduce_rows_kernel(const GemmDev 
             }
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
-                float t = apply_act(v[jj] + eb[ps][jj], g.act);
-                if (g.aux) t *= act_deriv(ea[ps][jj], g.deriv);
+                float t = act_apply(v[jj] + eb[ps][jj], g.act);
+                if (g.aux) t *= act_deriv_out(ea[ps][jj], g.deriv);
                 v[jj] = g.accumulate ? ec[ps][jj] + t : t;
                 hrow[col + jj] = v[jj];
             }
@@ -1905,7 +1887,7 @@ __global__ void __launch_bounds__(1024) splitk_reduce_rows_kernel(const GemmDev 
         const int n = threadIdx.x;
         float v = ((hpart[0][n] + hpart[1][n]) + hpart[2][n]) + hpart[3][n];
         v += hp.b ? hp.b[n] : 0.f;
-        v = rlx_small::act_apply(v, hp.act);
+        v = act_apply(v, hp.act);
         hp.y[(size_t)row * hp.N + n] = v;
         if (PPO) yrow[n] = v;
     }
@@ -1961,7 +1943,7 @@ __global__ void __launch_bounds__(1024) splitk_reduce_rows_kernel(const GemmDev 
 #pragma unroll
                 for (int n = 0; n < NN; ++n)
                     if (n < hp.N) s = fmaf(dzrow[n], wreg[j][n], s);
-                dx[k] = r.lower_act ? s * rlx_small::act_deriv_out(hrow[k], r.lower_act) : s;
+                dx[k] = r.lower_act ? s * act_deriv_out(hrow[k], r.lower_act) : s;
             }
         }
     }
@@ -2062,7 +2044,7 @@ __global__ void act_backward_kernel(float *__restrict__ dy, const float *__restr
                                     int kind) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
-        dy[i] *= act_deriv(y[i], kind);
+        dy[i] *= act_deriv_out(y[i], kind);
 }
 
 // RLX_ACT_LEAKY_RELU (alpha 0.2, tf.nn.leaky_relu's default) as launches of its own: the epilogues above, and so every hot
@@ -2166,7 +2148,7 @@ __global__ void col2im_kernel(const float *__restrict__ dcol, float *__restrict_
         const size_t o = (size_t)p * C + c;
         if (x_out) {
 #pragma unroll
-            for (int j = 0; j < VEC; ++j) s[j] *= act_deriv(x_out[o + j], deriv);
+            for (int j = 0; j < VEC; ++j) s[j] *= act_deriv_out(x_out[o + j], deriv);
         }
         if (VEC == 4) {
             *reinterpret_cast<float4 *>(dx + o) = make_float4(s[0], s[1], s[2], s[3]);

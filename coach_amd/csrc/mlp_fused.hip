@@ -28,11 +28,12 @@
 // Arithmetic: v_mfma_f32_32x32x2_f32 (exact fp32 products, k-ordered fmaf chain) for the three wide products,
 // plain fp32 FMAs for the narrow ones; TD targets in fp64 like the reference's Python loop.  Compiled with
 // -ffp-contract=off: the Adam step rounds like adam_tf1_kernel (optim.hip).
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using rlx::f32x16;
+using rlx::mfma_row;
 constexpr int kThreads = 256;
 constexpr int LD = 33;                 // LDS row pitch (words): conflict-free for row- and column-wise walks
 constexpr int kMaxA = 16;
@@ -60,8 +61,6 @@ struct MlpDqnDev {
     int huber, ddqn;
     float lr, beta1, beta2, eps, grad_scale;
 };
-
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // All workgroups of the grid meet here.  Producer side: plain stores, __syncthreads, ONE lane releases at
 // agent scope (L2 write-back), drains, and bumps the counter; consumer side: the same lane polls the counter
@@ -167,7 +166,7 @@ __device__ __forceinline__ void dense1(const float *xs, const float *W, long lon
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float v = acc[r] + bias[t];
-                h1dst[(n0 + l31) * LD + mfma_row(r, hi)] = v > 0.f ? v : 0.f;
+                h1dst[(n0 + l31) * LD + mfma_row(r, hi)] = rlx::relu(v);
             }
         }
     }
@@ -196,7 +195,7 @@ __device__ __forceinline__ void dense2(const float *h1s, const float *w2s, const
         const int o = b * LD + c;
         float v = ((red[o] + red[32 * LD + o]) + red[64 * LD + o]) + red[96 * LD + o];
         v += W[o_b2 + col0 + c];
-        h2dst[c * LD + b] = v > 0.f ? v : 0.f;
+        h2dst[c * LD + b] = rlx::relu(v);
     }
     __syncthreads();
 }
@@ -520,7 +519,7 @@ __global__ void __launch_bounds__(1024) mlp_q_act_kernel(const MlpActDev p) {
         }
         const float bv = b1[j];
 #pragma unroll
-        for (int e = 0; e < E; ++e) h1s[e * p.H1 + j] = fmaxf(acc[e] + bv, 0.f);
+        for (int e = 0; e < E; ++e) h1s[e * p.H1 + j] = rlx::relu(acc[e] + bv);
     }
     __syncthreads();
     // the wide layer: H1 x H2 weights through ONE compute unit.  A thread owns 4 adjacent hidden units (16-byte
@@ -564,7 +563,7 @@ __global__ void __launch_bounds__(1024) mlp_q_act_kernel(const MlpActDev p) {
             for (int e = 0; e < E; ++e) {
                 float v = parts[(size_t)(e * S) * p.H2 + j];
                 for (int q = 1; q < S; ++q) v += parts[(size_t)(e * S + q) * p.H2 + j];
-                h2s[e * p.H2 + j] = fmaxf(v + bv, 0.f);
+                h2s[e * p.H2 + j] = rlx::relu(v + bv);
             }
         }
     }
@@ -693,12 +692,7 @@ int rlx_mlp_dqn_update(const rlx_mlp_dqn_desc *d_host, void *stream) {
     p.huber = d.huber; p.ddqn = d.double_dqn;
     p.lr = d.learning_rate; p.beta1 = d.beta1; p.beta2 = d.beta2; p.eps = d.epsilon; p.grad_scale = d.grad_scale;
     const size_t lds = lds_floats(d.obs_dim, d.h1) * sizeof(float);
-    static size_t configured = 0;
-    if (lds > configured) {
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_dqn_update_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = lds;
-    }
+    RLX_HIP(rlx::allow_lds<mlp_dqn_update_kernel>(lds));
     RLX_LAUNCH((mlp_dqn_update_kernel), G, kThreads, lds, rlx::as_stream(stream), p);
     RLX_LAUNCH_CHECK();
     return RLX_OK;

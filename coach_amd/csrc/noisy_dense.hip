@@ -17,26 +17,15 @@
 // workgroups by shape alone (about 512 workgroups), the partial tiles go to a workspace and noisy_reduce_kernel adds
 // them in split order and applies the epilogue: sums are bit-identical run to run.  With one split the epilogue
 // runs in the product kernel.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using rlx::f32x16;
 
 constexpr int kRC = 64;            // reduction elements per staged step
 constexpr int kLd = kRC + 1;       // LDS row stride in floats
 constexpr int kTargetWgs = 512;
-
-__device__ __forceinline__ float nd_act(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == RLX_ACT_TANH) return tanhf(v);
-    return v;
-}
-__device__ __forceinline__ float nd_act_deriv(float y, int kind) {
-    if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (kind == RLX_ACT_TANH) return 1.f - y * y;
-    return 1.f;
-}
 
 struct NoisyProd {
     const float *a;            // [M][lda]: x (forward) or dz (input gradient)
@@ -59,9 +48,9 @@ struct NoisyProd {
 __device__ __forceinline__ float nd_epilogue(const NoisyProd &p, float v, int m, int j) {
     if (p.bm) {
         v += p.bm[j] + p.bs[j] * p.fb[j];
-        return nd_act(v, p.act);
+        return rlx::act_apply(v, p.act);
     }
-    if (p.aux) v *= nd_act_deriv(p.aux[(size_t)m * p.ld_aux + j], p.deriv);
+    if (p.aux) v *= rlx::act_deriv_out(p.aux[(size_t)m * p.ld_aux + j], p.deriv);
     return v;
 }
 

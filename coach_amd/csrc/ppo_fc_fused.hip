@@ -20,12 +20,15 @@
 // the heads' weight gradients.  1 MB of partials instead of 6.5 MB; nothing is read that another launch wrote except x.
 // Arithmetic of the losses: losses_body.hpp (the definitions the stand-alone loss kernels use).
 #include "losses_body.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
 using namespace rlx_losses;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rlx::f32x4;
+using rlx::f32x16;
+using rlx::act_apply;
+using rlx::act_deriv_out;
 
 constexpr int kThreads = 256, kRows = 64, kTileN = 32, kSplits = 8, kMaxA = 16, kMaxKc = 392;
 constexpr int kXP = kMaxKc + 1;                        // odd pitch: the MFMA A operand walks rows (lane = row)
@@ -56,17 +59,6 @@ struct FcHeadsDev {
 #define RLX_FC_STAMP_ANY(i) do { if (p.stamps && threadIdx.x == 0) p.stamps[i] = (long long)__builtin_readcyclecounter(); } while (0)
 #define RLX_FC_STAMP(i) do { if (p.stamps && blockIdx.x == 0 && threadIdx.x == 0) p.stamps[i] = (long long)__builtin_readcyclecounter(); } while (0)
 
-__device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == RLX_ACT_RELU) return v > 0.f ? v : 0.f;
-    if (act == RLX_ACT_TANH) return tanhf(v);
-    return v;
-}
-__device__ __forceinline__ float act_deriv_out(float y, int kind) {
-    if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (kind == RLX_ACT_TANH) return 1.f - y * y;
-    return 1.f;
-}
 // write-through / L2-served accesses for data another workgroup of this launch wrote (guide G16: sc1 both sides)
 __device__ __forceinline__ void store4_sc1(float *p, f32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
@@ -449,12 +441,7 @@ int rlx_ppo_fc_heads(const rlx_ppo_fc_heads_desc *d_host, void *stream) {
     p.stamps = g_fc_stamps ? reinterpret_cast<long long *>(p.dyg + 2 * kRows * kMaxA) : nullptr;
     p.tick = d.tickets;
     const size_t lds = kLdsFloats * sizeof(float);
-    static bool configured = false;
-    if (!configured) {
-        RLX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_fc_heads_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        configured = true;
-    }
+    RLX_HIP(rlx::allow_lds<ppo_fc_heads_kernel>(lds));
     RLX_LAUNCH((ppo_fc_heads_kernel), 2 * p.NT * kSplits, kThreads, lds, rlx::as_stream(stream), p);
     RLX_LAUNCH_CHECK();
     return RLX_OK;

@@ -2,9 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <mutex>
 #include "../../include/rlx.h"
 
 namespace rlx {
@@ -51,6 +53,27 @@ inline void launch(const char *name, F kernel, dim3 grid, dim3 block, unsigned s
         if (g_prof.active) ++g_prof.dropped;
         kernel<<<grid, block, shmem, s>>>(args...);
     }
+}
+
+// Lets kKernel be launched with `bytes` of dynamic LDS (above the 64 KB a kernel gets without asking), on the CURRENT
+// device: the attribute belongs to the device, so the largest value set is remembered per device, and a launch on a
+// second GPU sets it there too.  Two threads may both make a first launch: the mutex keeps the value remembered equal to
+// the value set; later calls only read.  A larger `bytes` raises the value (mlp_fused.hip's LDS depends on the layer sizes).
+constexpr int kMaxDevices = 64;
+template <auto kKernel>
+inline hipError_t allow_lds(size_t bytes) {
+    static std::atomic<size_t> allowed[kMaxDevices];
+    static std::mutex first_launch;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::atomic<size_t> *seen = dev >= 0 && dev < kMaxDevices ? &allowed[dev] : nullptr;      // beyond the table: set every time
+    if (seen && bytes <= seen->load(std::memory_order_acquire)) return hipSuccess;
+    std::lock_guard<std::mutex> lock(first_launch);
+    if (seen && bytes <= seen->load(std::memory_order_relaxed)) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kKernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && seen) seen->store(bytes, std::memory_order_release);
+    return e;
 }
 
 // np.clip(x, lo, hi) = np.minimum(np.maximum(x, lo), hi) as numpy evaluates it: x is kept where it is a NaN or strictly

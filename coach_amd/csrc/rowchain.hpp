@@ -23,7 +23,7 @@
 // products, then bias).  Tolerances against the oracle are those of tests/test_ac_nets.py (another fp32 summation order,
 // not another algorithm).
 #pragma once
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace rlx_chain {
 
@@ -37,18 +37,8 @@ constexpr int kPitch = kMaxWidth + 4;      // row pitch of the activation buffer
 constexpr int kTileCols = 16;              // weight columns per LDS tile of a transposed product
 constexpr int kTilePitch = kTileCols + 4;  // pitch / 4 odd: the 16-byte reads of 16 consecutive rows hit 64 distinct banks
 constexpr int kTileFloats = kMaxWidth * kTilePitch;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using rlx::f32x4;
 
-__device__ __forceinline__ float act_apply(float v, int act) {
-    if (act == RLX_ACT_RELU) return v <= 0.f ? 0.f : v;       // np.maximum(v, 0): a NaN stays NaN (v > 0 ? v : 0 made it 0)
-    if (act == RLX_ACT_TANH) return tanhf(v);
-    return v;
-}
-__device__ __forceinline__ float act_deriv_out(float y, int kind) {
-    if (kind == RLX_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (kind == RLX_ACT_TANH) return 1.f - y * y;
-    return 1.f;
-}
 __device__ __forceinline__ int pad16(int n) { return (n + 15) & ~15; }
 
 // Touch a weight span so that it is on its way into this XCD's L2 (and this CU's TLB) before the layer that streams it
@@ -218,7 +208,7 @@ __device__ __forceinline__ void dense_fwd(const float *xs, int xp, int K, const 
         }
         float v = parts[(size_t)r * N + n];
         for (int s = 1; s < S; ++s) v += parts[(size_t)(s * RR + r) * N + n];
-        v = act_apply(bias ? v + bias[n] : v, act);
+        v = rlx::act_apply(bias ? v + bias[n] : v, act);
         ys[r * yp + n] = v;
         if (gout && row0 + r < B) gout[(long long)(row0 + r) * gld + n] = v;
     }

@@ -1,5 +1,5 @@
 // Runtime entry points of librlx.so: error reporting, device enumeration, HIP events.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 #include <cstring>
 
 namespace rlx {
@@ -14,6 +14,8 @@ Profiler g_prof;
 }  // namespace rlx
 
 namespace {
+using rlx::f32x4;
+using rlx::f32x16;
 // one lane follows `steps` dependent loads through a chain of indices: the duration / steps is the latency of whatever
 // level of the memory hierarchy the chain's footprint reaches (bench.py's `box` block)
 __global__ void probe_chase_kernel(const int *__restrict__ chain, int start, int steps, int *__restrict__ out) {
@@ -25,7 +27,6 @@ __global__ void probe_chase_kernel(const int *__restrict__ chain, int start, int
 // readings of the shader-clock counter and of the constant 100 MHz counter; lane 0 of every workgroup's wave 0 records
 // both differences: cycles per MFMA, and the clock the shader actually ran at under that load
 __global__ void __launch_bounds__(256) probe_mfma_kernel(int iters, long long *__restrict__ out, float *__restrict__ sink) {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -48,8 +49,6 @@ __global__ void __launch_bounds__(256) probe_mfma_kernel(int iters, long long *_
 // other instructions in it, not the issue rate).
 template <bool SMALL, int CHAINS>
 __global__ void __launch_bounds__(256) probe_mfma_shape_kernel(int iters, long long *__restrict__ out, float *__restrict__ sink) {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x16 big[CHAINS];
     f32x4 small[CHAINS];
 #pragma unroll
@@ -99,7 +98,6 @@ __global__ void __launch_bounds__(256) probe_requests_kernel(const float *__rest
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(
         static_cast<unsigned>(reinterpret_cast<uintptr_t>(ring)) + (unsigned)wid * 1024u);
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 v[K];
     __syncthreads();
     const long long c0 = clock64();
@@ -107,9 +105,7 @@ __global__ void __launch_bounds__(256) probe_requests_kernel(const float *__rest
     for (int k = 0; k < K; ++k) {
         const float *q = p + (size_t)k * 256 * 1024;           // another 1 MB page of the buffer per request
         if (LDS_DMA) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(q), "s"(lds0 + 4096u * k) : "memory");
+            rlx::dma16(q, lds0 + 4096u * k);
         } else {
             asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v[k]) : "v"(q) : "memory");
         }

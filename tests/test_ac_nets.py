@@ -457,6 +457,33 @@ def test_batchnorm_kernels_match_oracle(dev, B, C):
 
 
 @pytest.mark.gpu
+def test_batchnorm_relu_keeps_a_nan_input(dev):
+    """rlx_bn_forward with the moving statistics (no batch statistic sees the NaN) and a relu: a NaN in x[0, 0] is a NaN in
+    y[0, 0] alone, as in oracle.nn.act; the other elements keep the bits of the run without it."""
+    import torch
+    from coach_amd import _rlx
+    from oracle import nn as N
+    lib, s_ = _rlx.lib(), _rlx.current_stream()
+    B, C = 2, 2
+    rng = np.random.RandomState(3)
+    arr = {k: _t(v[0], dev) for k, v in _bn_arrays(rng, [("bn", C)]).items()}
+    x = (rng.randn(B, C) * 2 + 0.5).astype(F32)
+    xn = x.copy()
+    xn[0, 0] = np.nan
+
+    def run(xh):
+        y = torch.zeros(B, C, dtype=torch.float32, device=dev)
+        lib.bn_forward(_t(xh, dev), arr["bn/gamma"], arr["bn/beta"], arr["bn/moving_mean"], arr["bn/moving_variance"], B, C,
+                       1e-3, 0, 1, y, None, None, s_)
+        return y.cpu().numpy()
+    clean, got = run(x), run(xn)
+    nan = np.isnan(N.act(xn, "relu"))
+    assert nan.sum() == 1 and nan[0, 0] and not np.isnan(clean).any()
+    assert np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(got[~nan].view(np.uint32), clean[~nan].view(np.uint32))
+
+
+@pytest.mark.gpu
 def test_ddpg_batchnorm_update_matches_oracle(dev):
     """DDPGAgentParameters(use_batchnorm=True) (agents/ddpg_agent.py:111-122): four learn_from_batch steps of the device
     agent against oracle.ac_nets.ddpg_update on batch-normalised networks — batch statistics in every pass of the update

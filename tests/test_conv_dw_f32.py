@@ -50,6 +50,38 @@ def test_conv_dw_f32_matches_oracle(rlx, dev, geom, B, T):
     np.testing.assert_allclose(got_b, db_ref, rtol=2e-5, atol=2e-6 * np.abs(db_ref).max())
 
 
+def test_second_device_in_one_process_gets_the_lds_opt_in_too(rlx):
+    """The kernel's 160 KB of dynamic LDS is an attribute of the kernel ON ONE DEVICE: a process that has launched on device 0
+    must set it again for its first launch on device 1 (a process-wide flag left that launch unconfigured: a returned launch
+    error).  Same seeded input on both devices at the smallest supported shape: both calls succeed, equal outputs."""
+    import torch
+    from coach_amd import _rlx
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs in one process")
+    (H, W, C, k, S), B, T, Co = CONV3, 3, 1, 64
+    assert rlx.conv_dw_f32_supported(B, H, W, C, k, k, S, Co, T) == 1 and rlx.conv_dw_f32_supported(B - 1, H, W, C, k, k, S, Co, T) == 0
+    rng = np.random.RandomState(7)
+    x = np.tanh(rng.randn(T, B, H, W, C)).astype(np.float32)
+    P, K = ((H - k) // S + 1) * ((W - k) // S + 1), k * k * C
+    dz = rng.randn(T, B * P, Co).astype(np.float32)
+    need = ctypes.c_longlong()
+    rlx.conv_dw_f32_workspace_floats(B, H, W, C, k, k, S, Co, T, ctypes.byref(need))
+    outs = []
+    for i in (0, 1):
+        with torch.cuda.device(i):
+            dev = torch.device("cuda", i)
+            ws = torch.zeros(need.value, dtype=torch.float32, device=dev)
+            dw = torch.full((T, K, Co), float("nan"), dtype=torch.float32, device=dev)
+            db = torch.full((T, Co), float("nan"), dtype=torch.float32, device=dev)
+            job, s_ = _rlx.SplitkJob(), _rlx.current_stream()
+            rlx.conv_dw_f32(torch.from_numpy(x).to(dev), B * H * W * C, torch.from_numpy(dz).to(dev), B * P * Co, B, H, W, C, k, k, S,
+                            Co, T, dw, K * Co, db, Co, ws, need.value, ctypes.byref(job), s_)       # raises unless RLX_OK
+            _rlx.splitk_reduce_jobs([job], s_)
+            torch.cuda.synchronize()
+            outs.append((dw.cpu(), db.cpu()))
+    assert bool(torch.isfinite(outs[0][0]).all()) and torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
 def test_unsupported_shapes_are_refused(rlx):
     assert rlx.conv_dw_f32_supported(64, 9, 9, 64, 3, 3, 1, 32, 2) == 0       # 32 filters
     assert rlx.conv_dw_f32_supported(64, 10, 10, 64, 3, 3, 1, 64, 2) == 0     # another geometry

@@ -42,6 +42,16 @@ def _torso(dev, act, seed):
 @pytest.mark.parametrize("B,depth", [(64, (4, 1)), (72, (4, 1)), (64, (2, 1)), (64, (3, 1)), (64, (6, 1)), (64, (8, 1)),
                                      (64, (4, 2)), (72, (6, 2)), (64, (8, 2))])
 def test_fused_pair_equals_the_two_tiled_launches_bit_for_bit(rlx, dev, act, B, depth, request):
+    _pair_against_the_tiled_launches(rlx, dev, act, B, depth, request)
+
+
+def test_fused_pair_keeps_a_nan_like_the_tiled_launches(rlx, dev, request):
+    """One NaN bias entry in conv1 (frame bytes cannot be NaN): the tiled launches carry it through every relu
+    (np.maximum(z, 0)); the fused pair must show a NaN wherever they do, and their bits elsewhere."""
+    _pair_against_the_tiled_launches(rlx, dev, "relu", 64, (4, 1), request, nan_bias=True)
+
+
+def _pair_against_the_tiled_launches(rlx, dev, act, B, depth, request, nan_bias=False):
     import torch
     from coach_amd import _rlx
     from coach_amd.nn import graph as G
@@ -51,6 +61,8 @@ def test_fused_pair_equals_the_two_tiled_launches_bit_for_bit(rlx, dev, act, B, 
     request.addfinalizer(lambda: setattr(G, "FUSE_CONV_FIRST", True))
     assert G._kw2_tiling(B * 81, 64, 2) and G._kw2_tiling(B * 49, 64, 2)
     params, torso = _torso(dev, act, 1)
+    if nan_bias:
+        params.w(torso.layers[0].bname, 0)[5] = float("nan")
     obs = torch.from_numpy(np.random.RandomState(2).randint(0, 256, size=(B, 84, 84, 4)).astype(np.uint8)).to(dev)
     x = G.input_tensor(obs, B, 84 * 84 * 4, u8=True, div=255.0)
     outs, names = {}, {}
@@ -71,9 +83,13 @@ def test_fused_pair_equals_the_two_tiled_launches_bit_for_bit(rlx, dev, act, B, 
     assert len(outs[True]) == len(outs[False]) == 4
     for i, (a, b) in enumerate(zip(outs[True], outs[False])):
         assert a.shape == b.shape
+        if nan_bias:                                            # the same NaN mask, the other elements bit for bit
+            assert torch.equal(a.isnan(), b.isnan()), "layer %d: %d NaN against %d" % (i, int(a.isnan().sum()), int(b.isnan().sum()))
+            assert bool(b.isnan().any()) and not bool(b.isnan().all()), i       # (tower 0 carries it, tower 1 does not)
+            a, b = a.nan_to_num(nan=3.0), b.nan_to_num(nan=3.0)
         assert torch.equal(a, b), "layer %d: %d of %d elements differ, max %g" % (
             i, int((a != b).sum()), a.numel(), float((a - b).abs().max()))
-    assert float(outs[True][2].abs().max()) > 0.05              # (not a comparison of zeros)
+    assert float(outs[True][2].nan_to_num().abs().max()) > 0.05   # (not a comparison of zeros)
 
 
 @pytest.mark.parametrize("act", ["tanh", "relu"])

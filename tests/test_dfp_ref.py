@@ -172,14 +172,18 @@ def test_build_and_binding_carry_the_new_entry_points():
     # the merge is written once: the kernels call the header's function
     assert len(re.findall(r"rlx::dfp_merge_row\(", src)) == 2 and "mean" not in src.split("namespace {")[1]
     # the GEMM epilogues and the narrow-dense body other files include compile as before: leaky_relu is kernels of its own
-    gemm = open(os.path.join(ROOT, "coach_amd", "csrc", "gemm.hip")).read()
-    assert "LEAKY" not in gemm.split("float apply_act(")[1].split("// Loads 4 logically")[0]
+    csrc = {f: open(os.path.join(ROOT, "coach_amd", "csrc", f)).read()
+            for f in sorted(os.listdir(os.path.join(ROOT, "coach_amd", "csrc"))) if f.endswith((".hip", ".hpp"))}
+    gemm = csrc["gemm.hip"]
     assert "d.activation <= 2 && d.deriv_kind >= 0 && d.deriv_kind <= 2" in gemm and "leaky_relu_kernel" in gemm
-    body = open(os.path.join(ROOT, "coach_amd", "csrc", "dense_small_body.hpp")).read()
-    assert body.count("#ifdef RLX_DENSE_SMALL_LEAKY") == 2 == body.count("RLX_ACT_LEAKY_RELU")
-    users = [f for f in sorted(os.listdir(os.path.join(ROOT, "coach_amd", "csrc"))) if f.endswith((".hip", ".hpp"))
-             if "#define RLX_DENSE_SMALL_LEAKY" in open(os.path.join(ROOT, "coach_amd", "csrc", f)).read()]
-    assert users == ["dense_small.hip"]
+    # the one definition of the activations carries the leaky branch behind a compile-time parameter that is off by
+    # default, and the narrow-dense body alone passes it -- switched on by dense_small.hip alone
+    shared = csrc["rlx_device.hpp"]
+    assert shared.count("template <bool kLeaky = false>") == 2 == shared.count("if (kLeaky && ")
+    assert [f for f, s in csrc.items() if re.search(r"act_(apply|deriv_out)<", s)] == ["dense_small_body.hpp"]
+    assert csrc["dense_small_body.hpp"].count("#ifdef RLX_DENSE_SMALL_LEAKY") == 1
+    assert [f for f, s in csrc.items() if "RLX_ACT_LEAKY_RELU) return" in s] == ["rlx_device.hpp"]
+    assert [f for f, s in csrc.items() if "#define RLX_DENSE_SMALL_LEAKY" in s] == ["dense_small.hip"]
     assert "rlx_leaky_relu" in protos
     # the launches that do not implement leaky_relu still refuse an activation above 2
     for f, n in (("noisy_dense.hip", 2), ("batchnorm.hip", 2), ("conv_fused.hip", 2), ("conv_bwd_fused.hip", 1),

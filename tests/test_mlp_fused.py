@@ -101,6 +101,59 @@ def test_fused_update_selects_a_nan_of_the_target_net_like_the_layerwise_path(de
         assert np.isnan(td["f"]).all() and np.isnan(td["p"]).all() and np.isnan(loss["f"]) and np.isnan(loss["p"])
 
 
+def _nan_in_b1(net):
+    name = [n for n in net.params.entries if n.endswith("bias")][0]
+    for buf in (net.params.weights, net.target):
+        net.params.w(name, 0, buf=buf)[3] = float("nan")
+
+
+def test_fused_update_keeps_a_nan_of_the_first_bias_like_the_layerwise_path(dev):
+    """A NaN in one element of b1, online and target, at the smallest sizes rlx_mlp_dqn_supported accepts: unit 3 of the
+    first layer is NaN in every row after np.maximum(z, 0), so every Q value, every target, every |TD error| and the loss
+    are NaN on the layer-by-layer path (rlx_gemm's epilogue).  The one-launch update agrees (v > 0 ? v : 0 made the unit 0 and
+    trained on with finite values)."""
+    import torch
+    from coach_amd import _rlx
+    dims, A, B = (1, 32, 32), 1, 1
+    lib = _rlx.lib()
+    assert lib.rlx_mlp_dqn_supported(B, *dims, A) and not lib.rlx_mlp_dqn_supported(B, dims[0], 31, 32, A) \
+        and not lib.rlx_mlp_dqn_supported(B, dims[0], 32, 31, A) and not lib.rlx_mlp_dqn_supported(B - 1, *dims, A)
+    fused, plain = _net(dev, dims, A, True, True), _net(dev, dims, A, True, False)
+    rng = np.random.RandomState(3)
+    dv = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x)).to(dev).to(dt)
+    args = (dv(rng.randn(B, dims[0]).astype(np.float32), torch.float32), dv(rng.randn(B, dims[0]).astype(np.float32), torch.float32),
+            B, dv(rng.randint(0, A, B), torch.int32), dv(rng.randn(B).astype(np.float32), torch.float32),
+            dv(np.zeros(B), torch.uint8), 0.97)
+    for k, net in (("f", fused), ("p", plain)):
+        _nan_in_b1(net)
+        td = torch.zeros(B, dtype=torch.float64, device=dev)
+        loss = float(net.learn_from_batch(*args, td_errors=td).item())
+        print(k, "loss", loss, "|TD|", td.cpu().numpy())
+        assert np.isnan(td.cpu().numpy()).all() and np.isnan(loss), k
+
+
+def test_fused_q_act_keeps_a_nan_of_the_first_bias_like_the_layer_launches(dev):
+    """rlx_mlp_q_act at the smallest sizes rlx_mlp_q_act_supported accepts, one NaN in b1: Q(s) is NaN exactly where the
+    layer launches' Q(s) is (everywhere: the NaN unit feeds every unit of the second layer)."""
+    import torch
+    from coach_amd import _rlx
+    from coach_amd.nn.networks import DQNNet
+    (d0, h1, h2), A, n_env = (1, 4, 4), 1, 1
+    lib = _rlx.lib()
+    assert not lib.rlx_mlp_q_act_supported(n_env, d0, 3, h2, A) and not lib.rlx_mlp_q_act_supported(n_env, d0, h1, 3, A)
+    net = DQNNet(dev, (d0,), A, embedder=[h1], middleware=[h2], learning_rate=1e-3, seed=3)
+    assert net.can_act_fused(n_env)
+    s = torch.from_numpy(np.random.RandomState(1).randn(n_env, d0).astype(np.float32)).to(dev)
+    q = lambda: torch.zeros(n_env, A, dtype=torch.float32, device=dev)
+    clean, got = q(), q()
+    net.q_act(s, n_env, None, None, None, 0.0, clean, None)
+    _nan_in_b1(net)
+    net.q_act(s, n_env, None, None, None, 0.0, got, None)
+    ref = net.q_values(s, n_env, tag="ref").data.view(n_env, A)
+    assert not bool(clean.isnan().any()) and bool(ref.isnan().all())
+    assert torch.equal(got.isnan(), ref.isnan())
+
+
 def test_fused_update_is_reproducible(dev):
     """fixed summation orders: two runs from the same state give bit-identical weights."""
     import torch

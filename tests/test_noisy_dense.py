@@ -125,6 +125,24 @@ def test_zero_stddev_equals_the_plain_dense_layer(dev, M, K, N):
     _close("y", y, y_plain, OUT)
 
 
+def test_relu_keeps_a_nan_bias_mean(dev):
+    """One NaN bias-mean entry: that column is NaN in every row, as np.maximum(z, 0) leaves it (v > 0 ? v : 0 made it 0);
+    the other columns keep the bits of the run without the NaN."""
+    import torch
+    M, K, N, col = 1, 4, 256, 77
+    G, params, layer, ctx = _layer(dev, K, N, "relu")
+    rng = np.random.RandomState(5)
+    layer.noise(ctx, "t").copy_(torch.from_numpy(rng.randn(K + 2 * N).astype(np.float32)))
+    x = torch.from_numpy(rng.randn(M, K).astype(np.float32)).to(dev).view(1, M, K)
+    clean = layer.forward(ctx, G.Tensor(x, M, K, 1), tag="t").data.cpu().numpy().reshape(M, N)
+    params.w(layer.bmname)[col] = float("nan")
+    got = layer.forward(ctx, G.Tensor(x, M, K, 1), tag="t").data.cpu().numpy().reshape(M, N)
+    nan = np.zeros((M, N), bool)
+    nan[:, col] = True
+    assert not np.isnan(clean).any() and np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(got[~nan].view(np.uint32), clean[~nan].view(np.uint32))
+
+
 def test_every_pass_and_every_graph_replay_draws_its_own_noise(dev):
     import torch
     from coach_amd.nn.networks import DQNNet

@@ -71,3 +71,39 @@ def test_fc_heads_one_launch_matches_the_three_launch_path(dev, B, A):
     s2, g2 = _run(net, True, obs, B, actions, adv, vt, old)
     np.testing.assert_array_equal(s2, s1)
     np.testing.assert_array_equal(g2, g1)
+
+
+@pytest.mark.gpu
+def test_fc_heads_one_launch_keeps_a_nan_like_the_three_launch_path(dev):
+    """One NaN bias entry of the FC layer (value tower), relu, at the smallest batch the launch accepts: the three-launch
+    path (rlx_gemm's epilogue: np.maximum(z, 0)) shows it in h and in the value; the one launch must show a NaN exactly
+    where that path does (v > 0 ? v : 0 made it 0), and elsewhere the bits of its own run without the NaN."""
+    import torch
+    from coach_amd import _rlx
+    from coach_amd.nn.networks import ClippedPPONet
+    B, A, shape, unit = 1, 2, (84, 84, 4), 7
+    net = ClippedPPONet(dev, shape, A, seed=5, activation="relu")
+    assert _rlx.lib().ppo_fc_heads_supported(B, 3136, 512, A) and not _rlx.lib().ppo_fc_heads_supported(B - 1, 3136, 512, A)
+    rng = np.random.RandomState(B)
+    obs = torch.from_numpy(rng.randint(0, 256, size=(B,) + shape).astype(np.uint8)).to(dev)
+    actions = torch.from_numpy(rng.randint(0, A, size=B).astype(np.int32)).to(dev)
+    adv = torch.from_numpy(rng.randn(B).astype(np.float32)).to(dev)
+    vt = torch.from_numpy(rng.randn(B).astype(np.float32)).to(dev)
+    net.update_target(1.0)
+    old = net.policy_probs(obs, B, use_target=True, tag="old").clone()
+    fc = net.torso.layers[-1]
+    assert fc.act == "relu"
+
+    def outputs(fused):
+        _run(net, fused, obs, B, actions, adv, vt, old)
+        buf = lambda name, shp: net.ctx.buffer(name, shp, tag="train").cpu().numpy().copy()
+        return buf(fc.name, (2, B, 512)), buf("main/v_head/dense", (1, B, 1)), buf("main/ppo_head/policy_fc", (1, B, A))
+    clean = outputs(True)
+    net.params.w(fc.bname, 0)[unit] = float("nan")
+    three, one = outputs(False), outputs(True)
+    assert np.isnan(three[0][0, :, unit]).all() and np.isnan(three[0]).sum() == B and np.isnan(three[1]).all() \
+        and not np.isnan(three[2]).any()
+    for c, a, b in zip(clean, one, three):
+        assert not np.isnan(c).any()
+        assert np.array_equal(np.isnan(a), np.isnan(b))
+        assert np.array_equal(a[~np.isnan(a)].view(np.uint32), c[~np.isnan(a)].view(np.uint32))
