@@ -263,7 +263,7 @@ __global__ void __launch_bounds__(T) td3_critic_backward_kernel(const Td3Dev p) 
                 for (int q = 1; q < kSplit; ++q) v += pp[(size_t)q * B];
                 qs = v + p.cw[cm.o_b3 + s * cm.s3];
             }
-            const float qn = qt[0] <= qt[1] ? qt[0] : qt[1];                      // output #2: min over the streams (:168)
+            const float qn = rlx::np_min_takes_first(qt[0], qt[1]) ? qt[0] : qt[1];  // output #2: min over the streams (:168)
             const double qd = (double)qn;
             double t;
             if (p.nonzero_terminal) t = (double)p.rewards[i] + (double)((float)p.discount * qn);   // fp32 product (:173)
@@ -802,6 +802,7 @@ struct SacDev {
     double discount;
     int resample;
     int B, D, A, H, nrb, Bp, ldx, ldh;
+    int ld1P, ld2P, ld1V, ld2V;                     // pad64 of the policy's / V's own widths: h1P dh1Pp, h2P dz2P, h1V dh1Vp, h2V dz2V
     // padded (rows to 128, columns to 64, zero outside): operands of the weight-gradient launch
     float *xs, *ab, *h1P, *h1V, *ho, *h2P, *h2V, *haB, *hs, *h2Q;
     float *dyP, *dz2P, *dh1Pp, *dvV, *dz2V, *dh1Vp, *dqQ, *dfc1, *dhqp;
@@ -847,8 +848,8 @@ __global__ void __launch_bounds__(T, 4) sac_layer1_kernel(const SacDev p) {
     float *out;
     int N;
     long long gld = p.ldh;
-    if (net == 0) { W = p.pw + p.pm.o_w1; bias = p.pw + p.pm.o_b1; N = p.pm.h1; out = p.h1P; }
-    else if (net == 1) { W = p.vw + p.vm.o_w1; bias = p.vw + p.vm.o_b1; N = p.vm.h1; out = p.h1V; }
+    if (net == 0) { W = p.pw + p.pm.o_w1; bias = p.pw + p.pm.o_b1; N = p.pm.h1; out = p.h1P; gld = p.ld1P; }
+    else if (net == 1) { W = p.vw + p.vm.o_w1; bias = p.vw + p.vm.o_b1; N = p.vm.h1; out = p.h1V; gld = p.ld1V; }
     else if (net == 2) { W = p.vwt + p.vm.o_w1; bias = p.vwt + p.vm.o_b1; N = p.vm.h1; out = p.h1VT; gld = N; }
     else {
         const int t = net - 3;
@@ -881,14 +882,15 @@ __global__ void __launch_bounds__(T, 4) sac_layer2_kernel(const SacDev p) {
 #pragma unroll
         for (int j = 0; j < kW3; ++j)
             if (j * T < n3) w3v[j] = w3g[min(tid + j * T, n3 - 1)];
-        load_rows<RS>(x, SP, h1, net == 2 ? m.h1 : p.ldh, m.h1, row0, B);
+        load_rows<RS>(x, SP, h1, net == 0 ? p.ld1P : (net == 1 ? p.ld1V : m.h1), m.h1, row0, B);
 #pragma unroll
         for (int j = 0; j < kW3; ++j)
             if (j * T < n3 && tid + j * T < n3) z[tid + j * T] = w3v[j];
         __syncthreads();
         RLX_STAMP(9);
         float *save = net == 0 ? p.h2P + lo : (net == 1 ? p.h2V + lo : nullptr);
-        dense_fwd<RS>(x, SP, m.h1, w + m.o_w2 + lo, m.h2, w + m.o_b2 + lo, hi - lo, RLX_ACT_RELU, y, SP, parts, save, p.ldh, row0, B);
+        dense_fwd<RS>(x, SP, m.h1, w + m.o_w2 + lo, m.h2, w + m.o_b2 + lo, hi - lo, RLX_ACT_RELU, y, SP, parts, save,
+                      net == 0 ? p.ld2P : p.ld2V, row0, B);
         RLX_STAMP(10);
         if (net == 0) head_partial_lds<RS>(y, SP, z, hi - lo, 2 * A, p.zP + (size_t)c * 2 * A, (long long)kSplit * 2 * A, row0, B);
         else head_partial<RS>(y, SP, w + m.o_w3, lo, hi, 1, (net == 1 ? p.vp : p.vTp) + (size_t)c * B, 1, row0, B);
@@ -1014,7 +1016,7 @@ __global__ void __launch_bounds__(T) sac_q_grad_kernel(const SacDev p) {
                 for (int z = 1; z < kSplit; ++z) v += pp[(size_t)z * B];
                 qv[u] = v + p.qw[q.o_bq + u * q.s_q];
             }
-            const bool first = qv[0] <= qv[1];               // tf.minimum: x <= y -> x gets the gradient
+            const bool first = rlx::np_min_takes_first(qv[0], qv[1]);   // tf.minimum: x <= y -> x gets the gradient; a NaN is kept
             const float m = first ? qv[0] : qv[1];
             if (t == 0 && c == 0) {
                 p.log_target[i] = m;
@@ -1102,7 +1104,7 @@ __global__ void __launch_bounds__(T) sac_backward_kernel(const SacDev p) {
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int e = min(tid + it * T, RS * wc - 1), r = e / wc, col = e - r * wc;
-            bv[it] = p.h2P[(size_t)min(row0 + r, B - 1) * p.ldh + lo + col];
+            bv[it] = p.h2P[(size_t)min(row0 + r, B - 1) * p.ld2P + lo + col];
         }
         constexpr int kW3 = 9;                      // (h2 / kSplit + 4) 2 A <= 9 T (sac_check)
         float w3v[kW3];
@@ -1187,11 +1189,11 @@ __global__ void __launch_bounds__(T) sac_backward_kernel(const SacDev p) {
                 for (int n = 0; n < A2; ++n) acc = fmaf(dyb[r * HP + n], w3s[k * A2 + n], acc);
             const float v = (k < wc && b[r * SP + k] > 0.f) ? acc : 0.f;
             cb[r * SP + k] = v;
-            if (k < wc && row0 + r < B) p.dz2P[(size_t)(row0 + r) * p.ldh + lo + k] = v;
+            if (k < wc && row0 + r < B) p.dz2P[(size_t)(row0 + r) * p.ld2P + lo + k] = v;
         }
         __syncthreads();
         RLX_STAMP(37);
-        dense_bwdT<RS>(cb, SP, wc, p.pw + m.o_w2 + lo, m.h2, m.h1, nullptr, 0, d, SP, wt, p.dh1Pp + (size_t)c * p.Bp * p.ldh, p.ldh,
+        dense_bwdT<RS>(cb, SP, wc, p.pw + m.o_w2 + lo, m.h2, m.h1, nullptr, 0, d, SP, wt, p.dh1Pp + (size_t)c * p.Bp * p.ld1P, p.ld1P,
                        row0, B);
         RLX_STAMP(38);
     } else {
@@ -1202,8 +1204,9 @@ __global__ void __launch_bounds__(T) sac_backward_kernel(const SacDev p) {
         const Mlp3 &m = p.vm;
         const int NH = isv ? m.h2 : H;
         const int lo = slice_lo(NH, c), hi = slice_lo(NH, c + 1), wc = hi - lo;
+        const int ld2 = isv ? p.ld2V : p.ldh, ld1 = isv ? p.ld1V : p.ldh;     // of this network's second / first layer buffers
         RLX_STAMP_WG(2 * kSplit, 48);
-        load_rows<RS>(b, SP, (isv ? p.h2V : p.h2Q + (size_t)t * p.Bp * p.ldh) + lo, p.ldh, wc, row0, B);
+        load_rows<RS>(b, SP, (isv ? p.h2V : p.h2Q + (size_t)t * p.Bp * p.ldh) + lo, ld2, wc, row0, B);
         if (tid < RS) {
             const int i = row0 + tid;
             float dv = 0.f, term = 0.f;
@@ -1249,13 +1252,13 @@ __global__ void __launch_bounds__(T) sac_backward_kernel(const SacDev p) {
             float v = 0.f;
             if (k < wc && b[r * SP + k] > 0.f) v = small[r] * w3[k];
             cb[r * SP + k] = v;
-            if (k < wc && row0 + r < B) save[(size_t)(row0 + r) * p.ldh + k] = v;
+            if (k < wc && row0 + r < B) save[(size_t)(row0 + r) * ld2 + k] = v;
         }
         __syncthreads();
         RLX_STAMP_WG(2 * kSplit, 50);
         const float *w2 = isv ? p.vw + m.o_w2 + lo : p.qw + q.o_w1 + t * q.s_1 + lo;
-        float *part = isv ? p.dh1Vp + (size_t)c * p.Bp * p.ldh : p.dhqp + ((size_t)t * kSplit + c) * p.Bp * p.ldh;
-        dense_bwdT<RS>(cb, SP, wc, w2, NH, isv ? m.h1 : H, nullptr, 0, d, SP, wt, part, p.ldh, row0, B);
+        float *part = isv ? p.dh1Vp + (size_t)c * p.Bp * ld1 : p.dhqp + ((size_t)t * kSplit + c) * p.Bp * ld1;
+        dense_bwdT<RS>(cb, SP, wc, w2, NH, isv ? m.h1 : H, nullptr, 0, d, SP, wt, part, ld1, row0, B);
         RLX_STAMP_WG(2 * kSplit, 51);
     }
 }
@@ -1302,14 +1305,17 @@ inline SacWs sac_layout(const rlx_sac_fused_desc &d) {
     auto take = [&](long long n) { const long long at = o; o += (n + 3) & ~3LL; return at; };
     const long long B = d.batch, Bp = pad128(d.batch), ldx = pad64(d.obs_dim), ldh = pad64(d.q_hidden), H = d.q_hidden, A = d.act_dim;
     const long long nrb = (B + RS - 1) / RS;
+    // every buffer a row of which holds a policy / V layer has that layer's own padded width (sac_check accepts the five
+    // widths independently: with all of them at pad64(q_hidden) the rows of a wider policy / V layer overlapped)
+    const long long l1P = pad64(d.policy_mlp.h1), l2P = pad64(d.policy_mlp.h2), l1V = pad64(d.v_mlp.h1), l2V = pad64(d.v_mlp.h2);
     // (the operands of the weight-gradient launch first, padded; they rely on the workspace having been ZEROED at allocation)
     w.xs = take(Bp * ldx); w.ab = take(Bp * 64);
-    w.h1P = take(Bp * ldh); w.h1V = take(Bp * ldh); w.ho = take(2 * Bp * ldh); w.h2P = take(Bp * ldh); w.h2V = take(Bp * ldh);
+    w.h1P = take(Bp * l1P); w.h1V = take(Bp * l1V); w.ho = take(2 * Bp * ldh); w.h2P = take(Bp * l2P); w.h2V = take(Bp * l2V);
     w.haB = take(2 * Bp * ldh); w.hs = take(2 * Bp * ldh); w.h2Q = take(2 * Bp * ldh);
-    w.dyP = take(Bp * 64); w.dz2P = take(Bp * ldh); w.dh1Pp = take(kSplit * Bp * ldh);
-    w.dvV = take(Bp * 64); w.dz2V = take(Bp * ldh); w.dh1Vp = take(kSplit * Bp * ldh);
+    w.dyP = take(Bp * 64); w.dz2P = take(Bp * l2P); w.dh1Pp = take(kSplit * Bp * l1P);
+    w.dvV = take(Bp * 64); w.dz2V = take(Bp * l2V); w.dh1Vp = take(kSplit * Bp * l1V);
     w.dqQ = take(2 * Bp * 64); w.dfc1 = take(2 * Bp * ldh); w.dhqp = take(2LL * kSplit * Bp * ldh);
-    w.h1VT = take(B * H); w.zP = take(B * kSplit * 2 * A); w.vp = take(kSplit * B); w.vTp = take(kSplit * B); w.qp = take(2LL * kSplit * B);
+    w.h1VT = take(B * d.v_mlp.h1); w.zP = take(B * kSplit * 2 * A); w.vp = take(kSplit * B); w.vTp = take(kSplit * B); w.qp = take(2LL * kSplit * B);
     w.logp0 = take(B); w.haP = take(2 * B * H); w.h2Qp = take(2 * B * H); w.qpp = take(2LL * kSplit * B); w.dapp = take(2LL * kSplit * B * A);
     w.v_loss_part = take(nrb); w.q_loss_part = take(2 * nrb);
     w.norm_part = take(sac_blocks(d));
@@ -1317,6 +1323,11 @@ inline SacWs sac_layout(const rlx_sac_fused_desc &d) {
     w.total = o;
     return w;
 }
+// The rule for what the fused SAC update takes: the five widths (policy h1 / h2, V h1 / h2, q_hidden) are accepted
+// INDEPENDENTLY of each other, each in [32 kSplit, SP - 4] and a multiple of 4 -- and so sac_layout / SacDev must give
+// every buffer the padded width of the layer it holds (ld1P, ld2P, ld1V, ld2V for the policy's and V's, ldh for the Q
+// towers', v_mlp.h1 for h1VT), never another network's.  A width this check lets through and the layout cannot hold is
+// a wrong answer without a fault: the stray rows stay inside the workspace.
 inline int sac_check(const rlx_sac_fused_desc &d) {
     const rlx_mlp3 &pm = d.policy_mlp, &vm = d.v_mlp;
     const int H = d.q_hidden;
@@ -1343,6 +1354,7 @@ inline SacDev sac_dev(const rlx_sac_fused_desc &d) {
     p.normals = d.normals; p.discount = d.discount; p.resample = d.resample_noise_per_pass;
     p.B = d.batch; p.D = d.obs_dim; p.A = d.act_dim; p.H = d.q_hidden; p.nrb = (d.batch + RS - 1) / RS;
     p.Bp = pad128(d.batch); p.ldx = pad64(d.obs_dim); p.ldh = pad64(d.q_hidden);
+    p.ld1P = pad64(d.policy_mlp.h1); p.ld2P = pad64(d.policy_mlp.h2); p.ld1V = pad64(d.v_mlp.h1); p.ld2V = pad64(d.v_mlp.h2);
     float *ws = d.workspace;
     p.xs = ws + w.xs; p.ab = ws + w.ab; p.h1P = ws + w.h1P; p.h1V = ws + w.h1V; p.ho = ws + w.ho; p.h2P = ws + w.h2P; p.h2V = ws + w.h2V;
     p.haB = ws + w.haB; p.hs = ws + w.hs; p.h2Q = ws + w.h2Q; p.dyP = ws + w.dyP; p.dz2P = ws + w.dz2P; p.dh1Pp = ws + w.dh1Pp;
@@ -1516,9 +1528,9 @@ int rlx_sac_fused_update(const rlx_sac_fused_desc *d_host, int write_grads, void
     const rlx_mlp3 &pm = d.policy_mlp, &vm = d.v_mlp;
     const long long Bp = p.Bp, ldh = p.ldh;
     const int D = d.obs_dim, A = d.act_dim, H = d.q_hidden;
-    b.add_partial_job(np, p.xs, p.ldx, p.dh1Pp, ldh, kSplit, Bp * ldh, p.h1P, pm.off_w1, pm.off_b1, D, pm.h1);
-    b.add_job(np, p.h1P, ldh, p.dz2P, ldh, pm.off_w2, pm.off_b2, pm.h1, pm.h2);
-    b.add_job(np, p.h2P, ldh, p.dyP, 64, pm.off_w3, pm.off_b3, pm.h2, 2 * A);
+    b.add_partial_job(np, p.xs, p.ldx, p.dh1Pp, p.ld1P, kSplit, Bp * p.ld1P, p.h1P, pm.off_w1, pm.off_b1, D, pm.h1);
+    b.add_job(np, p.h1P, p.ld1P, p.dz2P, p.ld2P, pm.off_w2, pm.off_b2, pm.h1, pm.h2);
+    b.add_job(np, p.h2P, p.ld2P, p.dyP, 64, pm.off_w3, pm.off_b3, pm.h2, 2 * A);
     const int nq = b.add_net(d.q);
     for (int t = 0; t < 2; ++t) {
         b.add_partial_job(nq, p.xs, p.ldx, p.dhqp + (size_t)t * kSplit * Bp * ldh, ldh, kSplit, Bp * ldh, p.ho + (size_t)t * Bp * ldh,
@@ -1531,9 +1543,9 @@ int rlx_sac_fused_update(const rlx_sac_fused_desc *d_host, int write_grads, void
                   d.q_off_out_b + t * d.q_stride_out, H, 1);
     }
     const int nv = b.add_net(d.v);
-    b.add_partial_job(nv, p.xs, p.ldx, p.dh1Vp, ldh, kSplit, Bp * ldh, p.h1V, vm.off_w1, vm.off_b1, D, vm.h1);
-    b.add_job(nv, p.h1V, ldh, p.dz2V, ldh, vm.off_w2, vm.off_b2, vm.h1, vm.h2);
-    b.add_job(nv, p.h2V, ldh, p.dvV, 64, vm.off_w3, vm.off_b3, vm.h2, 1);
+    b.add_partial_job(nv, p.xs, p.ldx, p.dh1Vp, p.ld1V, kSplit, Bp * p.ld1V, p.h1V, vm.off_w1, vm.off_b1, D, vm.h1);
+    b.add_job(nv, p.h1V, p.ld1V, p.dz2V, p.ld2V, vm.off_w2, vm.off_b2, vm.h1, vm.h2);
+    b.add_job(nv, p.h2V, p.ld2V, p.dvV, 64, vm.off_w3, vm.off_b3, vm.h2, 1);
     b.a.loss_part = p.q_loss_part; b.a.loss_out = d.q_loss; b.a.loss_streams = 2; b.a.loss_parts = p.nrb; b.a.loss_scale = 1.f;
     b.a.loss2_part = p.v_loss_part; b.a.loss2_out = d.v_loss; b.a.loss2_parts = p.nrb;
     return launch_dw(b, d.batch, write_grads, d.workspace + w.norm_part, d.policy.ticket, st);

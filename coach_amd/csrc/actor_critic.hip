@@ -44,14 +44,15 @@ __global__ void axpby_kernel(float *out, float a, const float *x, float b, const
         out[i] = a * x[i] + (y ? b * y[i] : 0.f);
 }
 
-// out_min = min(q1, q2); g1/g2 = grad_scale * d mean(min)/d q_i  (tf.minimum: x <= y -> x gets it)
+// out_min = min(q1, q2); g1/g2 = grad_scale * d mean(min)/d q_i  (tf.minimum: x <= y -> x gets it; a NaN of either
+// side is the minimum, as in np.minimum: rlx::np_min_takes_first)
 __global__ void min_pair_kernel(const float *__restrict__ q1, const float *__restrict__ q2,
                                 float *__restrict__ out_min, float *__restrict__ g1,
                                 float *__restrict__ g2, float grad_scale, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float a = q1[i], b = q2[i];
-    const bool first = a <= b;
+    const bool first = rlx::np_min_takes_first(a, b);
     if (out_min) out_min[i] = first ? a : b;
     if (g1) g1[i] = first ? grad_scale : 0.f;
     if (g2) g2[i] = first ? 0.f : grad_scale;
@@ -66,7 +67,7 @@ __global__ void sac_min_targets_kernel(const float *__restrict__ q1, const float
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float a = q1[i], b = q2[i];
-    const bool first = a <= b;
+    const bool first = rlx::np_min_takes_first(a, b);
     const float m = first ? a : b;
     out_min[i] = m;
     value_targets[i] = m - logprob[i];

@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(kMaxBlock) ac_critic_losses_kernel(const AcCri
         float qn = a.q_next1[i];
         if (a.q_next2) {
             const float b = a.q_next2[i];
-            qn = qn <= b ? qn : b;
+            qn = rlx::np_min_takes_first(qn, b) ? qn : b;
         }
         if (a.q_min_out) a.q_min_out[i] = qn;
         const double q = (double)qn;

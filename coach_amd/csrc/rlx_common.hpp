@@ -84,6 +84,11 @@ __device__ __forceinline__ double np_clip(double x, double lo, double hi) {
     return (x < hi || x != x) ? x : hi;
 }
 
+// np.minimum(a, b) over the twin Q streams as a SELECTION (the value and the gradient of the minimum go to one side): a
+// where a <= b -- a tie goes to a, tf.minimum's gradient rule -- or where a is a NaN, b otherwise.  A NaN of either stream
+// comes through (`a <= b ? a : b` alone returned b for a NaN a); NaN-free inputs select as before.
+__device__ __forceinline__ bool np_min_takes_first(float a, float b) { return a <= b || a != a; }
+
 // One step of np.argmax over a row: the FIRST maximum wins and a NaN counts as the maximum, so the first NaN of a row
 // wins and nothing after it is looked at (argmax_rows_kernel, explore.hip).  bv / best: the running maximum and its index.
 __device__ __forceinline__ void np_argmax_step(float v, int a, float &bv, int &best) {

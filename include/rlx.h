@@ -928,7 +928,8 @@ int rlx_exp_rows(const float *log_std, float *out, int batch, int action_dim,
 int rlx_axpby(float *out, float a, const float *x, float b, const float *y, long long n,
               void *stream);                   /* out = a*x + b*y (y may be NULL: then out = a*x whatever b is; out may be
                                                 * x or y: in place); heads/sac_q_head.py:63-67 */
-/* out_min = min(q1,q2); grad_i = grad_scale * d sum(min)/d q_i (tf.minimum: ties go to q1).
+/* out_min = min(q1,q2); grad_i = grad_scale * d sum(min)/d q_i (tf.minimum: ties go to q1).  A NaN of either side is
+ * the minimum, as in np.minimum (q1's where q1 is one), and takes the gradient.
  * heads/sac_q_head.py:84-88, heads/td3_v_head.py:54-58 */
 int rlx_min_pair(const float *q1, const float *q2, float *out_min, float *grad1, float *grad2,
                  float grad_scale, int n, void *stream);

@@ -221,15 +221,16 @@ def ddpg_update(actor, critic, batch, discount=0.99, clip=None, non_zero_termina
 
 
 def td3_update(actor, critic, batch, noise, training_iteration, low, high, discount=0.99,
-               noise_clipping=0.5, policy_every=2):
-    """TD3Agent.learn_from_batch (agents/td3_agent.py:148-209); `noise` = np.random.normal(0, policy_noise, shape)."""
+               noise_clipping=0.5, policy_every=2, clip=None, non_zero_terminal=False):
+    """TD3Agent.learn_from_batch (agents/td3_agent.py:148-209); `noise` = np.random.normal(0, policy_noise, shape).
+    clip / non_zero_terminal: clip_critic_targets and use_non_zero_discount_for_terminal_states (:171-180)."""
     s, a, r, done, ns = batch
     next_actions = actor.forward(ns, target=True)
     actions_mean = actor.forward(s)
     sm = T.td3_smooth_actions(next_actions, noise, noise_clipping, low, high).astype(F32)
     q_next = critic.forward(ns, sm, target=True)
     q_min = np.minimum(q_next[0], q_next[1])
-    y = T.ac_td_targets(r, done, q_min[:, None], discount).astype(F32)[:, 0]
+    y = T.ac_td_targets(r, done, q_min[:, None], discount, non_zero_terminal, clip).astype(F32)[:, 0]
     critic.forward(s, a)
     losses = critic.train_backward(y)
     norm = critic.global_norm()
@@ -240,7 +241,7 @@ def td3_update(actor, critic, batch, noise, training_iteration, low, high, disco
         actor.forward(s)
         actor.backward(-g)
         actor.apply()
-    return dict(loss=float(sum(losses)), targets=y, norm=norm)
+    return dict(loss=float(sum(losses)), targets=y, norm=norm, q_min=q_min)
 
 
 # ------------------------------------------------------------------------------------------ SAC
@@ -351,7 +352,7 @@ class SACQOracle(_Net):
 
     def action_gradient(self, q):
         B = q.shape[1]
-        first = q[0] <= q[1]
+        first = (q[0] <= q[1]) | np.isnan(q[0])       # the side np.minimum(q[0], q[1]) takes: a NaN is the minimum
         dq = np.stack([np.where(first, F32(1.0 / B), F32(0)), np.where(first, F32(0), F32(1.0 / B))]).astype(F32)
         return self._backward(dq)
 

@@ -11,7 +11,7 @@ Every function takes the fp32 device inputs and evaluates in float64, so a resul
   copy_2d(src, scale)                       -> scale * src (exact in float64: a 24 x 24 bit product)
   axpby(a, x, b, y)                         -> (a x + b y, |a x| + |b y|)
   exp_rows(log_std, batch)                  -> tile(exp(log_std))
-  min_pair(q1, q2, grad_scale)              -> (min, g1, g2): a tie (q1 == q2, +-0.0 included) goes to q1
+  min_pair(q1, q2, grad_scale)              -> (min, g1, g2): a tie (q1 == q2, +-0.0 included) goes to q1; a NaN is kept
   sac_min_targets(q1, q2, logp, grad_scale) -> (min, min - logp, g1, g2)
   dueling_combine(v, adv) / _backward(dq)   -> float64;  dueling_combine_f32 / _backward_f32: fp32, sums in index order
   global_norm(x)                            -> sqrt(sum x^2)
@@ -50,9 +50,10 @@ def exp_rows(log_std, batch):
 
 def min_pair(q1, q2, grad_scale):
     """tf.minimum(q1, q2) and the gradient of its sum: TensorFlow gives the gradient of minimum(x, y) to x where
-    x <= y.  The value on a tie is q1's (which matters only for the sign of a zero)."""
+    x <= y.  The value on a tie is q1's (which matters only for the sign of a zero).  A NaN of either side is the minimum
+    (np.minimum / tf.minimum keep it): q1's where q1 is one, q2's otherwise, and value and gradient go to the same side."""
     q1, q2 = np.asarray(q1, dtype=F32), np.asarray(q2, dtype=F32)
-    first = q1 <= q2
+    first = (q1 <= q2) | np.isnan(q1)
     gs = F32(grad_scale)
     return np.where(first, q1, q2), np.where(first, gs, F32(0)), np.where(first, F32(0), gs)
 

@@ -155,6 +155,10 @@ def _min_pair_inputs(n):
     k = np.arange(n)
     q1[k % 7 == 3], q2[k % 7 == 3] = 0.0, -0.0               # +0 vs -0 compare equal: q1's +0 comes out
     q1[k % 7 == 5], q2[k % 7 == 5] = -0.0, 0.0               # ... and q1's -0 here
+    if n >= 257:                                             # a NaN of either stream is the minimum (np.minimum keeps it):
+        q1[14] = np.nan                                      # of q1 alone: value and gradient are q1's
+        q2[22] = np.nan                                      # of q2 alone: q2's
+        q1[30] = q2[30] = np.nan                             # of both: q1's
     return q1, q2
 
 

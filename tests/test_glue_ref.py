@@ -178,7 +178,11 @@ def test_small_references():
     assert np.array_equal(m, np.minimum(x, y)) and np.array_equal(g1 + g2, np.full(50, 0.25, dtype=F32))
     m, g1, g2 = R.min_pair(np.array([0.0, -0.0, 1.0], dtype=F32), np.array([-0.0, 0.0, 1.0], dtype=F32), 1.0)
     assert np.signbit(m).tolist() == [False, True, False] and g1.tolist() == [1, 1, 1] and g2.tolist() == [0, 0, 0]
-    dy = rng.randn(6).astype(F32)
+    nan = F32("nan")                       # a NaN of one side or of both is the minimum, as in np.minimum
+    m, g1, g2 = R.min_pair(np.array([nan, 1.0, nan], dtype=F32), np.array([1.0, nan, nan], dtype=F32), 1.0)
+    assert np.isnan(m).all() and np.isnan(np.minimum(nan, F32(1.0))) and np.isnan(np.minimum(F32(1.0), nan))
+    assert g1.tolist() == [1, 0, 1] and g2.tolist() == [0, 1, 0]
+    dy =rng.randn(6).astype(F32)
     yy = np.array([0.0, -0.0, 1e-40, -1e-40, 1.0, -1.0], dtype=F32)
     assert R.act_backward(dy, yy, "relu").tolist() == [0, 0, float(dy[2]), 0, float(dy[4]), 0]
     assert R.act_backward(dy, yy, "tanh")[4:].tolist() == [0, 0]
