@@ -11,8 +11,14 @@ uniforms for a row that keeps no action).  Its output is the ``q_next_selector``
 first-maximum argmax is the reference's np.argmax.
 
 ``DDQNBCQAgent`` is driven by graph_managers/batch_rl_graph_manager.py; the dataset side — freeze, training /
-evaluation split, shuffled epochs — is in memories/episodic/episodic_experience_replay.py.  NNImitationModelParameters
-is a parameter class only: the imitation network it asks for is not served, and the agent refuses it.
+evaluation split, shuffled epochs — is in memories/episodic/episodic_experience_replay.py.
+
+NNImitationModelParameters, the reference's second action-drop method (:115-118), is served when the agent's
+network_wrappers carry an `imitation_model` wrapper whose single head is a ClassificationHeadParameters (what the
+reference's CartPole_DDQN_BCQ_BatchRL preset writes): ``ImitationActionMask`` runs that classifier (nn.networks.
+ClassificationNet) on s' and masks the actions whose probability is below mask_out_actions_threshold with ONE launch,
+rlx_bcq_imitation_selector; improve_reward_model trains it next to the reward model (:143-183).  Without such a wrapper
+the reference silently deep-copies the reward model's Q head; this agent refuses that case.
 
 Departures from the reference, all stated in DESIGN §8: the search is exact; the zero-confidence rows draw
 counter-based device uniforms (Philox, keyed by seed and rank, at a device event counter) instead of np.random.rand,
@@ -29,12 +35,12 @@ from ..base_parameters import Parameters
 from ..core_types import EnvironmentSteps, RunPhase
 from ..exploration_policies.parameter_noise import ParameterNoiseParameters, network_is_noisy
 from ..memories.episodic.episodic_experience_replay import EpisodicExperienceReplayParameters
-from ..nn.networks import DQNNet, dqn_net_kwargs
+from ..nn.networks import ClassificationNet, DQNNet, classification_net_kwargs, dqn_net_kwargs
 from ..schedules import LinearSchedule
 from .dqn_agent import DQNAgent, DQNAgentParameters, DQNAlgorithmParameters, check_load_memory_from_file_path
 
 
-class NNImitationModelParameters(Parameters):            # ddqn_bcq_agent.py:31-38 (a parameter class only)
+class NNImitationModelParameters(Parameters):            # ddqn_bcq_agent.py:31-38 (served by ImitationActionMask)
     def __init__(self):
         super().__init__()
         self.imitation_model_num_epochs = 100
@@ -140,6 +146,53 @@ class KNNActionMask(object):
         return out
 
 
+class ImitationActionMask(object):
+    """select_actions' NNImitationModelParameters branch (:115-133) up to its argmax: the imitation network's logits on
+    s', then rlx_bcq_imitation_selector — familiarity = their softmax (the network's predict, bit for bit), -inf where
+    familiarity < np.float32(mask_out_actions_threshold) (numpy compares the fp32 prediction with the Python float in
+    fp32), device uniforms for a row that keeps no action (KNNActionMask's draws on the same seed, rank and event)."""
+
+    def __init__(self, device, n_actions, parameters, net, seed=0, rank=0):
+        if not isinstance(parameters, NNImitationModelParameters):
+            raise ValueError('Unsupported action drop method {} for ImitationActionMask'.format(type(parameters)))
+        if not 1 <= int(n_actions) <= 18 or net.A != int(n_actions):
+            raise ValueError("the imitation action mask serves 1 to 18 actions and a network of as many classes, got %d "
+                             "and %d" % (n_actions, net.A))
+        self.lib = _rlx.lib()
+        self.device, self.A, self.p, self.net = device, int(n_actions), parameters, net
+        self.seed, self.rank = int(seed) & 0xFFFFFFFF, int(rank) & 0xFFFFFFFF
+        self.zero_rows = torch.zeros(1, dtype=torch.int32, device=device)
+
+    @property
+    def threshold(self):
+        return float(np.float32(self.p.mask_out_actions_threshold))
+
+    def selector(self, q_next_online, next_states, event, familiarity=None, out=None):
+        """-> sel [B, A], as KNNActionMask.selector; next_states are the observations of s' (the imitation network's
+        input), familiarity (optional, [B, A]) receives the probabilities.  self.zero_rows counts the rows that kept no
+        action."""
+        B, A = q_next_online.shape
+        if A != self.A or q_next_online.dtype != torch.float32 or q_next_online.stride(1) != 1:
+            raise ValueError("q_next_online is fp32 [B, %d] rows" % self.A)
+        z = self.net.logits(next_states, B, tag="next_im").data
+        if out is None:
+            out = torch.empty(B, A, dtype=torch.float32, device=self.device)
+        self.lib.bcq_imitation_selector(q_next_online.data_ptr(), q_next_online.stride(0), z, A, self.threshold, 0, B, A,
+                                        self.seed, self.rank, event, out.data_ptr(), out.stride(0),
+                                        None if familiarity is None else familiarity.data_ptr(),
+                                        A if familiarity is None else familiarity.stride(0), self.zero_rows,
+                                        _rlx.current_stream())
+        return out
+
+
+def imitation_model_wrapper(ap):
+    """the `imitation_model` network wrapper an NNImitationModelParameters agent is served with, or None"""
+    from ..architectures.head_parameters import ClassificationHeadParameters
+    w = ap.network_wrappers.get('imitation_model')
+    heads = list(getattr(w, "heads_parameters", ())) if w is not None else []
+    return w if len(heads) == 1 and isinstance(heads[0], ClassificationHeadParameters) else None
+
+
 class DDQNBCQAgentParameters(DQNAgentParameters):        # ddqn_bcq_agent.py:65-74
     def __init__(self):
         super().__init__()
@@ -153,7 +206,8 @@ class DDQNBCQAgentParameters(DQNAgentParameters):        # ddqn_bcq_agent.py:65-
 
 
 class DDQNBCQAgent(DQNAgent):
-    """Double DQN on a frozen dataset whose target action is restricted by the kNN action mask (ddqn_bcq_agent.py:79-223).
+    """Double DQN on a frozen dataset whose target action is restricted by the kNN action mask, or by the imitation
+    model's (NNImitationModelParameters with an imitation_model wrapper) (ddqn_bcq_agent.py:79-223).
     It never steps an environment to learn: train() is one shuffled epoch over the memory's training set.  A second
     network, `reward_model` (a DQNNet of its own wrapper parameters), is fitted to the rewards first; the embeddings
     the mask compares are its input embedder's output."""
@@ -164,9 +218,14 @@ class DDQNBCQAgent(DQNAgent):
         if not getattr(ap, "is_batch_rl_training", False):
             raise ValueError('DDQNBCQ agent can only be used in BatchRL')
         drop = ap.algorithm.action_drop_method_parameters
-        if isinstance(drop, NNImitationModelParameters):
-            raise ValueError('NNImitationModelParameters is not served yet by DDQNBCQAgent: only KNNParameters is')
-        if not isinstance(drop, KNNParameters):
+        imp = imitation_model_wrapper(ap) if isinstance(drop, NNImitationModelParameters) else None
+        if isinstance(drop, NNImitationModelParameters) and imp is None:
+            raise ValueError('NNImitationModelParameters is not served yet by DDQNBCQAgent without an imitation_model '
+                             'network wrapper whose single head is a ClassificationHeadParameters (the reference would '
+                             'deep-copy the reward model\'s Q head there)')
+        if imp is not None and network_is_noisy(imp):
+            raise ValueError("noisy dense layers are not implemented for DDQNBCQAgent's imitation model")
+        if imp is None and not isinstance(drop, KNNParameters):
             raise ValueError('Unsupported action drop method {} for DDQNBCQAgent'.format(type(drop)))
         if environment.p.kind == "image":
             raise ValueError("DDQNBCQAgent serves vector observations, not image observations")
@@ -185,8 +244,15 @@ class DDQNBCQAgent(DQNAgent):
         obs_shape = tuple(environment.p.observation_shape)
         rm = self.networks["reward_model"] = DQNNet(self.device, obs_shape, self.A, **dqn_net_kwargs(rmp, ap.seed or 0))
         rm.l2_regularization = float(getattr(rmp, "l2_regularization", 0) or 0)
-        self.mask = KNNActionMask(self.device, self.A, drop, seed=ap.seed or 0,
-                                  rank=self.dist.rank if self.dist is not None else 0)
+        rank = self.dist.rank if self.dist is not None else 0
+        if imp is not None:
+            im = self.networks["imitation_model"] = ClassificationNet(self.device, obs_shape, self.A,
+                                                                      **classification_net_kwargs(imp, ap.seed or 0))
+            self.mask = ImitationActionMask(self.device, self.A, drop, im, seed=ap.seed or 0, rank=rank)
+        else:                                          # (an imitation_model wrapper next to KNNParameters is not built)
+            self.mask = KNNActionMask(self.device, self.A, drop, seed=ap.seed or 0, rank=rank)
+        self.imitation = imp is not None
+        self.model_updates = []                        # improve_reward_model's (epoch, batch, network) in order
         self.training_epoch = 0
         self.target_copies = 0
         self._event = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -221,19 +287,44 @@ class DDQNBCQAgent(DQNAgent):
         rm.accumulate_regression(obs, B, targets)
         rm.apply_gradients(self._grad_scale("reward_model"))
 
+    def _imitation_update(self, batch, B):
+        """:168-171: the imitation model trained on the one-hot rows of the batch's actions (never formed: the loss
+        launch reads the actions) + train_and_sync_networks"""
+        im = self.networks["imitation_model"]
+        im.train_on_batch(batch._states["observation"], B, actions=batch.actions(),
+                          grad_scale=self._grad_scale("imitation_model"))
+
     def improve_reward_model(self, epochs):
-        """:135-216: `epochs` shuffled epochs of the reward model over the training set, then the per-action key sets
-        and average_dist over every transition of the complete episodes"""
+        """:135-216: shuffled epochs over the training set — ONE generator per epoch; per batch the reward model's update
+        while epoch < epochs, then (NNImitationModelParameters) the imitation model's while epoch <
+        imitation_model_num_epochs; total_epochs = max of the two.  The batch size is the reward model's.  With
+        KNNParameters: then the per-action key sets and average_dist over every transition of the complete episodes
+        (returned); no key sets are built for an imitation model.  The per-epoch loss sums are kept in
+        reward_model_losses / imitation_model_losses, the order of the updates in model_updates."""
         size = self.ap.network_wrappers['reward_model'].batch_size
-        self.reward_model_losses = []
-        for _ in range(epochs):
+        drop = self.ap.algorithm.action_drop_method_parameters
+        imitation_epochs = int(drop.imitation_model_num_epochs) if self.imitation else 0
+        self.reward_model_losses, self.imitation_model_losses, self.model_updates = [], [], []
+        for epoch in range(max(epochs, imitation_epochs)):
             total = torch.zeros(1, dtype=torch.float32, device=self.device)
-            for batch in self.memory.get_shuffled_training_data_generator(size):
+            im_total = torch.zeros(1, dtype=torch.float32, device=self.device)
+            for i, batch in enumerate(self.memory.get_shuffled_training_data_generator(size)):
                 B = batch.size
-                targets = self._buffers(B)["targets"]
-                self._run(("reward_model", B), lambda: self._reward_update(batch, B, targets))
-                total += self.networks["reward_model"].loss
-            self.reward_model_losses.append(total)
+                if epoch < epochs:
+                    targets = self._buffers(B)["targets"]
+                    self._run(("reward_model", B), lambda: self._reward_update(batch, B, targets))
+                    total += self.networks["reward_model"].loss
+                    self.model_updates.append((epoch, i, "reward_model"))
+                if epoch < imitation_epochs:
+                    self._run(("imitation_model", B), lambda: self._imitation_update(batch, B))
+                    im_total += self.networks["imitation_model"].loss
+                    self.model_updates.append((epoch, i, "imitation_model"))
+            if epoch < epochs:
+                self.reward_model_losses.append(total)
+            if epoch < imitation_epochs:
+                self.imitation_model_losses.append(im_total)
+        if self.imitation:
+            return None
         mem = self.memory
         n = mem.num_transitions_in_complete_episodes()
         emb, actions = None, torch.empty(n, dtype=torch.int32, device=self.device)
@@ -259,8 +350,9 @@ class DDQNBCQAgent(DQNAgent):
         main = self.networks["main"]
         nxt = batch._next_states["observation"]
         q_sel = main.q_values(nxt, B, tag="next_o", noise_pass="online_next").data.view(B, self.A)
-        sel = self.mask.selector(q_sel, self.embedding(nxt, B, tag="embed_next"), self._event,
-                                 familiarity=bufs["familiarity"], out=bufs["selector"])
+        # what the mask reads of s': the kNN mask its embedding, the imitation mask the observation itself
+        seen = nxt if self.imitation else self.embedding(nxt, B, tag="embed_next")
+        sel = self.mask.selector(q_sel, seen, self._event, familiarity=bufs["familiarity"], out=bufs["selector"])
         torch.clamp(self.mask.zero_rows, max=1, out=self._zero_flag)
         self.zero_row_updates.add_(self._zero_flag)
         self.zero_rows_total.add_(self.mask.zero_rows)

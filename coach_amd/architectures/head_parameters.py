@@ -37,8 +37,9 @@ class DuelingQHeadParameters(HeadParameters):
 
 
 class ClassificationHeadParameters(HeadParameters):
-    """head_parameters.py:194-201 — a parameter class only: presets may name it (Batch RL's imitation model), no device
-    network has this head and an agent that is asked to build one refuses."""
+    """head_parameters.py:194-201 — Dense(A) class logits under a softmax, the softmax cross entropy summed over the batch
+    (heads/classification_head.py).  Served by nn.networks.ClassificationNet (rlx_classification_head_loss) and
+    ClassificationArchitecture: Batch RL's imitation model (agents/ddqn_bcq_agent.py, NNImitationModelParameters)."""
     head_type = "ClassificationHead"
 
     def __init__(self, activation_function='relu', name='classification_head_params',

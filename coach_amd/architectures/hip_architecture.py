@@ -672,6 +672,40 @@ class PolicyGradientArchitecture(HipArchitecture):
         return float(sc[0]), [float(sc[0])], float(net.norm.item()), fetched
 
 
+# ============================================================= Classification (imitation models)
+class ClassificationArchitecture(HipArchitecture):
+    """embedder -> FC middleware -> ClassificationHead, fed the way DDQNBCQAgent.improve_reward_model feeds the imitation
+    model (ddqn_bcq_agent.py:168-171): inputs 'observation', targets = the one-hot (or any dense) [B, A] label matrix.
+    predict -> [class probabilities (B, A)].  The loss is the softmax cross entropy SUMMED over the batch
+    (rlx_classification_head_loss)."""
+
+    def _build(self, agent_parameters, spaces, np_, seed):
+        from ..nn.networks import ClassificationNet, classification_net_kwargs
+        A = _discrete_actions(spaces, "the ClassificationHead over a Box action space (one output) is not served")
+        return ClassificationNet(self.device, _obs_shape(spaces), A, **classification_net_kwargs(np_, seed))
+
+    def _handles(self):
+        self.output_heads = [_HeadFetches(0, ['output'])]
+
+    def _queue(self, inputs, tag):
+        obs, B = self._observation(inputs)
+        return [self.net.predict(obs, B, tag="%s_%d" % (tag, B))]
+
+    def _accumulate_impl(self, inputs, targets, additional_fetches, importance_weights):
+        net = self.net
+        obs, B = self._observation(inputs)
+        target = targets[0] if isinstance(targets, (list, tuple)) else targets
+        target = self._to_device(target, torch.float32).contiguous()
+        if tuple(target.shape) != (B, net.A):
+            raise ValueError("targets shape {} does not match the head output {}".format(tuple(target.shape), (B, net.A)))
+        if importance_weights is not None:
+            raise ValueError("the ClassificationHead takes no importance weights")
+        net.accumulate_gradients(obs, B, labels=target)
+        total_loss = float(net.loss.item())
+        net.check_status()
+        return total_loss, [total_loss], float(net.norm.item()), _fetched({}, additional_fetches)
+
+
 # ========================================================================== Actor-Critic
 class ActorCriticArchitecture(HipArchitecture):
     """embedder -> FC middleware -> VHead (head 0) + discrete PolicyHead (head 1), fed the way
@@ -984,6 +1018,7 @@ class DFPArchitecture(HipArchitecture):
 
 
 _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitecture,
+                       "BCNetworkParameters": PolicyGradientArchitecture,          # a discrete PolicyHead, targets of ones
                        "DFPNetworkParameters": DFPArchitecture,
                        "PPOActorNetworkParameters": PPOActorArchitecture,
                        "PPOCriticNetworkParameters": PPOCriticArchitecture,
@@ -999,6 +1034,10 @@ _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitec
 def _family_of(network_parameters):
     """The family is decided by the class of `agent_parameters.network_wrappers[name]`, as
     GeneralTensorFlowNetwork decides by the head parameter classes it is given."""
+    from .head_parameters import ClassificationHeadParameters
+    heads = list(getattr(network_parameters, "heads_parameters", ()) or ())
+    if len(heads) == 1 and isinstance(heads[0], ClassificationHeadParameters):
+        return ClassificationArchitecture               # a wrapper of any class under a ClassificationHead
     for cls in type(network_parameters).__mro__:
         if cls.__name__ in _BY_PARAMETER_CLASS:
             return _BY_PARAMETER_CLASS[cls.__name__]

@@ -25,9 +25,9 @@
 // negative, so the unsigned order is the float order: deterministic).  Two small launches frame it: +inf into
 // dist_out[i][s] before, the square root after.  An empty set keeps +inf.
 //
-// rlx_bcq_masked_selector.  One workgroup, one row per thread (batch <= 1024, as rlx_dqn_head_loss).
-#include "philox.hpp"
-#include "rlx_common.hpp"
+// rlx_bcq_masked_selector.  One workgroup, one row per thread (batch <= 1024, as rlx_dqn_head_loss).  Its row tail (the
+// draws of a row that keeps no action, the count of such rows) is bcq_selector_tail.hpp's, shared with imitation.hip.
+#include "bcq_selector_tail.hpp"
 
 namespace {
 
@@ -157,7 +157,7 @@ struct SelArgs {
 };
 
 __global__ void __launch_bounds__(1024) bcq_masked_selector_kernel(const SelArgs a) {
-    __shared__ int red[1024];
+    __shared__ int red[rlx::kBcqSelectorMaxBatch];
     const int b = threadIdx.x, A = a.n_actions;
     int zero = 0;
     if (b < a.batch) {
@@ -170,24 +170,9 @@ __global__ void __launch_bounds__(1024) bcq_masked_selector_kernel(const SelArgs
             if (!(v == -INFINITY)) zero = 0;
             s[k] = v;
         }
-        if (zero) {
-            const unsigned long long ev = (unsigned long long)a.event[0];
-            for (int k = 0; k < A; ++k) {
-                const rlx::U4 r = rlx::philox4x32_10((uint32_t)ev, (uint32_t)(ev >> 32), (uint32_t)b, (uint32_t)k,
-                                                     a.seed, a.rank);
-                s[k] = (float)(r.x >> 8) * 5.9604644775390625e-8f;          // [0, 1): 24 bits, exact in fp32
-            }
-        }
+        if (zero) rlx::bcq_zero_row_draws(s, b, A, a.seed, a.rank, a.event);      // bcq_selector_tail.hpp
     }
-    if (a.zero_rows) {                                        // uniform: the barriers below are taken by all or none
-        red[b] = zero;
-        __syncthreads();
-        for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-            if (b < d) red[b] += red[b + d];
-            __syncthreads();
-        }
-        if (b == 0) a.zero_rows[0] = red[0];
-    }
+    rlx::bcq_zero_row_count(zero, a.zero_rows, red);
 }
 
 // The reward model's targets (agents/value_optimization_agent.py:173-180): the prediction with the taken action's
@@ -252,9 +237,7 @@ int rlx_bcq_masked_selector(const float *q_next_online, long long ld_q, const fl
     a.q = q_next_online; a.ld_q = ld_q; a.fam = familiarity; a.ld_f = ld_f; a.threshold = threshold;
     a.batch = batch; a.n_actions = n_actions; a.seed = seed; a.rank = rank; a.event = event;
     a.sel = sel_out; a.ld_sel = ld_sel; a.zero_rows = zero_rows_out;
-    int threads = 64;
-    while (threads < batch) threads <<= 1;
-    RLX_LAUNCH((bcq_masked_selector_kernel), 1, threads, 0, rlx::as_stream(stream), a);
+    RLX_LAUNCH((bcq_masked_selector_kernel), 1, rlx::bcq_selector_threads(batch), 0, rlx::as_stream(stream), a);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

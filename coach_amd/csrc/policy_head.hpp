@@ -11,7 +11,24 @@ constexpr int kPgThreads = 256;
 constexpr int kPgMaxActions = kDistMaxActions;
 constexpr float kPgEps = 1.1920928955078125e-07f;   // np.finfo(np.float32).eps (rl_coach/utils.py: eps)
 
-// p = softmax(z) as csrc/c51.hip defines it, q = p + eps, S = sum q (index order), log pi = log q - log S with
+// The project's ONE softmax over a row of action logits (as csrc/c51.hip defines it), fp32: mx = max z,
+// e_j = (float)exp((double)(z_j - mx)), s = sum e_j in index order, p_j = e_j / s.  Shared by pg_row below and by the
+// classification head and BCQ's imitation selector (imitation.hip), so a network's predict and the selector's
+// familiarity are the same bits.  mx and s are handed back for log p_j = (z_j - mx) - log s.
+__device__ __forceinline__ void softmax_row(const float *x, int A, float *p, float &mx_out, float &s_out) {
+    float mx = x[0];
+    for (int j = 1; j < A; ++j) mx = fmaxf(mx, x[j]);
+    float s = 0.f;
+    for (int j = 0; j < A; ++j) {
+        p[j] = (float)exp((double)(x[j] - mx));
+        s += p[j];
+    }
+    for (int j = 0; j < A; ++j) p[j] = p[j] / s;
+    mx_out = mx;
+    s_out = s;
+}
+
+// p = softmax_row(z), q = p + eps, S = sum q (index order), log pi = log q - log S with
 // log x = (float)log((double)x), H = -sum (q / S) * log pi.  All fp32.
 struct PgRow {
     float p[kPgMaxActions], q[kPgMaxActions], lp[kPgMaxActions];
@@ -19,16 +36,10 @@ struct PgRow {
 };
 
 __device__ __forceinline__ void pg_row(const float *x, int A, PgRow &r) {
-    float mx = x[0];
-    for (int j = 1; j < A; ++j) mx = fmaxf(mx, x[j]);
-    float s = 0.f;
-    for (int j = 0; j < A; ++j) {
-        r.p[j] = (float)exp((double)(x[j] - mx));
-        s += r.p[j];
-    }
+    float mx, s;
+    softmax_row(x, A, r.p, mx, s);
     float S = 0.f;
     for (int j = 0; j < A; ++j) {
-        r.p[j] = r.p[j] / s;
         r.q[j] = r.p[j] + kPgEps;
         S += r.q[j];
     }

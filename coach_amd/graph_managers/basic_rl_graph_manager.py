@@ -192,6 +192,25 @@ class BasicRLGraphManager(object):
         self._set_phase(RunPhase.TRAIN)
         self._fresh_episodes()
         agent = self.agent
+        playing = getattr(agent.ap.algorithm, "num_consecutive_playing_steps", None)
+        if isinstance(playing, EnvironmentSteps) and playing.num_steps == 0:
+            # an agent that never plays to learn (Behavioral Cloning from a loaded memory): training phases only, the
+            # environment is not stepped; the period is counted in training iterations
+            if not isinstance(steps, TrainingSteps):
+                raise ValueError("num_consecutive_playing_steps = EnvironmentSteps(0) never steps the environment while "
+                                 "training: give improve_steps and steps_between_evaluation_periods in TrainingSteps, "
+                                 "not {}".format(type(steps).__name__))
+            done = 0
+            while done < steps.num_steps:
+                before = agent.training_iteration
+                agent.train()
+                trained = agent.training_iteration - before
+                if trained == 0:
+                    raise ValueError("nothing to train on: the memory is empty and the environment is never stepped "
+                                     "(load_memory_from_file_path)")
+                self.training_steps += trained
+                done += trained
+            return
         fused = getattr(agent, "step_and_train", None)
         done = 0
         while done < steps.num_steps:

@@ -1220,6 +1220,108 @@ class NAFNet(_NetBase):
         return self.loss
 
 
+def classification_net_kwargs(np_, seed):
+    """a network wrapper whose single head is a ClassificationHeadParameters (Batch RL's imitation model) -> the keywords
+    of ClassificationNet's constructor"""
+    from ..architectures.head_parameters import ClassificationHeadParameters
+    heads = list(np_.heads_parameters)
+    if len(heads) != 1 or not isinstance(heads[0], ClassificationHeadParameters):
+        raise ValueError("ClassificationNet serves a wrapper with exactly one ClassificationHeadParameters head, got %s"
+                         % [type(h).__name__ for h in heads])
+    return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),
+                head_gradient_rescale=heads[0].rescale_gradient_from_head_by_factor,
+                l2_regularization=float(getattr(np_, "l2_regularization", 0) or 0))
+
+
+class ClassificationNet(_NetBase):
+    """One embedder + FC middleware tower under a ClassificationHead (heads/classification_head.py): Dense(feat, A) named
+    'output' whose values are the class logits; the head's output is their softmax.  No target copy.  The loss is the
+    softmax cross entropy SUMMED over the batch (the head adds the per-row vector with tf.losses.add_loss and
+    general_network.py:360 takes tf.reduce_sum), from rlx_classification_head_loss (csrc/imitation.hip); its softmax is
+    the one rlx_bcq_imitation_selector applies to `logits`, so `predict` and the selector's familiarity are the same bits."""
+
+    def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
+                 learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None,
+                 head_gradient_rescale=1.0, l2_regularization=0.0, seed=0):
+        self.A = discrete_policy_actions(n_actions)
+        self.clip_gradients = clip_gradients
+        self.head_gradient_rescale = float(head_gradient_rescale)
+        self.l2_regularization = float(l2_regularization)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        self.head = G.Dense(self.params, "main/classification_head/output", feat, self.A, None, 1)
+        self.modules = [self.torso, self.head]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self.scalars = torch.zeros(2, dtype=torch.float32, device=device)     # the batch's summed loss, its correct rows
+        self.loss, self.correct = self.scalars[0:1], self.scalars[1:2]
+        self.l2_norm = torch.zeros(1, dtype=torch.float32, device=device)
+        self._predict_scalars = torch.zeros(2, dtype=torch.float32, device=device)     # predict leaves self.loss alone
+        self._probs = {}
+
+    MAX_ROWS = 1024          # rlx_classification_head_loss: one workgroup, one row per thread
+
+    def logits(self, obs, B, tag="logits"):
+        """the head's Dense output [B, A] (a Tensor; .data is the buffer), valid until the next pass under the same tag"""
+        return self.head.forward(self.ctx, self.trunk_forward(obs, B, tag)[-1], tag=tag)
+
+    def _probs_buffer(self, B, tag):
+        buf = self._probs.get((B, tag))
+        if buf is None:
+            buf = self._probs[(B, tag)] = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
+        return buf
+
+    def _head_loss(self, z, B, actions, labels, grad_scale, dz, probs, scalars=None):
+        if (actions is None) == (labels is None):
+            raise ValueError("exactly one of actions and labels is given")
+        if not 1 <= B <= self.MAX_ROWS:
+            raise ValueError("the classification head's loss launch serves 1 to %d rows, got %d" % (self.MAX_ROWS, B))
+        if labels is not None and (tuple(labels.shape) != (B, self.A) or labels.dtype != torch.float32 or
+                                   not labels.is_contiguous()):
+            raise ValueError("labels is a contiguous fp32 [%d, %d] tensor" % (B, self.A))
+        self.lib.classification_head_loss(z.data, self.A, actions, labels, self.A, float(grad_scale), B, self.A, dz,
+                                          self.A, probs, self.A, None, self.scalars if scalars is None else scalars, self.status,
+                                          self.ctx.stream)
+
+    def predict(self, obs, B, tag="predict"):
+        """the head's output: the class probabilities, fp32 [B, A] (softmax_row of the logits: the launch's probs_out)"""
+        z = self.logits(obs, B, tag)
+        probs = self._probs_buffer(B, tag)
+        zeros = self._probs.get(B)                    # the launch wants a target: action 0 of every row, gradient scale 0
+        if zeros is None:
+            zeros = self._probs[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._head_loss(z, B, zeros, None, 0.0, z.ensure_grad(), probs, scalars=self._predict_scalars)
+        return probs
+
+    def accumulate_gradients(self, obs, B, actions=None, labels=None):
+        """forward, the head loss against the actions (int32 [B]) or the dense target rows (fp32 [B, A]: the one-hot
+        matrix the reference passes), backward: the gradients in params.grads (clipped when clip_gradients is set), the
+        summed loss in self.loss, tf.global_norm of the raw gradients in self.norm"""
+        ctx = self.ctx
+        acts = self.trunk_forward(obs, B, "train")
+        z = self.head.forward(ctx, acts[-1], tag="train")
+        self._head_loss(z, B, actions, labels, 1.0, z.ensure_grad(), None)
+        self.head.backward(ctx, acts[-1], z)
+        if self.head_gradient_rescale != 1.0:         # rescale_gradient_from_head_by_factor
+            g = acts[-1].grad
+            self.lib.axpby(g, self.head_gradient_rescale, g, 0.0, None, g.numel(), ctx.stream)
+        self.torso.backward(ctx, acts)
+        if self.l2_regularization:                    # general_network.py:354-358, as DQNNet._apply_update
+            lam, p = self.l2_regularization, self.params
+            self.lib.axpby(p.grads, 1.0, p.grads, lam, p.weights, p.size, ctx.stream)
+            self.lib.global_norm(p.weights, p.size, self.l2_norm, ctx.ws.small, ctx.ws.small.numel(), ctx.stream)
+            self.loss.addcmul_(self.l2_norm, self.l2_norm, value=0.5 * lam)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss
+
+    def train_on_batch(self, obs, B, actions=None, labels=None, grad_scale=1.0, sync=None):
+        """Architecture.train_on_batch: accumulate_gradients, then one Adam step"""
+        self.accumulate_gradients(obs, B, actions=actions, labels=labels)
+        if sync is not None:
+            sync.all_reduce_sum(self.params.grads)
+        self.apply_gradients(grad_scale)
+        return self.loss
+
+
 def policy_gradient_net_kwargs(np_, alg, seed):
     """PolicyGradientNetworkParameters + the algorithm's beta_entropy -> the keywords of PolicyGradientNet's constructor"""
     return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),
@@ -1307,6 +1409,13 @@ class PolicyGradientNet(_WindowAccumulatingNet):
                               self.A, self.scalars, self.status, ctx.stream)
         self.head.backward(ctx, acts[-1], z)
         return self._finish_window(acts)
+
+    def learn_from_batch(self, obs, B, actions, advantages, grad_scale=1.0):
+        """one NON-accumulating update on a batch of B rows: window_gradients, then one Adam step on params.grads
+        (Architecture.train_on_batch; BCAgent.learn_from_batch with advantages of ones).  `accumulated` is not touched."""
+        loss = self.window_gradients(obs, B, actions, advantages)
+        self.adam.step(float(grad_scale))
+        return loss
 
 
 def actor_critic_net_kwargs(np_, alg, seed):

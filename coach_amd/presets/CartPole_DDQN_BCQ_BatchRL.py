@@ -10,14 +10,18 @@ reward-model epochs (lr 1e-4, no L2), greedy evaluation over 10 episodes after e
 (coach_amd/environments/cartpole_vector_environment.py).  make(off_policy_evaluation=True) adds what the reference preset
 sets for its off-policy evaluators: softmax_temperature = 0.2 on the `main` and `reward_model` wrappers, and the graph
 manager's switch (IPS, DM, DR, sequential DR and WIS after every epoch, in that epoch's CSV row).  It is off by default:
-the module-level graph_manager is the experiment as it was.  The reference preset's imitation-model wrapper stays out of
-scope and is not set.  make(dataset=path) trains on a logged CSV file instead of collecting (there is no
+the module-level graph_manager is the experiment as it was.  make(action_drop="nn") drops actions by the reference's
+second method instead: NNImitationModelParameters with the imitation-model wrapper of the reference preset's text (a
+ClassificationHead on Dense 1024-1024-512-512-256 and 128-64, lr 1e-4, no L2); the default "knn" sets no
+such wrapper and is the experiment as it was.  make(dataset=path) trains on a logged CSV file instead of collecting (there is no
 collecting agent then, and the environment only evaluates); with_environment=False runs without a simulator at all, from
 the spaces definition of CartPole: the epochs' rows then carry the off-policy estimates and no evaluation reward.
 """
 from copy import deepcopy
 
-from coach_amd.agents.ddqn_bcq_agent import DDQNBCQAgentParameters, KNNParameters
+from coach_amd.agents.ddqn_bcq_agent import DDQNBCQAgentParameters, KNNParameters, NNImitationModelParameters
+from coach_amd.architectures.head_parameters import ClassificationHeadParameters
+from coach_amd.architectures.layers import Dense
 from coach_amd.agents.dqn_agent import DQNAgentParameters
 from coach_amd.base_parameters import PresetValidationParameters, VisualizationParameters
 from coach_amd.core_types import CsvDataset, EnvironmentEpisodes, EnvironmentSteps, TrainingSteps
@@ -36,11 +40,14 @@ DATASET_SIZE = 10000
 
 def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, reward_model_num_epochs=30,
          improve_epochs=10000000000, batch_size=128, evaluation_episodes=10, train_to_eval_ratio=0.4,
-         off_policy_evaluation=False, dataset=None, with_environment=True):
+         off_policy_evaluation=False, dataset=None, with_environment=True, action_drop="knn"):
     """seed: the environment's reset-state streams; agent_seed: both agents' host generators and initial weights;
     off_policy_evaluation: the five off-policy estimates after every epoch (softmax_temperature 0.2);
     dataset: the path of a CSV file of logged transitions (core_types.CsvDataset) the trained agent's memory starts as;
-    with_environment: False — no simulator (needs a dataset)"""
+    with_environment: False — no simulator (needs a dataset);
+    action_drop: "knn" — the kNN action mask; "nn" — the imitation model's mask (NNImitationModelParameters)"""
+    if action_drop not in ("knn", "nn"):
+        raise ValueError('action_drop is "knn" or "nn", got %r' % (action_drop,))
     sched = ScheduleParameters()
     sched.improve_steps = TrainingSteps(improve_epochs)
     sched.steps_between_evaluation_periods = TrainingSteps(1)
@@ -62,6 +69,13 @@ def make(seed=1234, agent_seed=0, dataset_size=DATASET_SIZE, heatup_steps=1000, 
     agent.network_wrappers['reward_model'] = deepcopy(main)
     agent.network_wrappers['reward_model'].learning_rate = 0.0001
     agent.network_wrappers['reward_model'].l2_regularization = 0
+    if action_drop == "nn":
+        agent.algorithm.action_drop_method_parameters = NNImitationModelParameters()
+        im = agent.network_wrappers['imitation_model'] = deepcopy(main)
+        im.learning_rate, im.l2_regularization = 0.0001, 0
+        im.heads_parameters = [ClassificationHeadParameters()]
+        im.input_embedders_parameters['observation'].scheme = [Dense(1024), Dense(1024), Dense(512), Dense(512), Dense(256)]
+        im.middleware_parameters.scheme = [Dense(128), Dense(64)]
     if off_policy_evaluation:
         main.softmax_temperature = 0.2
         agent.network_wrappers['reward_model'].softmax_temperature = 0.2

@@ -1889,6 +1889,47 @@ int rlx_wolpertinger_select(const float *q, long long q_stride, const int *idx, 
 int rlx_discrete_to_box(const int *actions, int batch, const float *target_actions, long long ld_t, long long n_actions,
                         int action_dim, float *out, long long ld_out, int *status, void *stream);
 
+/* ------------------------------------ Imitation learning: classification head, BCQ's imitation-model mask -- */
+/* (csrc/imitation.hip; bit-exact numpy twin: tests/imitation_ref.py.  Entry points ADDED under ABI version 11: no
+ * existing signature or structure changed.)  Both are one launch of one workgroup, one row per thread, capturable,
+ * deterministic (no atomics in any sum), and share ONE softmax with rlx_pg_head_loss (csrc/policy_head.hpp, softmax_row):
+ *   mx = max_j z_j;  e_j = (float)exp((double)(z_j - mx));  s = sum_j e_j in index order;  p_j = e_j / s      (all fp32)
+ *
+ * rlx_classification_head_loss: ClassificationHead (architectures/tensorflow_components/heads/classification_head.py)
+ * between the forward and the backward pass.  logits [rows][ld]; the target is EITHER actions (int32 [rows]: the one-hot
+ * row, never formed) OR labels (fp32 [rows][ld_labels], the dense matrix Architecture.train_on_batch is handed): exactly
+ * one of the two is not NULL.  Per row, fp32:
+ *   log p_j = (z_j - mx) - (float)log((double)s)
+ *   actions: loss_b = -log p_a                         labels: loss_b = -(sum_j l_j * log p_j), index order from 0.f
+ *   dlogits[b][j] = (p_j - l_j) * grad_scale           (tf.nn.softmax_cross_entropy_with_logits: no sum-of-labels
+ *                                                       factor; l is the one-hot row in actions mode)
+ * The head hands the per-row vector to tf.losses.add_loss and general_network.py:360 takes its tf.reduce_sum, so
+ * scalars[0] = SUM_b loss_b — not a mean, and dlogits carries no 1 / rows — summed through the tree of a workgroup of
+ * T = max(64, rows rounded up to a power of two) threads (thread b holds loss_b, 0.f beyond the batch; for d = T / 2,
+ * T / 4 .. 1: v[b] += v[b + d] for b < d).  The head's loss_weight is not applied, as in the reference.
+ * scalars[1] = the number of rows whose first-maximum argmax of p equals the action (labels: the labels' first maximum).
+ * Optional outputs: probs_out [rows][ld_probs] = p (the head's output, what predict returns), row_loss_out [rows].
+ * status bit 0: an action outside [0, n_actions); that row has no term (row_loss_out 0), a zero gradient and is not
+ * counted.  Columns [n_actions, ld) of every output are not written.  1 <= rows <= 1024, 1 <= n_actions <= 18. */
+int rlx_classification_head_loss(const float *logits, long long ld, const int *actions, const float *labels,
+                                 long long ld_labels, float grad_scale, int rows, int n_actions, float *dlogits,
+                                 long long ld_dlogits, float *probs_out, long long ld_probs, float *row_loss_out,
+                                 float *scalars, int *status, void *stream);
+/* DDQNBCQAgent.select_actions, NNImitationModelParameters branch, up to its argmax (agents/ddqn_bcq_agent.py:115-133).
+ * imitation [batch][ld_i] is the imitation model's output on the next states: its logits (familiarity = the softmax
+ * above, hence the bits of the network's predict), or with RLX_IMITATION_INPUT_PROBS in flags the probabilities
+ * themselves.  familiarity_out (optional, [batch][ld_f]) receives the familiarity.  sel_out[b][a] = q_next_online[b][a],
+ * or -inf where familiarity[b][a] < threshold: an fp32 comparison, as numpy compares a float32 array with a Python
+ * float (the host passes np.float32(mask_out_actions_threshold)); a NaN familiarity is not masked.  A row that keeps no
+ * action gets rlx_bcq_masked_selector's draws on the same (seed, rank, event) — one definition,
+ * csrc/bcq_selector_tail.hpp — and is counted in zero_rows_out (optional device int).  event is READ FROM DEVICE
+ * MEMORY.  One workgroup: batch <= 1024, 1 <= n_actions <= 18. */
+#define RLX_IMITATION_INPUT_PROBS 1
+int rlx_bcq_imitation_selector(const float *q_next_online, long long ld_q, const float *imitation, long long ld_i,
+                               float threshold, int flags, int batch, int n_actions, unsigned int seed,
+                               unsigned int rank, const long long *event, float *sel_out, long long ld_sel,
+                               float *familiarity_out, long long ld_f, int *zero_rows_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
