@@ -39,6 +39,25 @@ constexpr int LD = 33;                 // LDS row pitch (words): conflict-free f
 constexpr int kMaxA = 16;
 constexpr int kSpinLimit = 1 << 22;    // ~ a second of s_sleep polling; a stuck barrier reports status bit 8
 
+// The LDS carve of mlp_dqn_update_kernel in floats: xs0, xs1 [D0p][LD]; h1a, h1b, w2s [H1][LD]; then the blocks below,
+// whose sizes do not depend on the shape.  lds_floats() and the kernel's carve are both written in these constants.
+constexpr int kRedFloats = 4 * 32 * LD;          // red        [4][32][LD]
+constexpr int kTileFloats = 32 * LD;             // h2a, h2b, dz2, dz2t   [32][LD] each
+constexpr int kQsFloats = 3 * 32 * kMaxA;        // qs         [3][32][A]
+constexpr int kDqsFloats = 32 * kMaxA;           // dqs        [32][A]
+constexpr int kB3Floats = 2 * kMaxA;             // b3s        [2][A]
+constexpr int kW3Floats = 2 * 32 * kMaxA;        // w3s        [2][32][A]
+constexpr int kRedToLred = kRedFloats + 4 * kTileFloats + kQsFloats + kDqsFloats + kB3Floats;   // from red to lred
+constexpr int kFixedFloats = kRedToLred + kThreads + kW3Floats;
+constexpr int kLdsLimitBytes = 160 * 1024;
+// the largest first-layer width rlx_mlp_dqn_supported can accept: a multiple of 32 that fits beside the smallest input
+// block (D0p = 2)
+constexpr int kMaxH1 = (kLdsLimitBytes / 4 - kFixedFloats - 2 * 2 * LD) / (3 * LD) / 32 * 32;
+// After the second barrier dz1 [32][S1] (S1 = H1 / G <= H1) is staged at `red` and runs past it whenever S1 > 132: into
+// h2a, h2b, dz2, dz2t, qs, dqs and b3s, all dead by then (last read in front of that barrier).  It must end in front of
+// lred, which the norm reduction behind it writes, and w3s.
+static_assert(32 * kMaxH1 <= kRedToLred, "dz1 [32][H1 / G] staged at `red` would reach lred");
+
 struct MlpDqnDev {
     float *w;                 // online weights (flat)           [updated]
     const float *wt;          // target weights (flat)
@@ -236,14 +255,14 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
     float *h1b = h1a + H1 * LD;              // [H1][LD]    h1 of the s' passes    (transient)
     float *w2s = h1b + H1 * LD;              // [H1][LD]    W2[:, slice]: target copy first, then the online copy
     float *red = w2s + H1 * LD;              // [4][32][LD] K-split partials / staging
-    float *h2a = red + 4 * 32 * LD;          // [32][LD]    online h2(s)[:, slice], c-major (kept)
-    float *h2b = h2a + 32 * LD;              // [32][LD]    transient
-    float *dz2 = h2b + 32 * LD;              // [32][LD]    [b][c]
-    float *dz2t = dz2 + 32 * LD;             // [32][LD]    [c][b]
-    float *qs = dz2t + 32 * LD;              // [3][32][A]  summed head outputs: online(s), target(s'), online(s')
-    float *dqs = qs + 3 * 32 * kMaxA;        // [32][A]
-    float *b3s = dqs + 32 * kMaxA;           // [2][A]      head bias online / target (read before anyone updates it)
-    float *lred = b3s + 2 * kMaxA;           // [256]
+    float *h2a = red + kRedFloats;           // [32][LD]    online h2(s)[:, slice], c-major (kept)
+    float *h2b = h2a + kTileFloats;          // [32][LD]    transient
+    float *dz2 = h2b + kTileFloats;          // [32][LD]    [b][c]
+    float *dz2t = dz2 + kTileFloats;         // [32][LD]    [c][b]
+    float *qs = dz2t + kTileFloats;          // [3][32][A]  summed head outputs: online(s), target(s'), online(s')
+    float *dqs = qs + kQsFloats;             // [32][A]
+    float *b3s = dqs + kDqsFloats;           // [2][A]      head bias online / target (read before anyone updates it)
+    float *lred = red + kRedToLred;          // [256]
     float *w3s = lred + kThreads;            // [2][32][A]  owned rows of the head: online / target (pre-update)
 
     // ---- inputs -> LDS (zero padded to 32 rows / even K)
@@ -352,7 +371,9 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
         const int b = e >> 5, c = e & 31;
         float s = 0.f;
         for (int a = 0; a < A; ++a) s += dqs[b * kMaxA + a] * w3s[c * kMaxA + a];
-        const float v = h2a[c * LD + b] > 0.f ? s : 0.f;
+        // a product, like every other launch's relu backward and the oracle's dy * (y > 0): a NaN or inf gradient at
+        // an inactive unit is NaN (a select wrote 0 and kept that unit's weights finite)
+        const float v = s * rlx::act_deriv_out(h2a[c * LD + b], RLX_ACT_RELU);
         dz2[b * LD + c] = v;
         dz2t[c * LD + b] = v;
     }
@@ -412,11 +433,13 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
     RLX_STAMP();                                                   // 7: barrier 2 passed
 
     const int S1 = H1 / G, i0 = g * S1;               // this workgroup's slice of the first layer
-    float *dz1 = red;                                  // [32][S1]
+    // [32][S1], S1 <= kMaxH1: past the end of `red` for S1 > 132, into blocks that are dead by now and short of lred
+    // (the static_assert at kRedToLred)
+    float *dz1 = red;
     for (int e = tid; e < 32 * S1; e += kThreads) {
         const int b = e / S1, i = e - b * S1;
         const float s = sum_strided(p.ws_dh1 + (size_t)b * H1 + i0 + i, (size_t)32 * H1, G, 0.f);
-        dz1[b * S1 + i] = h1a[(i0 + i) * LD + b] > 0.f ? s : 0.f;
+        dz1[b * S1 + i] = s * rlx::act_deriv_out(h1a[(i0 + i) * LD + b], RLX_ACT_RELU);
     }
     __syncthreads();
     for (int e = tid; e < (D0 + 1) * S1; e += kThreads) {      // rows 0..D0-1: dW1, row D0: db1
@@ -463,8 +486,7 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
 
 inline size_t lds_floats(int D0, int H1) {
     const int D0p = (D0 + 1) & ~1;
-    return (size_t)2 * D0p * LD + (size_t)3 * H1 * LD + 4 * 32 * LD + 4 * 32 * LD + 3 * 32 * kMaxA + 32 * kMaxA +
-           2 * kMaxA + kThreads + 2 * 32 * kMaxA;
+    return (size_t)2 * D0p * LD + (size_t)3 * H1 * LD + kFixedFloats;
 }
 
 
@@ -652,7 +674,7 @@ int rlx_mlp_dqn_supported(int batch, int obs_dim, int h1, int h2, int n_actions)
     if (h1 % 32 || h2 % 32 || h1 < 32 || h2 < 32) return 0;
     const int G = h2 / 32;
     if (G > 64 || h1 % G || (h1 / 4) % 2) return 0;
-    return lds_floats(obs_dim, h1) * sizeof(float) <= 160 * 1024 ? 1 : 0;
+    return lds_floats(obs_dim, h1) * sizeof(float) <= (size_t)kLdsLimitBytes ? 1 : 0;
 }
 
 int rlx_mlp_dqn_workspace_floats(int h1, int h2, int n_actions, long long *floats_host) {
