@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(kThreads) a3c_window_loss_kernel(const A3cArgs
         __syncthreads();
     }
     // the two heads, one row per thread: thread t owns rows t, t + 256, ... (it wrote their targets itself) and adds
-    // their terms in row order; the workgroup sums the 256 partials in a fixed tree
+    // their terms in row order
     const float fT = (float)T;
     float val = 0.f, pol = 0.f, ent = 0.f;
     for (int b = t; b < a.rows; b += kThreads) {
@@ -122,18 +122,7 @@ __global__ void __launch_bounds__(kThreads) a3c_window_loss_kernel(const A3cArgs
         }
         rlx::pg_row_loss_grad(a.logits + (size_t)b * a.ld, A, act, adv, a.beta, fT, d, pol, ent);
     }
-    val_s[t] = val;
-    pol_s[t] = pol;
-    ent_s[t] = ent;
-    __syncthreads();
-    for (int s = kThreads >> 1; s > 0; s >>= 1) {
-        if (t < s) {
-            val_s[t] += val_s[t + s];
-            pol_s[t] += pol_s[t + s];
-            ent_s[t] += ent_s[t + s];
-        }
-        __syncthreads();
-    }
+    rlx::tree_sum(kThreads, val_s, val, pol_s, pol, ent_s, ent);
     if (t == 0) {
         const float value_loss = val_s[0] / fT, policy_loss = -(pol_s[0] / fT), mean_h = ent_s[0] / fT;
         a.scalars[0] = value_loss + (policy_loss - a.beta * mean_h);

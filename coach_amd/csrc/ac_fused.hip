@@ -116,8 +116,7 @@ __device__ __forceinline__ void head_partial(const float *hs, int hp, const floa
         const int r = o / NO, j = o - r * NO;
         float sum = 0.f;
         for (int k = n_lo + lane; k < n_hi; k += 64) sum = fmaf(hs[r * hp + (k - n_lo)], W3[(size_t)k * NO + j], sum);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        sum = rlx::wave_sum(sum);
         if (lane == 0 && row0 + r < B) out[(long long)(row0 + r) * ld + j] = sum;
     }
 }
@@ -592,8 +591,7 @@ __global__ void __launch_bounds__(kDwThreads) mlp_dw_adam_kernel(const DwArgs a)
     for (int r = 0; r < 16; ++r)
         if (ok[r]) ss += acc[r] * acc[r];
     if (bias_lane) ss += bsum * bsum;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) ss += __shfl_xor(ss, d, 64);
+    ss = rlx::wave_sum(ss);
     if (lane == 0) ss_s[wave] = ss;
     __syncthreads();
     if (tid == 0) {
@@ -644,8 +642,7 @@ __global__ void __launch_bounds__(kDwThreads) mlp_dw_adam_kernel(const DwArgs a)
         float s = 0.f;
         for (int t = nn.tile_lo + lane; t < nn.tile_hi; t += 64)
             s += __hip_atomic_load(&a.norm_part[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+        s = rlx::wave_sum(s);
         if (lane == 0) {
             if (nn.norm_out) nn.norm_out[0] = sqrtf(s);
             const float p1 = nn.state[0], p2 = nn.state[1];
@@ -658,8 +655,7 @@ __global__ void __launch_bounds__(kDwThreads) mlp_dw_adam_kernel(const DwArgs a)
         for (int s = 0; s < a.loss_streams; ++s) {
             float v = 0.f;
             for (int i = lane; i < a.loss_parts; i += 64) v += a.loss_part[(size_t)s * a.loss_parts + i];
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+            v = rlx::wave_sum(v);
             v = a.loss_scale * v / (float)a.B;
             total += v;
             if (lane == 0) a.loss_out[s] = v;
@@ -668,8 +664,7 @@ __global__ void __launch_bounds__(kDwThreads) mlp_dw_adam_kernel(const DwArgs a)
         if (a.loss2_out) {
             float v = 0.f;
             for (int i = lane; i < a.loss2_parts; i += 64) v += a.loss2_part[i];
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+            v = rlx::wave_sum(v);
             if (lane == 0) a.loss2_out[0] = v / (float)a.B;
         }
     }

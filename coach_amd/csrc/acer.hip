@@ -119,8 +119,7 @@ __global__ void __launch_bounds__(kThreads) acer_window_loss_kernel(const AcerAr
             __syncthreads();
         }
     }
-    // phase 3, the two heads, one row per thread again (it wrote the row's values itself); the workgroup sums the 256
-    // partials of every scalar in a fixed tree
+    // phase 3, the two heads, one row per thread again (it wrote the row's values itself)
     const float fT = (float)T;
     float qsum = 0.f;
     rlx::AcerRowSums s{0.f, 0.f, 0.f, 0.f};
@@ -149,17 +148,7 @@ __global__ void __launch_bounds__(kThreads) acer_window_loss_kernel(const AcerAr
             a.avg_p + (size_t)b * a.ld_ap, a.rho + (size_t)b * a.ld_rho, a.rho_i[b], qret, V, a.c, a.delta, a.beta,
             trust, fT, dz, s);
     }
-    sum_s[0][t] = qsum;
-    sum_s[1][t] = s.prob;
-    sum_s[2][t] = s.bias;
-    sum_s[3][t] = s.kl;
-    sum_s[4][t] = s.ent;
-    __syncthreads();
-    for (int d = kThreads >> 1; d > 0; d >>= 1) {
-        if (t < d)
-            for (int n = 0; n < 5; ++n) sum_s[n][t] += sum_s[n][t + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kThreads, sum_s[0], qsum, sum_s[1], s.prob, sum_s[2], s.bias, sum_s[3], s.kl, sum_s[4], s.ent);
     if (t == 0) {
         const float q_loss = sum_s[0][0] / fT, prob_loss = -(sum_s[1][0] / fT), bias_loss = -(sum_s[2][0] / fT);
         const float policy_loss = prob_loss + bias_loss, mean_h = sum_s[4][0] / fT;

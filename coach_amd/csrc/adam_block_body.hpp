@@ -7,7 +7,7 @@
 // bit-identical.  The update's products and sums must not be contracted: a translation unit that is not compiled with
 // -ffp-contract=off includes this header under `#pragma clang fp contract(off)`.
 #pragma once
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace rlx_adam {
 
@@ -68,12 +68,7 @@ __device__ __forceinline__ float block_step(float *__restrict__ w, const float *
             for (int k = 0; k < 4; ++k) ss += gp[k] * gp[k];
         }
     if (has_tail) ss += gt * gt;
-    red[threadIdx.x] = ss;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kBlock, red, ss);
     float old = 0.f;
     if (threadIdx.x == 0) {
         if (EXCHANGE) old = __hip_atomic_exchange(&sumsq_part[vb], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

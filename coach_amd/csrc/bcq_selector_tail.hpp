@@ -4,7 +4,7 @@
 // tests/bcq_ref.py (uniforms) is the restatement.
 #pragma once
 #include "philox.hpp"
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace rlx {
 
@@ -28,14 +28,8 @@ __device__ __forceinline__ void bcq_zero_row_draws(float *s, int b, int A, uint3
 // red: kBcqSelectorMaxBatch ints of LDS.
 __device__ __forceinline__ void bcq_zero_row_count(int zero, int *zero_rows, int *red) {
     if (!zero_rows) return;
-    const int b = threadIdx.x;
-    red[b] = zero;
-    __syncthreads();
-    for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-        if (b < d) red[b] += red[b + d];
-        __syncthreads();
-    }
-    if (b == 0) zero_rows[0] = red[0];
+    tree_sum(blockDim.x, red, zero);
+    if (threadIdx.x == 0) zero_rows[0] = red[0];
 }
 
 // The workgroup of a selector launch: the smallest power of two >= batch, at least one wave.

@@ -41,9 +41,7 @@ __device__ __forceinline__ void dense_small_fwd_row(const SmallDense &p, int row
     }
 #pragma unroll
     for (int n = 0; n < NN; ++n) {
-        float v = acc[n];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const float v = rlx::wave_sum(acc[n]);
         if (lane == 0) part[wave][n] = v;
     }
     __syncthreads();

@@ -3,7 +3,7 @@
 // choice of the acting kernels; and on the host the size checks of the loss entry points.  Everything a head does with
 // its atoms (means / softmax expectations, targets / projection, the loss itself) stays in its own file.
 #pragma once
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace rlx {
 
@@ -29,10 +29,10 @@ __device__ __forceinline__ bool taken_action_valid(int act, int n_actions, int t
 
 // The batch sum of a loss kernel with one workgroup of THREADS threads per row (batch <= THREADS): thread 0 publishes
 // its row's partial (row_partial is read in thread 0 only) and draws a ticket; the workgroup that draws the last one
-// sums row_partials[0 .. batch) in a fixed tree, so the sum does not depend on the order of arrival.  Returns true in
-// every thread of that workgroup, with the sum in red[0], and false in every thread of the others; the ticket is left
-// at zero for the next launch.  Every thread of the workgroup must call it (barriers inside); red is THREADS floats of
-// LDS and `last` one shared flag.
+// sums row_partials[0 .. batch), zero-padded to THREADS, by tree_sum, so the sum does not depend on the order of
+// arrival.  Returns true in every thread of that workgroup, with the sum in red[0], and false in every thread of the
+// others; the ticket is left at zero for the next launch.  Every thread of the workgroup must call it (barriers
+// inside) with t = threadIdx.x; red is THREADS floats of LDS and `last` one shared flag.
 // This is the only hand-off between workgroups in these kernels: every access to row_partials and ticket is an
 // agent-scope atomic, and their orders (and the fence) are part of the protocol, not a style.
 template <int THREADS>
@@ -47,12 +47,8 @@ __device__ __forceinline__ bool ticketed_batch_sum(float row_partial, int b, int
     __syncthreads();
     if (!*last) return false;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    red[t] = t < batch ? __hip_atomic_load(&row_partials[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    __syncthreads();
-    for (int d = THREADS >> 1; d > 0; d >>= 1) {
-        if (t < d) red[t] += red[t + d];
-        __syncthreads();
-    }
+    tree_sum(THREADS, red,
+             t < batch ? __hip_atomic_load(&row_partials[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f);
     return true;
 }
 

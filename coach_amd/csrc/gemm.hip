@@ -1975,11 +1975,12 @@ __device__ __forceinline__ void ppo_heads_tail_body(const PpoTailDev &a, int kbl
                 l_ent = a.row_terms[(size_t)b * 4 + 2];
                 l_kl = a.row_terms[(size_t)b * 4 + 3];
             }
-            block_sum3_first(l_sur, l_ent, l_kl, red, a.red_threads);
-            if (threadIdx.x == 0) ppo_discrete_scalars(l_sur, l_ent, l_kl, a.beta, B, a.scalars);
+            rlx::tree_sum(a.red_threads, red[0], l_sur, red[1], l_ent, red[2], l_kl);
+            if (threadIdx.x == 0) ppo_discrete_scalars(red[0][0], red[1][0], red[2][0], a.beta, B, a.scalars);
+            __syncthreads();       // nothing reuses red: kept so that the launch has the barriers it had
         } else {
             const float local = b < B ? a.row_terms[(size_t)b * 4] : 0.f;
-            const float s = block_sum_first(local, red[0], a.red_threads);
+            const float s = block_sum(local, red[0], a.red_threads);
             if (threadIdx.x == 0) a.scalars[4] = s / (float)B;
         }
     }

@@ -84,16 +84,7 @@ __global__ void __launch_bounds__(kMaxRows) classification_head_loss_kernel(cons
         }
         if (a.row_loss) a.row_loss[b] = loss;
     }
-    loss_s[b] = loss;
-    hit_s[b] = hit;
-    __syncthreads();
-    for (int t = blockDim.x >> 1; t > 0; t >>= 1) {
-        if (b < t) {
-            loss_s[b] += loss_s[b + t];
-            hit_s[b] += hit_s[b + t];
-        }
-        __syncthreads();
-    }
+    rlx::tree_sum(blockDim.x, loss_s, loss, hit_s, hit);
     if (b == 0) {
         a.scalars[0] = loss_s[0];
         a.scalars[1] = (float)hit_s[0];

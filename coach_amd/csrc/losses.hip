@@ -42,7 +42,7 @@ regression_loss_body(const float *__restrict__ out, const float *__restrict__ ta
         }
         local += w * row;
     }
-    const float s = block_sum(local, red);
+    const float s = block_sum(local, red, blockDim.x);
     if (threadIdx.x == 0 && scalars) scalars[0] = s / (float)batch;
 }
 
@@ -82,9 +82,9 @@ ppo_discrete_loss_body(const float *__restrict__ logits, long long ld, const int
         l_ent += t.ent;
         l_kl += t.kl;
     }
-    const float sur = block_sum(l_sur, red);
-    const float ent = block_sum(l_ent, red);
-    const float kl = block_sum(l_kl, red);
+    const float sur = block_sum(l_sur, red, blockDim.x);
+    const float ent = block_sum(l_ent, red, blockDim.x);
+    const float kl = block_sum(l_kl, red, blockDim.x);
     if (threadIdx.x == 0 && scalars) ppo_discrete_scalars(sur, ent, kl, beta, batch, scalars);
 }
 
@@ -229,8 +229,8 @@ ppo_continuous_loss_kernel(const float *__restrict__ mean, long long ld, const f
             }
         }
     }
-    const float sur = block_sum(l_sur, red);
-    const float kls = block_sum(l_kl, red);
+    const float sur = block_sum(l_sur, red, blockDim.x);
+    const float kls = block_sum(l_kl, red, blockDim.x);
     if (dlog_std) {
         // d loss / d log_std[a] = sum_b g_logp_b * (d^2 / sd^3 - 1 / sd) * exp(log_std) - beta * dH/d log_std:
         // one fixed-order workgroup reduction per action dimension (reproducible, no atomics)
@@ -242,7 +242,7 @@ ppo_continuous_loss_kernel(const float *__restrict__ mean, long long ld, const f
                 const float d = actions[(size_t)b * A + a] - mean[(size_t)b * ld + a];
                 part = my_glp * (d * d / (sd * sd * sd) - 1.f / sd) * e;
             }
-            const float tot = block_sum(part, red);
+            const float tot = block_sum(part, red, blockDim.x);
             if (threadIdx.x == 0) dlog_std[a] = tot - grad_scale * beta * e / sd;
         }
     }

@@ -1,54 +1,19 @@
 // Per-sample arithmetic of the head losses (see losses.hip), shared with the fused Clipped-PPO heads kernel
 // (ppo_heads_fused.hip): one definition, one rounding.
 #pragma once
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace rlx_losses {
 
 constexpr int kMaxBlock = 1024;
 
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int d = nt >> 1; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
-    float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// block_sum over the first nt threads of a LARGER block (the tree of a block of nt threads)
-__device__ __forceinline__ float block_sum_first(float v, float *red, int nt) {
-    const int tid = threadIdx.x;
-    if (tid < nt) red[tid] = v;
-    __syncthreads();
-    for (int d = nt >> 1; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
+// rlx::tree_sum of the first nt threads' v, returned in every thread, with red free for the next sum.  red holds
+// blockDim.x floats (every thread stores its v), also where nt is smaller.
+__device__ __forceinline__ float block_sum(float v, float *red, int nt) {
+    rlx::tree_sum(nt, red, v);
     const float r = red[0];
     __syncthreads();
     return r;
-}
-
-// three such sums through ONE tree (each component goes through exactly the additions of block_sum_first)
-__device__ __forceinline__ void block_sum3_first(float &x, float &y, float &z, float (*red)[256], int nt) {
-    const int tid = threadIdx.x;
-    if (tid < nt) { red[0][tid] = x; red[1][tid] = y; red[2][tid] = z; }
-    __syncthreads();
-    for (int d = nt >> 1; d > 0; d >>= 1) {
-        if (tid < d) {
-            red[0][tid] += red[0][tid + d];
-            red[1][tid] += red[1][tid + d];
-            red[2][tid] += red[2][tid + d];
-        }
-        __syncthreads();
-    }
-    x = red[0][0]; y = red[1][0]; z = red[2][0];
-    __syncthreads();
 }
 
 // scalars[0..3] of the discrete Clipped-PPO head from the batch sums (ppo_head.py:62-96)

@@ -350,12 +350,7 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
             }
         }
     }
-    lred[tid] = term;
-    __syncthreads();
-    for (int d = 32; d > 0; d >>= 1) {               // the 64-entry tree of dqn_head_loss_kernel at B <= 32
-        if (tid < d) lred[tid] += lred[tid + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(64, lred, term);                   // the 64-entry tree of dqn_head_loss_kernel at B <= 32
     if (g == 0 && tid == 0 && p.loss) p.loss[0] = lred[0] / (float)B;
     RLX_STAMP();                                                   // 5: loss / dQ
 
@@ -457,12 +452,7 @@ __global__ void __launch_bounds__(kThreads) mlp_dqn_update_kernel(const MlpDqnDe
     RLX_STAMP();                                                   // 8: first layer's gradient + Adam
     // ---- tf.global_norm partial; the last workgroup to take a ticket finishes norm + Adam state and re-arms
     __syncthreads();
-    lred[tid] = ad.ss;
-    __syncthreads();
-    for (int d = kThreads >> 1; d > 0; d >>= 1) {
-        if (tid < d) lred[tid] += lred[tid + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kThreads, lred, ad.ss);
     if (tid == 0) {
         p.ws_norm[g] = lred[0];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -595,8 +585,7 @@ __global__ void __launch_bounds__(1024) mlp_q_act_kernel(const MlpActDev p) {
         const int e = o / p.A, a = o - e * p.A;
         float part = 0.f;
         for (int k = lane; k < p.H2; k += 64) part = fmaf(h2s[e * p.H2 + k], W3[(size_t)k * p.A + a], part);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
+        part = rlx::wave_sum(part);
         if (lane == 0) {
             const float v = part + b3[a];
             qs[o] = v;

@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(kThreads) nstep_q_window_loss_kernel(const NSt
         }
     }
     // the head, one row per thread: thread t owns rows t, t + 256, ... (it wrote their targets itself) and adds their
-    // terms in row order; the workgroup sums the 256 partials in a fixed tree
+    // terms in row order
     float sum = 0.f;
     for (int b = t; b < T; b += kThreads) {
         const float *q = a.q_online + (size_t)b * a.ld_q;
@@ -103,12 +103,7 @@ __global__ void __launch_bounds__(kThreads) nstep_q_window_loss_kernel(const NSt
         d[act] = rlx_losses::regression_grad(1.f, 1.f, g, T);
         if (td) td[act] = tgt;
     }
-    sum_s[t] = sum;
-    __syncthreads();
-    for (int s = kThreads >> 1; s > 0; s >>= 1) {
-        if (t < s) sum_s[t] += sum_s[t + s];
-        __syncthreads();
-    }
+    rlx::tree_sum(kThreads, sum_s, sum);
     if (t == 0) a.scalars[0] = sum_s[0] / (float)T;
 }
 

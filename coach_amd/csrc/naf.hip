@@ -13,7 +13,7 @@
 //
 // Mapping: one wave per batch row, four rows per 256-thread workgroup; lane c owns column c of L (contiguous in
 // l_vector), d_c, mu_c and y_c.  The row's l_vector (at most 528 floats), d, y and the diagonal live in LDS.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(kNafThreads) naf_head_loss_kernel(const NafLos
         for (int r = ln + 1; r < A; ++r) dlr[r - ln] = tc * s.d[r];
     }
     // The batch sum: wave 0 publishes its workgroup's row terms and draws a ticket; the workgroup that draws the last
-    // one sums partials[0 .. batch) in a fixed tree (rlx::ticketed_batch_sum's protocol with several rows per
+    // one sums partials[0 .. batch) by rlx::tree_sum (rlx::ticketed_batch_sum's protocol with several rows per
     // workgroup: every access to partials and ticket is an agent-scope atomic, the release is wave 0's).
     if (t < kNafRows && blockIdx.x * kNafRows + t < B)
         __hip_atomic_store(&a.partials[blockIdx.x * kNafRows + t], term_s[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -152,12 +152,8 @@ __global__ void __launch_bounds__(kNafThreads) naf_head_loss_kernel(const NafLos
     __syncthreads();
     if (!last_s) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    red[t] = t < B ? __hip_atomic_load(&a.partials[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    __syncthreads();
-    for (int d = kNafMaxBatch >> 1; d > 0; d >>= 1) {
-        if (t < d) red[t] += red[t + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kNafMaxBatch, red,
+                  t < B ? __hip_atomic_load(&a.partials[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f);
     if (t == 0) a.loss[0] = red[0] / (float)B;
 }
 

@@ -24,7 +24,7 @@
 // the product of the importance ratios rides in the same tree.  A second launch of one workgroup sums the three per-row
 // columns and the three per-episode columns in a fixed-shape fp64 tree and writes the five estimates.  No floating-point
 // atomics anywhere: the same bits on every call.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
@@ -173,12 +173,7 @@ __device__ __forceinline__ double block_sum(const double *__restrict__ x, long l
     const int tid = threadIdx.x;
     double s = 0.0;
     for (long long i = tid; i < n; i += kSumThreads) s = s + x[i];
-    red[tid] = s;
-    __syncthreads();
-    for (int d = kSumThreads >> 1; d > 0; d >>= 1) {
-        if (tid < d) red[tid] = red[tid] + red[tid + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kSumThreads, red, s);
     const double r = red[0];
     __syncthreads();
     return r;

@@ -94,12 +94,7 @@ __global__ void adam_tf1_kernel(float *__restrict__ w, const float *__restrict__
         w[i] -= (m[i] * alpha) / (sqrtf(v[i]) + eps);
     }
     if (NORM) {
-        red[threadIdx.x] = ss;
-        __syncthreads();
-        for (int d = kBlock >> 1; d > 0; d >>= 1) {
-            if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-            __syncthreads();
-        }
+        rlx::tree_sum(kBlock, red, ss);
         if (threadIdx.x == 0) sumsq_part[blockIdx.x] = red[0];
     }
 }
@@ -157,12 +152,7 @@ adam_step_kernel(float *__restrict__ w, const float *__restrict__ g, float *__re
         if (MIX) target[i] = rate * w[i] + one_minus_rate * target[i];
     }
     if (NORM) {
-        red[threadIdx.x] = ss;
-        __syncthreads();
-        for (int d = kBlock >> 1; d > 0; d >>= 1) {
-            if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-            __syncthreads();
-        }
+        rlx::tree_sum(kBlock, red, ss);
         if (threadIdx.x == 0) {
             // with the ticket: an agent-scope store (written through to the memory side, past this XCD's L2) ...
             if (TICKET) __hip_atomic_store(&sumsq_part[blockIdx.x], red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -193,12 +183,7 @@ adam_step_kernel(float *__restrict__ w, const float *__restrict__ g, float *__re
     float s = 0.f;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += kBlock)
         s += __hip_atomic_load(&sumsq_part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kBlock, red, s);
     if (threadIdx.x == 0) {
         norm_out[0] = sqrtf(red[0]);
         state[0] = b1p * beta1;
@@ -243,12 +228,7 @@ __device__ __forceinline__ void adam_norm_finish(const float old, unsigned int *
         if ((int)threadIdx.x + k * kBlock < nparts) s += part[k];
     for (int i = threadIdx.x + 4 * kBlock; i < nparts; i += kBlock)
         s += __hip_atomic_load(&sumsq_part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kBlock, red, s);
     if (threadIdx.x == 0) {
         norm_out[0] = sqrtf(red[0]);
         state[0] = b1p * beta1;
@@ -308,12 +288,7 @@ __global__ void adam_finish_norm_kernel(float *state, float beta1, float beta2,
     __shared__ float red[kBlock];
     float s = 0.f;
     for (int i = threadIdx.x; i < nparts; i += kBlock) s += part[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kBlock, red, s);
     if (threadIdx.x == 0) {
         norm_out[0] = sqrtf(red[0]);
         state[0] *= beta1;
@@ -348,24 +323,14 @@ __global__ void sumsq_partial_kernel(const float *__restrict__ x, long long n, f
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
         s += x[i] * x[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kBlock, red, s);
     if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 __global__ void sumsq_final_kernel(const float *__restrict__ part, int nparts, float *__restrict__ out) {
     __shared__ float red[kBlock];
     float s = 0.f;
     for (int i = threadIdx.x; i < nparts; i += kBlock) s += part[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = kBlock >> 1; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(kBlock, red, s);
     if (threadIdx.x == 0) out[0] = sqrtf(red[0]);
 }
 

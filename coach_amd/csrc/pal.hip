@@ -16,7 +16,7 @@
 // One workgroup (batch <= 1024), one row per thread, the batch mean by the fixed-order LDS tree of dqn_head_loss_kernel
 // over blockDim leaves.  Latency-bound, a few hundred bytes: the point is that no Q value leaves the device between
 // the network passes.
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 
 namespace {
 
@@ -83,12 +83,7 @@ __global__ void __launch_bounds__(1024) mixed_target_head_loss_kernel(const Mixe
             }
         }
     }
-    red[i] = term;
-    __syncthreads();
-    for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-        if (i < d) red[i] += red[i + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(blockDim.x, red, term);
     if (i == 0 && a.loss) a.loss[0] = red[0] / (float)a.batch;
 }
 

@@ -165,8 +165,8 @@ struct HeadLossArgs {
     int *status;
 };
 
-// ONE workgroup: thread t owns rows t, t + 256, ...; a thread adds its rows' terms in row order and the workgroup sums
-// the 256 partials in a fixed tree.  Rows [T, rows) are padding: zero gradient, no term.
+// ONE workgroup: thread t owns rows t, t + 256, ...; a thread adds its rows' terms in row order.  Rows [T, rows) are
+// padding: zero gradient, no term.
 __global__ void __launch_bounds__(kPgThreads) pg_head_loss_kernel(const HeadLossArgs a) {
     __shared__ float pol_s[kPgThreads], ent_s[kPgThreads];
     const int t = threadIdx.x, A = a.A;
@@ -182,16 +182,7 @@ __global__ void __launch_bounds__(kPgThreads) pg_head_loss_kernel(const HeadLoss
         }
         rlx::pg_row_loss_grad(a.logits + (size_t)b * a.ld, A, act, a.advantages[b], a.beta, fT, d, pol, ent);
     }
-    pol_s[t] = pol;
-    ent_s[t] = ent;
-    __syncthreads();
-    for (int s = kPgThreads >> 1; s > 0; s >>= 1) {
-        if (t < s) {
-            pol_s[t] += pol_s[t + s];
-            ent_s[t] += ent_s[t + s];
-        }
-        __syncthreads();
-    }
+    rlx::tree_sum(kPgThreads, pol_s, pol, ent_s, ent);
     if (t == 0) {
         const float mean_h = ent_s[0] / fT;
         a.scalars[0] = -(pol_s[0] / fT) - a.beta * mean_h;

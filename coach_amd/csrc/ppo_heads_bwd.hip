@@ -61,8 +61,9 @@ __global__ void __launch_bounds__(256) ppo_heads_loss_bwd_kernel(const PpoHeadsB
                 }
             }
             if (writer) {
-                block_sum3_first(l_sur, l_ent, l_kl, red, a.red_threads);
-                if (threadIdx.x == 0) ppo_discrete_scalars(l_sur, l_ent, l_kl, a.beta, B, a.scalars);
+                rlx::tree_sum(a.red_threads, red[0], l_sur, red[1], l_ent, red[2], l_kl);
+                if (threadIdx.x == 0) ppo_discrete_scalars(red[0][0], red[1][0], red[2][0], a.beta, B, a.scalars);
+                __syncthreads();       // nothing reuses red: kept so that the launch has the barriers it had
             }
         } else {
             float local = 0.f;
@@ -75,7 +76,7 @@ __global__ void __launch_bounds__(256) ppo_heads_loss_bwd_kernel(const PpoHeadsB
                 local = w * l;
             }
             if (writer) {
-                const float s = block_sum_first(local, red[0], a.red_threads);
+                const float s = block_sum(local, red[0], a.red_threads);
                 if (threadIdx.x == 0) a.scalars[4] = s / (float)B;
             }
         }

@@ -10,7 +10,7 @@
 //
 // which is why this head is a launch of its own: one workgroup, one row per thread (batch <= 1024), in three phases.
 //   A  per row: log pi(a), log pi_old(a), ratio, entropy, KL(old || new); the optional likelihood_ratio output.
-//   B  the batch sums through the fixed LDS tree (rlx_losses::block_sum, no atomics), KL mean, the factor c.
+//   B  the batch sums through the fixed LDS tree (rlx::tree_sum, no atomics), KL mean, the factor c.
 //   C  the gradient rows: (-adv ratio / B) dlogp/dz + (c / B) dKL_b/dz - (beta / B) dH_b/dz, times grad_scale.
 // kl_coefficient is a DEVICE scalar (ppo_head.py:42-45 keeps it in a tf.Variable): a captured graph survives
 // rlx_ppo_kl_coefficient_update changing it between training phases.
@@ -109,9 +109,9 @@ ppo_kl_discrete_kernel(const float *__restrict__ logits, long long ld, const int
         }
     }
     // ---- B
-    const float sur = block_sum(l_sur, red);
-    const float ent = block_sum(l_ent, red);
-    const float kl = block_sum(l_kl, red);
+    const float sur = block_sum(l_sur, red, blockDim.x);
+    const float ent = block_sum(l_ent, red, blockDim.x);
+    const float kl = block_sum(l_kl, red, blockDim.x);
     const float inv = 1.f / (float)batch;
     const float s_sur = -sur * inv, s_ent = ent * inv, s_kl = kl * inv;       // ppo_discrete_scalars' expressions
     const KlPenalty pen = kl_penalty(s_sur, beta * ent * inv, s_kl, use_kl, kl_coefficient, kl_cutoff, high);
@@ -176,8 +176,8 @@ ppo_kl_continuous_kernel(const float *__restrict__ mean, long long ld, const flo
         if (ratio_out) ratio_out[b] = ratio;
     }
     // ---- B
-    const float sur = block_sum(l_sur, red);
-    const float kls = block_sum(l_kl, red);
+    const float sur = block_sum(l_sur, red, blockDim.x);
+    const float kls = block_sum(l_kl, red, blockDim.x);
     const float inv = 1.f / (float)batch;
     const float s_sur = -sur * inv, s_kl = kls * inv;
     const KlPenalty pen = kl_penalty(s_sur, beta * ent, s_kl, use_kl, kl_coefficient, kl_cutoff, high);
@@ -206,7 +206,7 @@ ppo_kl_continuous_kernel(const float *__restrict__ mean, long long ld, const flo
                     part = part + cb * ((1.f - (sdo * sdo + dm * dm) / (sd * sd)) * e / sd);
                 }
             }
-            const float tot = block_sum(part, red);
+            const float tot = block_sum(part, red, blockDim.x);
             if (b == 0) dlog_std[a] = grad_scale * (tot - beta * e / sd);
         }
     }

@@ -123,13 +123,8 @@ __global__ void __launch_bounds__(kQrThreads) qr_dqn_head_loss_kernel(const QrAr
     for (int c = t; c < A * N; c += kQrThreads)
         if (!valid || c / N != act) drow[c] = 0.f;
     if (t < N && valid) drow[(size_t)act * N + t] = a.grad_scale * (-(g / (float)N));
-    red[t] = term;
-    __syncthreads();
-    for (int d = kQrThreads >> 1; d > 0; d >>= 1) {
-        if (t < d) red[t] += red[t + d];
-        __syncthreads();
-    }
-    // the batch sum: the row partials, summed in a fixed tree by the workgroup that draws the last ticket
+    rlx::tree_sum(kQrThreads, red, term);
+    // the batch sum: the row partials, summed by the workgroup that draws the last ticket
     if (!rlx::ticketed_batch_sum<kQrThreads>(red[0], b, a.batch, a.row_partials, a.ticket, red, &last_s, t)) return;
     if (t == 0) a.loss[0] = red[0] / (float)N;
 }

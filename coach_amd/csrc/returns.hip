@@ -17,7 +17,7 @@
 // All arithmetic is fp64 like the reference; inputs/outputs are the fp32 arrays the network uses.
 // HBM-bound: 17 B per step (r, V, done in; advantage, value target out) — SURVEY.md §8(d).
 // Compiled with -ffp-contract=off (see Makefile).
-#include "rlx_common.hpp"
+#include "rlx_device.hpp"
 #include "episode_returns.hpp"
 #include "reward_filter.hpp"
 
@@ -144,7 +144,7 @@ reverse_scan_kernel(const float *__restrict__ rewards, const float *__restrict__
 }
 
 // (x - mean) / std  with numpy's definitions: mean = sum/n, std = sqrt(mean(|x-mean|^2)).
-// One workgroup; deterministic tree reductions in fp64.
+// One workgroup; both sums by rlx::tree_sum in fp64.
 __global__ void __launch_bounds__(1024)
 standardize_kernel(const double *__restrict__ x, long long n, float *__restrict__ out32,
                    double *__restrict__ out64, double *__restrict__ stats) {
@@ -153,12 +153,7 @@ standardize_kernel(const double *__restrict__ x, long long n, float *__restrict_
     const int tid = threadIdx.x, nt = blockDim.x;
     double s = 0.0;
     for (long long i = tid; i < n; i += nt) s += x[i];
-    red[tid] = s;
-    __syncthreads();
-    for (int d = nt >> 1; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(nt, red, s);
     if (tid == 0) mean_s = red[0] / (double)n;
     __syncthreads();
     const double mean = mean_s;
@@ -167,12 +162,7 @@ standardize_kernel(const double *__restrict__ x, long long n, float *__restrict_
         double d = x[i] - mean;
         s += d * d;
     }
-    red[tid] = s;
-    __syncthreads();
-    for (int d = nt >> 1; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(nt, red, s);
     if (tid == 0) {
         std_s = sqrt(red[0] / (double)n);
         if (stats) {

@@ -43,4 +43,51 @@ __device__ __forceinline__ void dma16(const float *gsrc, unsigned lds_dst) {
                  : "memory");
 }
 
+// ---- The two sums of the library.  Losses, gradient norms and batch statistics are pinned to references bit for bit
+// (tests/*_ref.py), so the ORDER of their additions is part of the contract: neither atomics (order of arrival) nor a
+// running sum, but the two fixed shapes below, one definition each.
+
+// The 64 lanes of a wave: the xor butterfly, distances 32, 16, .. 1.  Every lane ends up with the sum; all 64 lanes
+// must call it.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+namespace detail {
+__device__ __forceinline__ void tree_store(int) {}
+template <typename T, typename... Rest>
+__device__ __forceinline__ void tree_store(int t, T *red, T v, Rest... rest) {
+    red[t] = v;
+    tree_store(t, rest...);
+}
+__device__ __forceinline__ void tree_add(int, int) {}
+template <typename T, typename... Rest>
+__device__ __forceinline__ void tree_add(int t, int d, T *red, T, Rest... rest) {
+    red[t] += red[t + d];
+    tree_add(t, d, rest...);
+}
+}  // namespace detail
+
+// The workgroup: tree_sum(n, red, v) adds the values v of threads 0 .. n - 1 (n a power of two, at most the workgroup;
+// a constant or blockDim.x) through the LDS array red as a halving tree: level d = n/2, n/4, .. 1 adds red[t + d]
+// into red[t] for t < d, one barrier per level.  The sum is in red[0], visible to every thread, when it returns; it
+// does not depend on the launch, and float or double alike round once per level and pair (tree_sum in tests/*_ref.py
+// restates it).  tree_sum(n, red_a, a, red_b, b, ...) takes several sums through the same levels and barriers, each
+// exactly the additions of its own tree_sum.  EVERY thread of the workgroup must call it (barriers inside), and every
+// thread stores its v: red holds one entry per THREAD of the workgroup, also where n is smaller (no guard on the store:
+// every caller's array is that wide, and the store stays what the hand-written copies had).  red is the caller's to
+// reuse only after a barrier of its own.
+template <typename... RedValuePairs>
+__device__ __forceinline__ void tree_sum(int n, RedValuePairs... red_value_pairs) {
+    const int t = threadIdx.x;
+    detail::tree_store(t, red_value_pairs...);
+    __syncthreads();
+    for (int d = n >> 1; d > 0; d >>= 1) {
+        if (t < d) detail::tree_add(t, d, red_value_pairs...);
+        __syncthreads();
+    }
+}
+
 }  // namespace rlx

@@ -372,8 +372,7 @@ __device__ __forceinline__ void dense_bwdT_few_rows(const float *dys, int dp, in
         const int r = o / K, k = o - r * K;
         float s = 0.f;
         for (int n = lane; n < N; n += 64) s = fmaf(dys[r * dp + n], W[(size_t)k * ldw + n], s);
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+        s = rlx::wave_sum(s);
         if (lane == 0) dxs[r * xp + k] = scale * s;
     }
     __syncthreads();

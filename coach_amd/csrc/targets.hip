@@ -52,7 +52,7 @@ __global__ void dqn_targets_kernel(const float *__restrict__ q_next, const float
 // prioritized replay, and — because TD_targets equals Q_online except at the taken action — the
 // MSE / Huber loss and its gradient, which are non-zero only at [b, a_b]:
 //   loss = mean_b( w_b * l(y_b, Q(s_b, a_b)) ),   dQ[b][a_b] = grad_scale * w_b * l'(.) / B.
-// One workgroup (B <= 1024): per-sample work in registers, the batch mean by a fixed-order LDS tree.
+// One workgroup (B <= 1024): per-sample work in registers, the batch mean by rlx::tree_sum.
 __global__ void __launch_bounds__(1024)
 dqn_head_loss_kernel(const float *__restrict__ q, long long ld_q, const float *__restrict__ q_next,
                      const float *__restrict__ q_sel, long long ld_next, const int *__restrict__ actions,
@@ -91,12 +91,7 @@ dqn_head_loss_kernel(const float *__restrict__ q, long long ld_q, const float *_
             }
         }
     }
-    red[i] = term;
-    __syncthreads();
-    for (int d = blockDim.x >> 1; d > 0; d >>= 1) {
-        if (i < d) red[i] += red[i + d];
-        __syncthreads();
-    }
+    rlx::tree_sum(blockDim.x, red, term);
     if (i == 0 && loss) loss[0] = red[0] / (float)batch;
 }
 
@@ -158,12 +153,7 @@ __global__ void __launch_bounds__(256) dqn_head_loss_bwd_kernel(const DqnHeadBwd
             }
         }
         if (writer) {                                         // (block-uniform) the stand-alone kernel's tree over its blockDim
-            red[i] = i < a.red_threads ? term : 0.f;
-            __syncthreads();
-            for (int d = a.red_threads >> 1; d > 0; d >>= 1) {
-                if (i < d) red[i] += red[i + d];
-                __syncthreads();
-            }
+            rlx::tree_sum(a.red_threads, red, term);
             if (i == 0 && a.loss) a.loss[0] = red[0] / (float)B;
         }
         __syncthreads();

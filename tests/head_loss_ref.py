@@ -57,6 +57,36 @@ def sum_depth(batch):
     return (-(-batch // nt) - 1) + int(np.log2(nt))
 
 
+def tree_sum(terms, threads, dtype=F32):
+    """The workgroup sum of the kernels (rlx::tree_sum), operation for operation: thread t adds terms t, t + threads, ...
+    in that order to 0, then the `threads` partials fold in halves -- red[t] += red[t + d] for d = threads/2 .. 1 -- each
+    addition rounded to `dtype`."""
+    terms = np.asarray(terms, dtype=dtype).ravel()
+    red = np.zeros(threads, dtype=dtype)
+    for b0 in range(0, terms.size, threads):
+        chunk = terms[b0:b0 + threads]
+        red[:chunk.size] = red[:chunk.size] + chunk
+    d = threads // 2
+    while d:
+        red[:d] = red[:d] + red[d:2 * d]
+        d //= 2
+    return red[0]
+
+
+def running_sum(terms, dtype=F32):
+    """the same terms added one after the other: what the tree is NOT (the tree tests assert that the two differ)"""
+    return np.cumsum(np.asarray(terms, dtype=dtype).ravel(), dtype=dtype)[-1]
+
+
+def wide_terms(rng, n, dtype=F32):
+    """n values of either sign over six decades: a tree and a running sum of many of them differ in the last bits.  Three
+    values are 1, 2^p, 1 with p the significand's width: the tree adds the two ones first, (1 + 1) + 2^p = 2^p + 2
+    exactly, the running sum loses both, (1 + 2^p) + 1 = 2^p."""
+    if n == 3:
+        return np.array([1.0, 2.0 ** (np.finfo(dtype).nmant + 1), 1.0], dtype=dtype)
+    return (rng.choice([-1.0, 1.0], size=n) * 10.0 ** rng.uniform(-3, 3, size=n)).astype(dtype)
+
+
 # ------------------------------------------------------------------------------------------------ softmax
 def softmax(logits):
     """tf.nn.softmax (ppo_head.py:110): p_j = exp(z_j - max) / sum_k exp(z_k - max)   -> (p [B, n], units [B, n]).

@@ -377,3 +377,24 @@ def test_cartpole_c51_preset_reaches_the_golden_threshold(dev, tmp_path):
     from test_cartpole import _golden
     st = _golden(dev, "CartPole_C51", tmp_path)
     assert st["passed"], st
+
+
+@pytest.mark.parametrize("B", [1, 3, 200])
+def test_the_batch_sum_is_the_tree_of_the_row_partials(rlx, dev, B):
+    """the loss is head_loss_ref.tree_sum over 256 threads of the row partials the workgroups left in the workspace, bit
+    for bit (rlx::ticketed_batch_sum); logits scaled row by row over four decades spread the rows' cross entropies, and
+    over 200 rows their running sum is another number (asserted)."""
+    import torch
+    from head_loss_ref import running_sum, tree_sum
+    rng = np.random.RandomState(90 + B)
+    z, logits, logits_next, actions, rewards, go = _inputs(rng, B, 3, 11, "c51")
+    logits = (logits * (10.0 ** rng.uniform(-2, 1.3, size=(B, 1, 1)))).astype(np.float32)
+    ws = torch.zeros(256, dtype=torch.float32, device=dev)
+    ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+    loss = _launch(rlx, dev, logits, logits_next, z, actions, rewards, go, 0.99, ws, ticket)["loss"]
+    rows = ws.cpu().numpy()
+    assert not rows[B:].any()
+    tree, running = tree_sum(rows, 256), running_sum(rows[:B])
+    print("loss %r tree %r running %r" % (loss, tree, running))
+    assert B <= 3 or tree.tobytes() != running.tobytes()
+    assert loss.tobytes() == tree.tobytes()

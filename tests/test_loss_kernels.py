@@ -507,3 +507,33 @@ def test_ac_critic_losses_keeps_a_nan_target(rlx, dev, nonzero):
     _same_bits(y_dev[[30, 31]], np.array([clip[1], clip[0]], dtype=F32), "infinite targets are clipped")
     assert np.array_equal(np.isnan(dq_dev), np.broadcast_to(isnan, (T, B)))
     assert np.isnan(_h(loss)).all()
+
+
+# ------------------------------------------------------------------------------------------------ the batch sum's order
+TREE_BATCHES = [1, 3, 1025]       # one row; fewer rows than a wave, not a power of two; the 1024-thread cap plus one
+
+
+def _tree_case(B):
+    """MSE rows (out - 0)^2 of D = 1 over twelve decades: terms, their tree and their running sum"""
+    out = R.wide_terms(np.random.RandomState(700 + B), B).reshape(B, 1)
+    if B == 3:
+        out = np.array([[1.0], [4096.0], [1.0]], dtype=F32)           # squares 1, 2^24, 1: wide_terms' three values
+    terms = (out * out).astype(F32)                                   # e = out - 0 exact, l = e * e one rounding
+    return out, R.tree_sum(terms, R.block_for(B)), R.running_sum(terms)
+
+
+@pytest.mark.parametrize("B", TREE_BATCHES)
+def test_the_chosen_rows_tell_the_tree_from_a_running_sum(B):
+    _, tree, running = _tree_case(B)
+    assert B == 1 or tree.tobytes() != running.tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", TREE_BATCHES)
+def test_regression_loss_sums_the_batch_in_the_tree(rlx, dev, B):
+    """the loss scalar is head_loss_ref.tree_sum of the rows' terms over block_for(B) threads, divided by B, bit for bit
+    (rows whose running sum differs from the tree: the test above)"""
+    out, tree, _ = _tree_case(B)
+    _, l = _run_regression(rlx, dev, out, np.zeros_like(out), None, B, 1, "mse", 1.0, 1.0, 0, want_grad=False)
+    print("loss %r tree / B %r" % (l[0], tree / F32(B)))
+    _same_bits(l, [tree / F32(B)], "regression loss, B = %d" % B)

@@ -278,3 +278,32 @@ def test_behaviour_probabilities(rlx, dev, A, n):
     forced = _behaviour(rlx, dev, q, u, 0.0, True, T)
     assert (forced.view(np.uint32) == uniform.view(np.uint32)).all()
     assert ulps(pi, R.softmax32(q, T)) <= PI_ULP
+
+
+SUM_THREADS = 1024                # kSumThreads of csrc/ope.hip: the one workgroup of the estimates' sums
+
+
+def _tree_case(n):
+    """n rows in episodes of 1 or 2 steps, rewards over six decades (so are the IPS / DM / DR columns)"""
+    from head_loss_ref import wide_terms
+    lengths = [2] * (n // 2) + [1] * (n % 2)
+    c = make(lengths, 3, seed=60 + n)
+    c["rewards"] = wide_terms(np.random.RandomState(60 + n), n)
+    c["reward_model"] = (c["reward_model"] * np.abs(c["rewards"])[:, None]).astype(np.float32)
+    return c
+
+
+@pytest.mark.parametrize("n", [1, 3, SUM_THREADS + 1])
+def test_the_estimates_sum_their_columns_in_the_tree(rlx, dev, n):
+    """IPS, DM and DR are head_loss_ref.tree_sum (fp64, 1024 threads) of the row columns the launch itself wrote, divided
+    by n, bit for bit; over 1025 rows the running sum of the same column gives another IPS (asserted)."""
+    from head_loss_ref import running_sum, tree_sum
+    c = _tree_case(n)
+    _, cols, eps, out, status = device_run(rlx, dev, c)
+    assert status == 0
+    fn, E = np.float64(n), np.float64(eps.shape[1])
+    ips, dm, dr = (tree_sum(cols[k], SUM_THREADS, np.float64) for k in ("ips", "dm", "dr"))
+    want = np.array([ips / fn, dm / fn, dr / fn + dm / fn, tree_sum(eps[0], SUM_THREADS, np.float64) / E])
+    print("device %r\ntree   %r\nrunning IPS %r" % (out[:4], want, running_sum(cols["ips"], np.float64) / fn))
+    assert n <= 3 or ips != running_sum(cols["ips"], np.float64)
+    assert out[:4].tobytes() == want.tobytes()

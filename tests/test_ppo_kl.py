@@ -503,3 +503,36 @@ def test_coefficient_update_with_nothing_accumulated(rlx, dev):
     c, kl = _update(rlx, dev, [0.0, 0.0, 0.0, 0.0], 0.01, 0.7)
     _same_bits([c], [F32(0.7)], "coefficient")
     _same_bits([kl], [F32(0.0)], "mean KL")
+
+
+# ------------------------------------------------------------------------------------------------ the batch sum's order
+TREE_BATCHES = [1, 3, 65]         # one row; fewer rows than a wave, not a power of two; one row past the 64-thread block
+
+
+def _tree_case(B):
+    case = dict(R.discrete_case(900 + B, B, 6))
+    case["advantages"] = H.wide_terms(np.random.RandomState(900 + B), B)
+    return case
+
+
+@pytest.mark.parametrize("B", TREE_BATCHES)
+def test_the_chosen_advantages_tell_the_tree_from_a_running_sum(B):
+    """with ratios near 1 the surrogate rows are about the advantages: their tree and their running sum differ"""
+    adv = _tree_case(B)["advantages"]
+    assert B == 1 or H.tree_sum(adv, H.block_for(B)).tobytes() != H.running_sum(adv).tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", TREE_BATCHES)
+def test_discrete_surrogate_sums_the_batch_in_the_tree(rlx, dev, B):
+    """scalars[0] is -tree_sum(ratio_b * advantage_b) * (1 / B) in fp32, bit for bit, with the ratios the launch itself
+    wrote (no expf left in the comparison) and block_for(B) threads; it is not the running sum of the same rows."""
+    case = _tree_case(B)
+    out = _run_discrete(rlx, dev, case, 6, 0, 0.0, 1.0, KLC, 1e9, HIGH, False, want="sr")
+    assert out["status"] == 0
+    rows = (out["r"] * case["advantages"]).astype(F32)
+    inv = F32(1) / F32(B)
+    tree, running = H.tree_sum(rows, H.block_for(B)), H.running_sum(rows)
+    print("surrogate %r tree %r running %r" % (out["s"][0], -tree * inv, -running * inv))
+    assert B <= 3 or tree.tobytes() != running.tobytes()
+    _same_bits(out["s"][:1], [-tree * inv], "surrogate, B = %d" % B)

@@ -230,3 +230,26 @@ def test_cartpole_qr_dqn_preset_reaches_the_golden_threshold(dev, tmp_path):
     from test_cartpole import _golden
     st = _golden(dev, "CartPole_QR_DQN", tmp_path)
     assert st["passed"], st
+
+
+@pytest.mark.parametrize("B", [1, 3, 200])
+def test_the_batch_sum_is_the_tree_of_the_row_partials(rlx, dev, B):
+    """loss * N is head_loss_ref.tree_sum over 256 threads of the row partials the workgroups left in the workspace, bit
+    for bit (rlx::ticketed_batch_sum): rewards over six decades spread the rows' partials, and over 200 rows their running
+    sum is another number (asserted).  One workgroup per row, so 200 rows use the tree's upper levels."""
+    import torch
+    from head_loss_ref import running_sum, tree_sum, wide_terms
+    rng = np.random.RandomState(80 + B)
+    A, N = 3, 8
+    theta, theta_next = rng.randn(B, A, N).astype(np.float32), rng.randn(B, A, N).astype(np.float32)
+    rewards = wide_terms(rng, B)
+    ws = torch.zeros(256, dtype=torch.float32, device=dev)
+    ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+    loss = _launch(rlx, dev, theta, theta_next, rng.randint(0, A, size=B), rewards, np.zeros(B, bool), 0.99, 1.0, ws,
+                   ticket)[3]
+    rows = ws.cpu().numpy()
+    assert not rows[B:].any()
+    tree, running = tree_sum(rows, 256), running_sum(rows[:B])
+    print("loss %r tree / N %r running / N %r" % (loss, tree / np.float32(N), running / np.float32(N)))
+    assert B <= 3 or tree.tobytes() != running.tobytes()
+    assert loss.tobytes() == (tree / np.float32(N)).tobytes()

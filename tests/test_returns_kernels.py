@@ -375,3 +375,42 @@ def test_episode_nstep_returns_refusals(rlx, dev, why):
     out.check_guards()
     compact.check_guards()
     inp.check_unchanged()
+
+
+STANDARDIZE_THREADS = 1024        # the one workgroup of rlx_standardize
+TREE_SIZES = [1, 3, 1025]         # one value; fewer than a wave, not a power of two; the workgroup's width plus one
+
+
+def _standardize_tree(x):
+    """mean and std as the kernel takes them: two head_loss_ref.tree_sum in fp64 over 1024 threads (x, then the squares of
+    x - mean), each divided by n, one square root"""
+    from head_loss_ref import tree_sum
+    n = np.float64(x.size)
+    mean = tree_sum(x, STANDARDIZE_THREADS, np.float64) / n
+    d = x - mean
+    return mean, np.sqrt(tree_sum(d * d, STANDARDIZE_THREADS, np.float64) / n)
+
+
+def _tree_values(n):
+    from head_loss_ref import wide_terms
+    return wide_terms(np.random.RandomState(40 + n), n, np.float64)
+
+
+@pytest.mark.parametrize("n", TREE_SIZES)
+def test_the_chosen_values_tell_the_tree_from_a_running_sum(n):
+    from head_loss_ref import running_sum
+    x = _tree_values(n)
+    mean, _ = _standardize_tree(x)
+    assert n == 1 or mean != running_sum(x, np.float64) / np.float64(n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", TREE_SIZES)
+def test_standardize_takes_its_two_sums_in_the_tree(rlx, dev, n):
+    """the statistics are the tree's bit for bit (fp64, no contraction; division and square root are correctly rounded on
+    either side), on values over six decades whose running sum gives another mean (the test above)"""
+    x = _tree_values(n)
+    mean, std = _standardize_tree(x)
+    _, _, ms = _standardize(rlx, dev, x)
+    print("mean %r tree %r   std %r tree %r" % (ms[0], mean, ms[1], std))
+    assert same_bits(ms, np.array([mean, std]))
