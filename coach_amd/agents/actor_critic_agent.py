@@ -10,7 +10,11 @@ rlx_a3c_window_loss (csrc/a3c.hip), restates learn_from_batch :138-165 — R = 0
 A_VALUE loop or the GAE recurrences in the reference's order and rounding, the fp32 placeholders — and both heads' losses
 and gradients; backward; accumulated += gradients.  Every apply_gradients_every_x_episodes episodes: one TF1 Adam step.
 Neither V nor the targets leave the device.  The window, pointer and apply cadence are the base's.
-Discrete action spaces only: the continuous PolicyHead (and with it ContinuousEntropy exploration) is not served.
+On a Box action space, with `exploration = ContinuousEntropyParameters()`: the continuous PolicyHead — a bounded mean
+stream and a softplus standard-deviation stream (ContinuousActorCriticNet) — acts by np.random.normal(mean, std) on host
+normals, stores float actions, and the window's launch is rlx_a3c_continuous_window_loss: the same targets, the Gaussian
+log-probability and entropy in place of the categorical ones.  No 'Entropy' sample is emitted there (the reference emits
+none).  Under any other exploration parameters a Box action space is refused.
 """
 import torch
 
@@ -18,8 +22,9 @@ from .. import _rlx
 from ..architectures.head_parameters import PolicyHeadParameters, VHeadParameters
 from ..architectures.scheme_views import SchemeViews
 from ..exploration_policies.categorical import CategoricalParameters
+from ..exploration_policies.continuous_entropy import ContinuousEntropyParameters
 from ..memories.episodic.single_episode_buffer import SingleEpisodeBufferParameters
-from ..nn.networks import ActorCriticNet, actor_critic_net_kwargs
+from ..nn.networks import ActorCriticNet, ContinuousActorCriticNet, actor_critic_net_kwargs, box_output_scale
 from .policy_optimization_agent import PolicyGradientRescaler, PolicyOptimizationAgent
 from .vector_agent import AlgorithmParameters
 
@@ -56,8 +61,8 @@ class ActorCriticNetworkParameters(SchemeViews):         # actor_critic_agent.py
 class ActorCriticAgentParameters(object):                # actor_critic_agent.py:80-90
     def __init__(self):
         self.algorithm = ActorCriticAlgorithmParameters()
-        # the reference maps DiscreteActionSpace -> Categorical, BoxActionSpace -> ContinuousEntropy; the Box branch needs
-        # the continuous PolicyHead, which is not served
+        # the reference maps DiscreteActionSpace -> Categorical, BoxActionSpace -> ContinuousEntropy; here the default
+        # stays the discrete one and a Box environment asks for ContinuousEntropyParameters() explicitly
         self.exploration = CategoricalParameters()
         self.memory = SingleEpisodeBufferParameters()
         self.network_wrappers = {"main": ActorCriticNetworkParameters()}
@@ -73,6 +78,7 @@ _RESCALERS = (PolicyGradientRescaler.A_VALUE, PolicyGradientRescaler.GAE)
 
 class ActorCriticAgent(PolicyOptimizationAgent):
     SIGNAL_NAMES = PolicyOptimizationAgent.SIGNAL_NAMES + ["Advantages", "Values", "Value Loss", "Policy Loss"]  # :98-101
+    BOX_EXPLORATION = ContinuousEntropyParameters
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         rescaler = agent_parameters.algorithm.policy_gradient_rescaler
@@ -89,8 +95,11 @@ class ActorCriticAgent(PolicyOptimizationAgent):
         self.debug_targets = None        # tests set this to a list: (V, value targets, advantages) clones per window
 
     def _make_network(self, obs_shape, wrapper):
-        return ActorCriticNet(self.device, obs_shape, self.A,
-                              **actor_critic_net_kwargs(wrapper, self.ap.algorithm, self.ap.seed or 0))
+        kw = actor_critic_net_kwargs(wrapper, self.ap.algorithm, self.ap.seed or 0)
+        if self.continuous:
+            return ContinuousActorCriticNet(self.device, obs_shape, self.A, box_output_scale(self.low, self.high),
+                                            self.learned_std, **kw)
+        return ActorCriticNet(self.device, obs_shape, self.A, **kw)
 
     def _window_device(self, env, start, end, complete):
         """learn_from_batch (:127-186) on steps [start, end) of env's episode.  The bootstrap state is always forwarded

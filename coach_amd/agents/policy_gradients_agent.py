@@ -8,16 +8,21 @@ rlx_pg_episode_window, restates the returns of the episode (n_step -1), update_e
 with its quirks and the 'Returns Mean' / 'Returns Variance' samples, and leaves the fp32 advantages column; forward on the
 window's states; ONE launch, rlx_pg_head_loss, gives -mean(log pi(a) * advantage) - beta * mean entropy and dlogits;
 backward; accumulated += gradients.  Every apply_gradients_every_x_episodes episodes: one TF1 Adam step.
-Discrete action spaces only: the continuous PolicyHead (and with it AdditiveNoise exploration) is not served.
+On a Box action space, with `exploration = AdditiveNoiseParameters()`: the continuous PolicyHead's bounded mean stream
+under a given std of ones (the reference never assigns policy_std; ContinuousPolicyGradientNet), actions = mean + the
+noise schedule's std * host normals, float actions in the episode rows, and the head launch is
+rlx_pg_continuous_head_loss.  No 'Entropy' sample is emitted there.  Under any other exploration parameters a Box
+action space is refused.
 """
 import torch
 
 from .. import _rlx
 from ..architectures.head_parameters import PolicyHeadParameters
 from ..architectures.scheme_views import SchemeViews
+from ..exploration_policies.additive_noise import AdditiveNoiseParameters
 from ..exploration_policies.categorical import CategoricalParameters
 from ..memories.episodic.single_episode_buffer import SingleEpisodeBufferParameters
-from ..nn.networks import PolicyGradientNet, policy_gradient_net_kwargs
+from ..nn.networks import ContinuousPolicyGradientNet, PolicyGradientNet, box_output_scale, policy_gradient_net_kwargs
 from .policy_optimization_agent import PolicyGradientRescaler, PolicyOptimizationAgent
 from .vector_agent import AlgorithmParameters
 
@@ -52,8 +57,8 @@ class PolicyGradientAlgorithmParameters(AlgorithmParameters):          # policy_
 class PolicyGradientsAgentParameters(object):            # policy_gradients_agent.py:74-84
     def __init__(self):
         self.algorithm = PolicyGradientAlgorithmParameters()
-        # the reference maps DiscreteActionSpace -> Categorical, BoxActionSpace -> AdditiveNoise; the Box branch needs
-        # the continuous PolicyHead, which is not served
+        # the reference maps DiscreteActionSpace -> Categorical, BoxActionSpace -> AdditiveNoise; here the default stays
+        # the discrete one and a Box environment asks for AdditiveNoiseParameters() explicitly
         self.exploration = CategoricalParameters()
         self.memory = SingleEpisodeBufferParameters()
         self.network_wrappers = {"main": PolicyGradientNetworkParameters()}
@@ -71,6 +76,7 @@ _RESCALERS = (PolicyGradientRescaler.TOTAL_RETURN, PolicyGradientRescaler.FUTURE
 
 class PolicyGradientsAgent(PolicyOptimizationAgent):
     SIGNAL_NAMES = PolicyOptimizationAgent.SIGNAL_NAMES + ["Returns Mean", "Returns Variance"]      # :90-91
+    BOX_EXPLORATION = AdditiveNoiseParameters
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         rescaler = agent_parameters.algorithm.policy_gradient_rescaler
@@ -86,8 +92,11 @@ class PolicyGradientsAgent(PolicyOptimizationAgent):
         self.window_stats = torch.zeros(4, dtype=torch.float64, device=dev)  # Returns Mean, Returns Variance, episode mean, std
 
     def _make_network(self, obs_shape, wrapper):
-        return PolicyGradientNet(self.device, obs_shape, self.A,
-                                 **policy_gradient_net_kwargs(wrapper, self.ap.algorithm, self.ap.seed or 0))
+        kw = policy_gradient_net_kwargs(wrapper, self.ap.algorithm, self.ap.seed or 0)
+        if self.continuous:
+            return ContinuousPolicyGradientNet(self.device, obs_shape, self.A, box_output_scale(self.low, self.high),
+                                               self.learned_std, **kw)
+        return PolicyGradientNet(self.device, obs_shape, self.A, **kw)
 
     def _window_device(self, env, start, end, complete):
         """learn_from_batch (:98-133) on steps [start, end) of env's episode, preceded by what train() does to the

@@ -24,6 +24,10 @@ env order:
     apply_gradients_every_x_episodes == 0` — checked at EVERY window, as the reference does — with `current_episode` as
     handle_episode_ended left it: it counts an env's finished episode before that env's train();
   * `training_iteration` counts windows.
+A Box action space is served where a subclass names the exploration parameters that build the continuous PolicyHead
+(`BOX_EXPLORATION`: Actor-Critic under ContinuousEntropyParameters, Policy Gradients under AdditiveNoiseParameters): the
+policy streams' forward gives (mean, std), the exploration policy forms mean + std * z on host normals, the episode rows
+hold float actions, heat-up draws uniformly in the box, and no 'Entropy' sample is emitted (the reference emits none).
 Window lengths differ from update to update, so train() issues its launches eagerly (the network context keys its
 buffers by shape); acting is a captured graph.  Data-parallel training is refused: the reference's on-policy agents
 train asynchronously (`async_training`), which has no mapping onto the synchronous gradient all-reduce yet.
@@ -35,9 +39,11 @@ import torch
 
 from .. import _rlx
 from ..core_types import RunPhase
+from ..exploration_policies.additive_noise import AdditiveNoise
 from ..exploration_policies.categorical import Categorical
+from ..exploration_policies.continuous_entropy import ContinuousEntropy, ContinuousEntropyParameters
 from ..memories.episodic.single_episode_buffer import SingleEpisodeBuffer
-from .vector_agent import VectorOffPolicyAgent
+from .vector_agent import BoxActionAgent, VectorOffPolicyAgent
 
 
 class PolicyGradientRescaler(Enum):                      # policy_optimization_agent.py:30-39
@@ -56,6 +62,7 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
     """the stepping machinery of the vector agents under an on-policy train(); a subclass gives `_make_network` and
     `_window_device` (the reference's learn_from_batch on one window)."""
     SIGNAL_NAMES = VectorOffPolicyAgent.SIGNAL_NAMES + ["Entropy"]            # policy_optimization_agent.py:58
+    BOX_EXPLORATION = None           # the exploration parameters under which a subclass serves a Box action space
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         # refused before anything touches the device
@@ -63,20 +70,35 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
             raise ValueError("data-parallel on-policy training is not served: the reference's policy-optimisation agents "
                              "train asynchronously (async_training), which has no mapping onto the gradient all-reduce")
         ep = environment.p
-        if getattr(ep, "action_dim", None) is not None or not getattr(ep, "num_actions", None):
+        box = getattr(ep, "action_dim", None) is not None or not getattr(ep, "num_actions", None)
+        if box and (self.BOX_EXPLORATION is None or getattr(ep, "action_dim", None) is None):
             raise ValueError("a Box action space needs the continuous PolicyHead, which is not served: the "
                              "policy-optimisation agents take discrete action spaces only")
+        if box and not isinstance(agent_parameters.exploration, self.BOX_EXPLORATION):
+            raise ValueError("a Box action space needs the continuous PolicyHead, which %s builds when "
+                             "agent_parameters.exploration is set to a %s (got %s)"
+                             % (type(self).__name__, self.BOX_EXPLORATION.__name__,
+                                type(agent_parameters.exploration).__name__))
         if getattr(ep, "kind", "vector") == "image":
             raise ValueError("image observations are not served by the on-policy agents' episode buffer")
         super().__init__(agent_parameters, environment, device, None, use_graphs)
         alg = self.ap.algorithm
-        self.A = int(ep.num_actions)
+        self.continuous = box
+        if box:
+            BoxActionAgent._set_action_bounds(self, ep)
+            if not (np.all(np.isfinite(self.low)) and np.all(np.isfinite(self.high))):
+                raise ValueError("Additive noise exploration requires bounded actions")      # additive_noise.py:71-73
+            # ContinuousEntropyParameters: the head has a standard-deviation stream (policy_head.py:124-131)
+            self.learned_std = isinstance(self.ap.exploration, ContinuousEntropyParameters)
+        else:
+            self.A = int(ep.num_actions)
         self.policy_gradient_rescaler = getattr(alg, "policy_gradient_rescaler", None)      # :49-51
         self.networks = {"main": self._make_network(tuple(ep.observation_shape), self.ap.network_wrappers["main"])}
         self.memory = self._make_episode_buffer(tuple(ep.observation_shape))
         self.exploration_policy = self._make_exploration_policy()
         dev, n, L = self.device, self.n_env, self.L
-        self.actions = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.actions = torch.zeros(n, self.A, dtype=torch.float32, device=dev) if box else \
+            torch.zeros(n, dtype=torch.int32, device=dev)
         self.action_probabilities = torch.zeros(n, self.A, dtype=torch.float32, device=dev)
         self.entropy = torch.zeros(n, dtype=torch.float32, device=dev)         # the 'Entropy' samples of the last step
         # statistics for variance reduction (:53-57): sized by the environment's episode limit, not 100 000
@@ -98,10 +120,15 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
 
     def _make_episode_buffer(self, obs_shape):
         """the staging buffer of the running episodes; ACER's also keeps the acting probabilities and feeds a replay"""
-        return SingleEpisodeBuffer(self.device, self.n_env, obs_shape, self.L)
+        return SingleEpisodeBuffer(self.device, self.n_env, obs_shape, self.L,
+                                   action_dim=self.A if self.continuous else None)
 
     def _make_exploration_policy(self):
-        """the family acts by a categorical draw on the policy head; a value-based member (N-step Q) gives its own"""
+        """the family acts by a categorical draw on the policy head, or by Gaussian noise around the continuous head's
+        mean; a value-based member (N-step Q) gives its own"""
+        if self.continuous:
+            cls = ContinuousEntropy if self.learned_std else AdditiveNoise
+            return cls(self.low, self.high, self.n_env, self.device, self.ap.exploration)
         return Categorical(self.A, self.n_env, self.device, self.ap.exploration)
 
     def _window_device(self, env, start, end, complete):
@@ -110,6 +137,8 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
 
     # --------------------------------------------------------------------------------- acting
     def random_actions(self):
+        if self.continuous:
+            return BoxActionAgent.random_actions(self)
         a = np.array([np.random.choice(self.A) for _ in range(self.n_env)], dtype=np.int32)
         self.actions.copy_(self._to_device("rand_act", a, torch.int32))
         return self.actions
@@ -121,9 +150,17 @@ class PolicyOptimizationAgent(VectorOffPolicyAgent):
         self.lib.action_entropy(self.action_probabilities, self.A, self.n_env, self.A, self.entropy,
                                 _rlx.current_stream())
 
+    def _policy_forward(self, states):
+        self._policy_mean, self._policy_std = self.networks["main"].policy_values(states, self.n_env, tag="act")
+
     def choose_action(self, states):
         pol = self.exploration_policy
         pol.phase = self.phase
+        if self.continuous:
+            # the head's (mean, std), then np.random.normal(mean, std) outside TEST: the network's std under
+            # ContinuousEntropy, the schedule's under AdditiveNoise.  No 'Entropy' sample (:153-154 is the discrete branch)
+            self._run(("act", states.data_ptr()), lambda: self._policy_forward(states))
+            return pol.get_action(self._policy_mean, self.actions, self._policy_std if self.learned_std else None)
         u = pol.draw()                                               # host RNG, per env, in order
         staged = pol.stage(u) if u is not None else None
         self._run(("act", staged is not None, states.data_ptr()), lambda: self._act_device(states, staged))

@@ -5,13 +5,14 @@
 //   * PolicyOptimizationAgent.update_episode_statistics          agents/policy_optimization_agent.py:72-83
 //   * PolicyGradientsAgent.learn_from_batch's rescaling loop     agents/policy_gradients_agent.py:102-126
 //   * PolicyHead, discrete branch (loss, entropy regularisation) architectures/tensorflow_components/heads/policy_head.py:75-100
+//   * PolicyHead, continuous branch (Box action spaces)          .../heads/policy_head.py:102-146 (gaussian_policy_head.hpp)
 //   * the 'Entropy' sample of choose_action                      agents/policy_optimization_agent.py:154
 //
 // These are latency-bound row kernels over tens to hundreds of rows, launched once per update window: each is ONE
 // workgroup, so every sum has a fixed order and no float atomics or hand-offs between workgroups are needed.
 // tests/pg_ref.py is the numpy restatement; it states every fp32 / fp64 rounding point named here.
 // Compiled with -ffp-contract=off so the fp64 arithmetic rounds like numpy.
-#include "policy_head.hpp"
+#include "gaussian_policy_head.hpp"
 #include "episode_returns.hpp"
 
 namespace {
@@ -190,6 +191,47 @@ __global__ void __launch_bounds__(kPgThreads) pg_head_loss_kernel(const HeadLoss
     }
 }
 
+// The continuous PolicyHead against fp32 advantages: the rows in chunks of 256 through the head's LDS tiles
+// (gaussian_policy_head.hpp); thread t owns rows t, t + 256, ... and adds their terms in row order.  Rows [T, rows) are
+// padding: zero gradient, no term.
+struct ContinuousHeadLossArgs {
+    rlx::GaussianHead h;
+    const float *advantages;
+    float beta;
+    int rows, T;
+    float *scalars;             // [2]: loss, mean entropy
+};
+
+__global__ void __launch_bounds__(kPgThreads) pg_continuous_head_loss_kernel(const ContinuousHeadLossArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float tiles[];
+    __shared__ float pol_s[kPgThreads], ent_s[kPgThreads];
+    const float fT = (float)a.T;
+    const float *advantages = a.advantages;
+    float pol = 0.f, ent = 0.f;
+    for (int r0 = 0; r0 < a.rows; r0 += kPgThreads)
+        rlx::gaussian_head_chunk(a.h, tiles, r0, a.rows, a.T, a.beta, fT, [advantages](int b) { return advantages[b]; },
+                                 pol, ent);
+    rlx::tree_sum(kPgThreads, pol_s, pol, ent_s, ent);
+    if (threadIdx.x == 0) {
+        const float mean_h = ent_s[0] / fT;
+        a.scalars[0] = -(pol_s[0] / fT) - a.beta * mean_h;
+        a.scalars[1] = mean_h;
+    }
+}
+
+// mean = c * tanh(m) (or m), std = softplus(s) + eps (or the given std): the head's own functions, one element per thread
+__global__ void gaussian_policy_forward_kernel(const float *__restrict__ mean_pre, long long ld_m,
+                                               const float *__restrict__ std_pre, long long ld_s,
+                                               const float *__restrict__ std, const float *__restrict__ scale, int n,
+                                               int D, float *__restrict__ mean_out, float *__restrict__ std_out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * D) return;
+    const int r = e / D, j = e - r * D;
+    float dmu_dm;
+    mean_out[e] = rlx::gaussian_mean(mean_pre[(size_t)r * ld_m + j], scale, j, dmu_dm);
+    std_out[e] = std_pre ? rlx::gaussian_std(std_pre[(size_t)r * ld_s + j]) : std[j];
+}
+
 __global__ void action_entropy_kernel(const float *__restrict__ probs, long long ld, int n_env, int A,
                                       float *__restrict__ out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,6 +275,39 @@ int rlx_pg_head_loss(const float *logits, long long ld, const int *actions, cons
     HeadLossArgs a{logits, ld, actions, advantages, beta_entropy, rows, true_rows, n_actions, dlogits, ld_dlogits,
                    scalars, status};
     RLX_LAUNCH((pg_head_loss_kernel), 1, kPgThreads, 0, rlx::as_stream(stream), a);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_pg_continuous_head_loss(const float *mean_pre, long long ld_m, const float *std_pre, long long ld_s,
+                                const float *std, const float *scale, const float *actions, const float *advantages,
+                                float beta_entropy, int rows, int true_rows, int action_dim, float *dmean_pre,
+                                long long ld_dm, float *dstd_pre, long long ld_ds, float *scalars, void *stream) {
+    const char *fn = "rlx_pg_continuous_head_loss";
+    const rlx::GaussianHead h{mean_pre, ld_m, std_pre, ld_s, std, scale, actions, action_dim, dmean_pre, ld_dm, dstd_pre,
+                              ld_ds};
+    if (int rc = rlx::check_gaussian_head(fn, h)) return rc;
+    RLX_REQUIRE(advantages && scalars, "%s: null pointer", fn);
+    RLX_REQUIRE(true_rows >= 1 && rows >= true_rows, "%s: unsupported sizes (1 <= true rows=%d <= rows=%d)", fn,
+                true_rows, rows);
+    const size_t lds = rlx::gaussian_tiles_bytes(action_dim);
+    RLX_HIP(rlx::allow_lds<pg_continuous_head_loss_kernel>(lds));
+    ContinuousHeadLossArgs a{h, advantages, beta_entropy, rows, true_rows, scalars};
+    RLX_LAUNCH((pg_continuous_head_loss_kernel), 1, kPgThreads, (unsigned)lds, rlx::as_stream(stream), a);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_gaussian_policy_forward(const float *mean_pre, long long ld_m, const float *std_pre, long long ld_s,
+                                const float *std, const float *scale, int n, int action_dim, float *mean_out,
+                                float *std_out, void *stream) {
+    RLX_REQUIRE(mean_pre && (std_pre || std) && mean_out && std_out, "rlx_gaussian_policy_forward: null pointer");
+    RLX_REQUIRE(action_dim >= 1 && action_dim <= rlx::kGaussMaxDim && n >= 1 && n <= (1 << 24),
+                "rlx_gaussian_policy_forward: unsupported sizes (1 <= D=%d <= 32, 1 <= n=%d <= 2^24)", action_dim, n);
+    RLX_REQUIRE(ld_m >= action_dim && (!std_pre || ld_s >= action_dim),
+                "rlx_gaussian_policy_forward: leading dimension < D");
+    RLX_LAUNCH((gaussian_policy_forward_kernel), (n * action_dim + 255) / 256, 256, 0, rlx::as_stream(stream), mean_pre,
+               ld_m, std_pre, ld_s, std, scale, n, action_dim, mean_out, std_out);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

@@ -51,8 +51,10 @@ class AdditiveNoise(object):
             return (noise * (self.high - self.low)).astype(np.float32)
         return np.full(self.A, noise, dtype=np.float32)
 
-    def get_action(self, action_means, out_actions):
-        """action_means: device fp32 [n_env, A]."""
+    def get_action(self, action_means, out_actions, action_stds=None):
+        """action_means: device fp32 [n_env, A].  action_stds: device fp32 [n_env, A], the standard deviations a
+        network gave with the means (the second element of the reference's action_values list, :101-103): outside TEST
+        they replace the schedule's value, per sample."""
         std = self.current_std()
         if self.phase != RunPhase.TEST:
             for _ in range(self.n_env):
@@ -64,6 +66,7 @@ class AdditiveNoise(object):
         else:
             self._z.push(np.zeros((self.n_env, self.A)))
         self.d_std.copy_(torch.from_numpy(std), non_blocking=True)
-        self.lib.gaussian_action(action_means, self.d_std, None, self.d_z, None, None,
+        per_sample = action_stds if self.phase != RunPhase.TEST else None
+        self.lib.gaussian_action(action_means, self.d_std, per_sample, self.d_z, None, None,
                                  self.n_env, self.A, out_actions, _rlx.current_stream())
         return out_actions

@@ -16,6 +16,8 @@ response is not yet counted started from), so the window's T + 1 states are `obs
 finished episode it is `next_obs[end - 1]`, the observation BEFORE the reset (`last_next_state`).
 ACER adds two things, both optional: a per-row column `mu` for the behaviour policy's probabilities of the acting step,
 and a replay of complete episodes (memories/episodic/episode_store.py) that receives an env's rows when its episode ends.
+On a Box action space (`action_dim`) the action column is float32 [rows, D]: the continuous PolicyHead's agents store the
+noisy action as the exploration policy returned it, D floats per env in the same copy launch.
 Evaluation never writes: `begin_evaluation` only redirects the acting state, as the device replays do.
 """
 import numpy as np
@@ -33,11 +35,12 @@ class SingleEpisodeBufferParameters(MemoryParameters):                  # single
 
 class SingleEpisodeBuffer(Memory):
     def __init__(self, device=None, n_env=1, observation_shape=None, max_episode_length=None,
-                 action_probabilities=0, replay=None):
+                 action_probabilities=0, replay=None, action_dim=None):
         """action_probabilities: A > 0 adds a per-row column [rows, A] for the behaviour policy's probabilities of the
         acting step (ACER's info['all_action_probabilities']), written by the step's one copy launch; replay: an
-        EpisodeStore that receives every finished episode's rows (ACER).  Without them the rows and launches are the
-        on-policy agents'."""
+        EpisodeStore that receives every finished episode's rows (ACER); action_dim: D of a Box action space — the
+        action column is float32 [rows, D], D floats per env in the same copy launch, instead of int32 [rows].  Without
+        them the rows and launches are the on-policy agents'."""
         super().__init__((MemoryGranularity.Episodes, 1))                   # single_episode_buffer.py:33
         if device is None or observation_shape is None or not max_episode_length:
             raise ValueError("the device episode buffer needs a device, an observation shape and the episode limit")
@@ -48,7 +51,8 @@ class SingleEpisodeBuffer(Memory):
         self.obs_dim = int(observation_shape[0])
         rows = self.rows = self.n_env * self.L
         self.obs = torch.zeros(rows, self.obs_dim, dtype=torch.float32, device=device)
-        self.action = torch.zeros(rows, dtype=torch.int32, device=device)
+        self.action = torch.zeros(rows, dtype=torch.int32, device=device) if action_dim is None else \
+            torch.zeros(rows, int(action_dim), dtype=torch.float32, device=device)
         self.reward = torch.zeros(rows, dtype=torch.float32, device=device)
         self.game_over = torch.zeros(rows, dtype=torch.uint8, device=device)
         self.next_obs = torch.zeros(rows, self.obs_dim, dtype=torch.float32, device=device)     # before the reset

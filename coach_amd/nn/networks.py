@@ -1479,6 +1479,129 @@ class ActorCriticNet(_WindowAccumulatingNet):
         return self._finish_window(acts)
 
 
+def box_output_scale(low, high):
+    """BoxActionSpace.max_abs_range per dimension (spaces.py) -> the bounded mean stream's scale [D], or None when any
+    bound is infinite (the head's unbounded branch, policy_head.py:107-114)"""
+    scale = np.maximum(np.abs(np.asarray(low, dtype=np.float32)), np.abs(np.asarray(high, dtype=np.float32)))
+    return scale if np.all(scale < np.inf) else None
+
+
+class _GaussianPolicyStreams:
+    """the continuous PolicyHead (heads/policy_head.py:102-146) of the two networks below: Dense(feat, D) named
+    'fc_mean' with default initialisation and, with learned_std (ContinuousEntropyParameters), Dense(feat, D) named
+    'fc_std' with normalized-columns init std 0.01; otherwise the std is `policy_std` [D], ones unless assigned (the
+    reference's policy_stdev variable).  The arithmetic behind the streams is csrc/gaussian_policy_head.hpp's."""
+
+    def _build_policy_streams(self, feat, action_dim, learned_std):
+        self.D = int(action_dim)
+        if not 1 <= self.D <= 32:
+            raise ValueError("the continuous PolicyHead serves 1 to 32 action dimensions, got %d" % self.D)
+        name = "main/policy_values_head/"
+        self.policy_heads = [G.Dense(self.params, name + "fc_mean", feat, self.D, None, 1)]
+        if learned_std:
+            self.policy_heads.append(G.Dense(self.params, name + "fc_std", feat, self.D, None, 1,
+                                             init=G.normalized_columns(0.01)))
+        self.learned_std = bool(learned_std)
+
+    def _finish_policy_streams(self, output_scale):
+        self.output_scale = None if output_scale is None else torch.as_tensor(
+            np.broadcast_to(np.asarray(output_scale, dtype=np.float32), (self.D,)).copy(), device=self.device)
+        self.policy_std = None if self.learned_std else torch.ones(self.D, dtype=torch.float32, device=self.device)
+
+    def _stream_args(self, outs):
+        """the policy streams' outputs -> (mean_pre, ld, std_pre, ld, std, scale) of the three entry points"""
+        s = outs[1].data if self.learned_std else None
+        return outs[0].data, self.D, s, self.D, self.policy_std, self.output_scale
+
+    def _stream_grads(self, outs):
+        """-> (dmean_pre, ld, dstd_pre, ld): the streams' gradient buffers"""
+        ds = outs[1].ensure_grad() if self.learned_std else None
+        return outs[0].ensure_grad(), self.D, ds, self.D
+
+    def _mean_std(self, outs, B, tag):
+        """the streams' outputs on B rows -> (mean, std) [B, D] buffers (rlx_gaussian_policy_forward)"""
+        mean = self.ctx.buffer("policy_mean", (B, self.D), tag=tag)
+        std = self.ctx.buffer("policy_std", (B, self.D), tag=tag)
+        self.lib.gaussian_policy_forward(*self._stream_args(outs), B, self.D, mean, std, self.ctx.stream)
+        return mean, std
+
+    def policy_values(self, obs, B, tag="act"):
+        """(mean, std) [B, D] of the policy on obs; a V head is not run"""
+        feat = self.trunk_forward(obs, B, tag)[-1]
+        return self._mean_std(self._heads_forward([(l, feat) for l in self.policy_heads], tag), B, tag)
+
+
+class ContinuousPolicyGradientNet(_GaussianPolicyStreams, PolicyGradientNet):
+    """PolicyGradientNet on a Box action space: the torso under the continuous PolicyHead; the head's loss and its
+    gradients come from rlx_pg_continuous_head_loss (csrc/policy_gradient.hip).  Policy Gradients explores with
+    AdditiveNoise, so the std is the given one (learned_std=False)."""
+
+    def __init__(self, device, obs_shape, action_dim, output_scale=None, learned_std=False, activation="relu",
+                 embedder="Medium", middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99,
+                 optimizer_epsilon=1e-4, clip_gradients=None, beta_entropy=0.0, seed=0):
+        self.clip_gradients = clip_gradients
+        self.beta_entropy = float(beta_entropy)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        self._build_policy_streams(feat, action_dim, learned_std)
+        self.modules = [self.torso] + self.policy_heads
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self._finish_policy_streams(output_scale)
+        self._finish_accumulating(("loss", "entropy"))
+
+    def window_gradients(self, obs, T, actions, advantages):
+        """PolicyGradientNet.window_gradients with float actions [T, D]"""
+        acts = self.trunk_forward(obs, T, "train")
+        fork = self._fork(acts[-1], self.policy_heads, "train")
+        outs = self._heads_forward(fork, "train")
+        self.lib.pg_continuous_head_loss(*self._stream_args(outs), actions, advantages, self.beta_entropy, T, T, self.D,
+                                         *self._stream_grads(outs), self.scalars, self.ctx.stream)
+        self._heads_backward(acts[-1], fork, outs)
+        return self._finish_window(acts)
+
+
+class ContinuousActorCriticNet(_GaussianPolicyStreams, ActorCriticNet):
+    """ActorCriticNet on a Box action space: the torso under the VHead and the continuous PolicyHead; the launch between
+    the forward and the backward pass of a window is rlx_a3c_continuous_window_loss (csrc/a3c.hip).  Actor-Critic
+    explores with ContinuousEntropy, so the std is the network's (learned_std=True)."""
+
+    def __init__(self, device, obs_shape, action_dim, output_scale=None, learned_std=True, activation="relu",
+                 embedder="Medium", middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99,
+                 optimizer_epsilon=1e-4, clip_gradients=40.0, beta_entropy=0.0, v_loss_weight=0.5, seed=0):
+        self.clip_gradients = clip_gradients
+        self.beta_entropy, self.v_loss_weight = float(beta_entropy), float(v_loss_weight)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        self.v_head = G.Dense(self.params, "main/v_values_head/output", feat, 1, None, 1, init=G.normalized_columns(1.0))
+        self._build_policy_streams(feat, action_dim, learned_std)
+        self.heads = [self.v_head] + self.policy_heads
+        self.modules = [self.torso] + self.heads
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self._finish_policy_streams(output_scale)
+        self._finish_accumulating(("loss", "value_loss", "policy_loss", "entropy"))
+
+    def predict(self, obs, B, tag="predict"):
+        """every head -> (V [B], mean [B, D], std [B, D]) as buffers"""
+        feat = self.trunk_forward(obs, B, tag)[-1]
+        outs = self._heads_forward([(l, feat) for l in self.heads], tag)
+        return (outs[0].data.view(B),) + self._mean_std(outs[1:], B, tag)
+
+    def window_gradients(self, obs_rows, T, bootstrap, actions, targets, advantages, rewards=None, game_over=None,
+                         discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False):
+        """ActorCriticNet.window_gradients with float actions [T, D]"""
+        rows = T + int(bool(bootstrap))
+        acts = self.trunk_forward(obs_rows, rows, "train")
+        fork = self._fork(acts[-1], self.heads, "train")
+        outs = self._heads_forward(fork, "train")
+        v = outs[0]
+        self.values = v.data.view(rows)
+        self.lib.a3c_continuous_window_loss(v.data, 1, *self._stream_args(outs[1:]), actions, rewards, game_over, T, rows,
+                                            self.D, float(discount), float(gae_lambda), int(rescaler),
+                                            int(bool(estimate_with_gae)), self.beta_entropy, self.v_loss_weight, targets,
+                                            advantages, v.ensure_grad(), 1, *self._stream_grads(outs[1:]), self.scalars,
+                                            self.status, self.ctx.stream)
+        self._heads_backward(acts[-1], fork, outs)
+        return self._finish_window(acts)
+
+
 def n_step_q_net_kwargs(np_, seed):
     """NStepQNetworkParameters -> the keywords of NStepQNet's constructor"""
     return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),

@@ -1,0 +1,46 @@
+"""Continuous-control Actor-Critic (A3C) for the device engine, with the hyper-parameters of
+rl_coach/presets/Mujoco_A3C.py: whole-episode update windows (num_steps_between_gradient_updates = 10000000), the
+accumulated gradients applied every episode, entropy regularisation 0.0001, lr 1e-5, rewards rescaled by 1/20, no
+heat-up, one evaluation episode every 20 episodes — and its golden test: an evaluation reward of 400 within 1000 episodes
+on inverted_pendulum with 8 workers (presets/Mujoco_A3C.py:43-49).  The exploration parameters are set explicitly:
+ContinuousEntropyParameters gives the policy head its standard-deviation stream (the reference picks them by the action
+space's type; the parameter objects here default to the discrete Categorical).  The reference preset also normalises
+observations with an input filter; the on-policy base's stepping applies reward filters only, so that filter is left
+out.  The MuJoCo level is replaced by the synthetic vector environment, as Mujoco_PPO runs here (HalfCheetah-like
+shapes: obs 17, act 6)."""
+from coach_amd.agents.actor_critic_agent import ActorCriticAgentParameters
+from coach_amd.base_parameters import PresetValidationParameters
+from coach_amd.core_types import EnvironmentEpisodes, EnvironmentSteps, TrainingSteps
+from coach_amd.environments.synthetic_vector_environment import SyntheticVectorEnvironmentParameters
+from coach_amd.exploration_policies.continuous_entropy import ContinuousEntropyParameters
+from coach_amd.filters.filter import InputFilter
+from coach_amd.filters.reward import RewardRescaleFilter
+from coach_amd.graph_managers.basic_rl_graph_manager import BasicRLGraphManager, ScheduleParameters
+
+
+def make(num_envs=1, obs_dim=17, action_dim=6, episode_length=1000, seed=1234, agent_seed=0):
+    agent = ActorCriticAgentParameters()
+    agent.seed = agent_seed
+    agent.exploration = ContinuousEntropyParameters()
+    agent.algorithm.apply_gradients_every_x_episodes = 1
+    agent.algorithm.num_steps_between_gradient_updates = 10000000
+    agent.algorithm.beta_entropy = 0.0001
+    agent.network_wrappers['main'].learning_rate = 0.00001
+    agent.input_filter = InputFilter()
+    agent.input_filter.add_reward_filter('rescale', RewardRescaleFilter(1 / 20.))
+    env = SyntheticVectorEnvironmentParameters("vector", num_envs, (obs_dim,), None, action_dim=action_dim,
+                                               episode_length=episode_length, seed=seed)
+    sched = ScheduleParameters()
+    sched.improve_steps = TrainingSteps(20000000)
+    sched.steps_between_evaluation_periods = EnvironmentEpisodes(20)
+    sched.evaluation_steps = EnvironmentEpisodes(1)
+    sched.heatup_steps = EnvironmentSteps(0)
+    validation = PresetValidationParameters(test=True, min_reward_threshold=400, max_episodes_to_achieve_reward=1000,
+                                            num_workers=8)
+    validation.reward_test_level = 'inverted_pendulum'
+    validation.trace_test_levels = ['inverted_pendulum', 'hopper']
+    return BasicRLGraphManager(agent_params=agent, env_params=env, schedule_params=sched,
+                               preset_validation_params=validation)
+
+
+graph_manager = make()

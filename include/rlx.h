@@ -1589,6 +1589,29 @@ int rlx_pg_episode_window(const float *rewards, int length, int start, double di
 int rlx_pg_head_loss(const float *logits, long long ld, const int *actions, const float *advantages, float beta_entropy,
                      int rows, int true_rows, int n_actions, float *dlogits, long long ld_dlogits, float *scalars,
                      int *status, void *stream);
+/* PolicyHead, continuous branch (Box action spaces: heads/policy_head.py:102-146; loss and entropy regularisation
+ * :75-87 over tf MultivariateNormalDiag) as one launch of one workgroup (csrc/gaussian_policy_head.hpp; entry points
+ * ADDED).  mean_pre [rows][ld_m] / std_pre [rows][ld_s] are the fc_mean / fc_std outputs; rows [true_rows, rows) are
+ * padding (zero gradient, no term); every mean divides by T = true_rows.  Per row, fp32, D = action_dim, sums over j in
+ * index order, exp / log / log1p / tanh taken in fp64 on the fp32 argument and rounded once:
+ *   mu_j = scale_j * tanh(m_j), or m_j when scale is NULL (an unbounded space, :107-114)
+ *   sigma_j = (max(s_j, 0) + log1p(exp(-|s_j|))) + eps (ContinuousEntropyParameters, :124-129), or std_j when std_pre
+ *             is NULL (the given policy_std, :137)
+ *   u_j = (a_j - mu_j) / sigma_j;  log pi = (-1/2 sum u_j^2 - sum log sigma_j) - D/2 log(2 pi);
+ *   H = D/2 (1 + log(2 pi)) + sum log sigma_j
+ * scalars[0] = loss = -(1/T) sum_b log pi_b adv_b - beta_entropy * scalars[1], scalars[1] = (1/T) sum_b H_b (thread
+ * partials in row order, then a fixed tree: no atomics); dmean_pre = dloss/dm, dstd_pre = dloss/ds (written, and
+ * needed, only with std_pre).  Columns [D, ld) of any buffer are neither read nor written.  The action_penalty
+ * regulariser (:148-152) is not built: neither agent's algorithm parameters carry one.  1 <= action_dim <= 32. */
+int rlx_pg_continuous_head_loss(const float *mean_pre, long long ld_m, const float *std_pre, long long ld_s,
+                                const float *std, const float *scale, const float *actions, const float *advantages,
+                                float beta_entropy, int rows, int true_rows, int action_dim, float *dmean_pre,
+                                long long ld_dm, float *dstd_pre, long long ld_ds, float *scalars, void *stream);
+/* The head's outputs (policy_head.py:116-131) for acting and predict: mean_out / std_out [n][action_dim] from the same
+ * functions the loss launches use, so both see the same bits. */
+int rlx_gaussian_policy_forward(const float *mean_pre, long long ld_m, const float *std_pre, long long ld_s,
+                                const float *std, const float *scale, int n, int action_dim, float *mean_out,
+                                float *std_out, void *stream);
 /* The 'Entropy' sample of PolicyOptimizationAgent.choose_action (policy_optimization_agent.py:154), per env, fp32:
  * -sum_j p_j * log(p_j + eps) on action probabilities [n_env][ld]. */
 int rlx_action_entropy(const float *probs, long long ld, int n_env, int n_actions, float *entropy_out, void *stream);
@@ -1626,6 +1649,22 @@ int rlx_a3c_window_loss(const float *V, long long ld_v, const float *logits, lon
                         float beta_entropy, float v_loss_weight, double *targets_out, double *advantages_out, float *dV,
                         long long ld_dv, float *dlogits, long long ld_dlogits, float *scalars, int *status,
                         void *stream);
+/* rlx_a3c_window_loss with the policy half replaced by the continuous PolicyHead (Box action spaces:
+ * architectures/tensorflow_components/heads/policy_head.py:102-146, its loss and entropy regularisation :75-87;
+ * entry point ADDED, no existing signature changed).  The targets, the advantages, the V head, RLX_A3C_TARGETS_GIVEN,
+ * the refusals and RLX_A3C_STATUS_NO_BOOTSTRAP_ROW are those of rlx_a3c_window_loss (one definition,
+ * csrc/a3c_targets.hpp); the policy half is rlx_pg_continuous_head_loss's row arithmetic (below) on mean_pre
+ * [rows][ld_m], std_pre [rows][ld_s] or NULL with std [D], scale [D] or NULL, actions fp32 [T][D], with the window's
+ * advantages rounded to fp32 once.  The bootstrap row has dV = 0, dmean_pre = 0, dstd_pre = 0 and no term; dstd_pre is
+ * written (and needed) only with std_pre.  scalars as rlx_a3c_window_loss.  1 <= action_dim <= 32. */
+int rlx_a3c_continuous_window_loss(const float *V, long long ld_v, const float *mean_pre, long long ld_m,
+                                   const float *std_pre, long long ld_s, const float *std, const float *scale,
+                                   const float *actions, const float *rewards, const unsigned char *game_over, int T,
+                                   int rows, int action_dim, double discount, double gae_lambda, int rescaler,
+                                   int estimate_state_value_using_gae, float beta_entropy, float v_loss_weight,
+                                   double *targets_out, double *advantages_out, float *dV, long long ld_dv,
+                                   float *dmean_pre, long long ld_dm, float *dstd_pre, long long ld_ds, float *scalars,
+                                   int *status, void *stream);
 
 /* ------------------------------------------------------------- N-step Q (added entry point) -- */
 /* NStepQAgent.learn_from_batch (agents/n_step_q_agent.py:99-140) between the forward and the backward pass of one update
