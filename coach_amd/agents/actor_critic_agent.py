@@ -15,7 +15,15 @@ stream and a softplus standard-deviation stream (ContinuousActorCriticNet) — a
 normals, stores float actions, and the window's launch is rlx_a3c_continuous_window_loss: the same targets, the Gaussian
 log-probability and entropy in place of the categorical ones.  No 'Entropy' sample is emitted there (the reference emits
 none).  Under any other exploration parameters a Box action space is refused.
+With `middleware_parameters = LSTMMiddlewareParameters(...)` the network is recurrent (nn/networks.py, csrc/lstm.hip) and
+the agent keeps two states per env, the A3C paper's handling: the ACTING state, which every acting step advances and which
+is zeroed when the env's episode starts, and `window_state`, the state a window's forward pass starts from -- the state
+the actor had before it consumed the window's first observation.  train() runs one acting step ahead of the stored
+transitions, so after a window that does not end the episode that is the network's "previous" state (the state before
+the newest acting step), copied at that moment; after one that ends the episode it is zeros.  Training never writes the
+acting state; TRAIN and TEST phases are handled alike.
 """
+import numpy as np
 import torch
 
 from .. import _rlx
@@ -41,6 +49,9 @@ class ActorCriticAlgorithmParameters(AlgorithmParameters):            # actor_cr
 
 
 class ActorCriticNetworkParameters(SchemeViews):         # actor_critic_agent.py:69-77 + NetworkParameters defaults
+    _LSTM_MIDDLEWARE = True
+    lstm_cells = None                # an instance field once middleware_parameters = LSTMMiddlewareParameters(...) set it
+
     def __init__(self):
         self.activation_function = 'relu'
         self.embedder_scheme = 'Medium'
@@ -79,6 +90,7 @@ _RESCALERS = (PolicyGradientRescaler.A_VALUE, PolicyGradientRescaler.GAE)
 class ActorCriticAgent(PolicyOptimizationAgent):
     SIGNAL_NAMES = PolicyOptimizationAgent.SIGNAL_NAMES + ["Advantages", "Values", "Value Loss", "Policy Loss"]  # :98-101
     BOX_EXPLORATION = ContinuousEntropyParameters
+    LSTM_MIDDLEWARE = True
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         rescaler = agent_parameters.algorithm.policy_gradient_rescaler
@@ -93,6 +105,10 @@ class ActorCriticAgent(PolicyOptimizationAgent):
         self.advantages = torch.zeros(L, dtype=torch.float64, device=dev)        # action_advantages of the window
         self.returns = torch.zeros(L, dtype=torch.float64, device=dev)           # a finished episode's discounted returns
         self.debug_targets = None        # tests set this to a list: (V, value targets, advantages) clones per window
+        lstm = self.networks["main"].lstm
+        # (c, h) [n_env, cells]: the state every env's NEXT update window starts from; None for a feed-forward network
+        self.window_state = None if lstm is None else tuple(
+            torch.zeros(self.n_env, lstm.H, dtype=torch.float32, device=dev) for _ in range(2))
 
     def _make_network(self, obs_shape, wrapper):
         kw = actor_critic_net_kwargs(wrapper, self.ap.algorithm, self.ap.seed or 0)
@@ -110,9 +126,17 @@ class ActorCriticAgent(PolicyOptimizationAgent):
         rows, last_next_state, game_over = self.memory.bootstrap_rows(env, start, end, complete)
         if rows is None:                                 # the reset overwrote the state behind a finished episode
             rows = net.stage_rows(obs, last_next_state)
+        ws = self.window_state
         loss = net.accumulate_window(rows, T, True, actions, self.value_targets, self.advantages, rewards[start:end],
                                      game_over, alg.discount, alg.gae_lambda, self.policy_gradient_rescaler.value,
-                                     alg.estimate_state_value_using_gae)
+                                     alg.estimate_state_value_using_gae,
+                                     initial_state=None if ws is None else tuple(s[env:env + 1] for s in ws))
+        if ws is not None:               # the next window's start: the state before the newest acting step, or a new episode's
+            for s, before in zip(ws, net.acting_state(self.n_env)[1]):
+                if complete:
+                    s[env].zero_()
+                else:
+                    s[env].copy_(before[env])
         self.signals = {"Loss": net.loss, "Grads (unclipped)": net.norm, "Values": net.values[:T],
                         "Advantages": self.advantages[:T], "Value Loss": net.value_loss, "Policy Loss": net.policy_loss}
         if complete:                                     # handle_episode_ended: a sample per transition (agent.py:569-570)
@@ -123,6 +147,28 @@ class ActorCriticAgent(PolicyOptimizationAgent):
             self.debug_targets.append((net.values[:T + 1].clone(), self.value_targets[:T].clone(),
                                        self.advantages[:T].clone(), game_over.clone()))
         return loss
+
+    def handle_episode_ended(self):
+        """an env whose episode just ended acts on its next observation from a zero state (every phase)"""
+        super().handle_episode_ended()
+        if getattr(self, "window_state", None) is not None:
+            self.networks["main"].reset_state(np.nonzero(self._episode_steps == 0)[0].tolist())
+
+    def _zero_recurrent_state(self):
+        if getattr(self, "window_state", None) is not None:
+            self.networks["main"].reset_state()
+            for s in self.window_state:
+                s.zero_()
+
+    def reset_internal_state(self):
+        self._zero_recurrent_state()
+        return super().reset_internal_state()
+
+    def evaluate_episodes(self, episodes_per_env=1):
+        try:
+            return super().evaluate_episodes(episodes_per_env)
+        finally:                         # training resumes on fresh episodes
+            self._zero_recurrent_state()
 
     def check_status(self):
         super().check_status()

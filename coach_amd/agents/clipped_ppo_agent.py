@@ -30,6 +30,7 @@ from ..nn.networks import ClippedPPONet
 from ..schedules import ConstantSchedule
 
 
+from ..architectures.middleware_parameters import refuse_lstm_middleware
 from ..architectures.scheme_views import SchemeViews
 
 
@@ -115,6 +116,7 @@ class ClippedPPOAgent(object):
 
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         self.ap = agent_parameters
+        refuse_lstm_middleware(agent_parameters, type(self).__name__)
         self.env = environment
         self.device = device or environment.device
         self.dist = dist if (dist is not None and dist.enabled) else None

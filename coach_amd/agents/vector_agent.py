@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _rlx
+from ..architectures.middleware_parameters import refuse_lstm_middleware
 from ..core_types import EnvironmentEpisodes, EnvironmentSteps, RunPhase, TrainingSteps
 
 
@@ -251,8 +252,12 @@ class VectorOffPolicyAgent(GraphRunner):
     SIGNAL_NAMES = ["Loss", "Learning Rate", "Grads (unclipped)", "Discounted Return"]
     signal_stats = None              # DeviceSignals once enable_signal_statistics() is called (CSV logging)
 
+    LSTM_MIDDLEWARE = False          # ActorCriticAgent alone serves LSTMMiddlewareParameters
+
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         self.ap = agent_parameters
+        if not self.LSTM_MIDDLEWARE:
+            refuse_lstm_middleware(agent_parameters, type(self).__name__)
         self.noise_source = self._resolve_noise_source()          # (checked before anything touches the device)
         self.env = environment
         self.device = device or environment.device

@@ -715,6 +715,9 @@ class ActorCriticArchitecture(HipArchitecture):
     accumulate_gradients -> total loss, [value loss, policy loss, the entropy regulariser], the gradients' norm."""
 
     def _build(self, agent_parameters, spaces, np_, seed):
+        if getattr(np_, "lstm_cells", None) is not None:
+            raise ValueError("LSTMMiddlewareParameters: the backend interface (ActorCriticArchitecture) has no recurrent "
+                             "state to feed; the LSTM middleware runs under ActorCriticAgent")
         A = _discrete_actions(spaces, "the continuous PolicyHead (a Box action space) is not served: the actor-critic "
                                       "network has the discrete head only")
         return ActorCriticNet(self.device, _obs_shape(spaces), A,

@@ -49,6 +49,21 @@ class _SchemeView(object):
                 self._owner.batchnorm = bool(value)
 
 
+class _EmbedderViews(dict):
+    """what `input_embedders_parameters` returns: `[...] = InputEmbedderParameters(...)` on it reaches the owner's
+    setter (reference presets replace single entries that way), reading gives the live views"""
+
+    def __init__(self, owner, views):
+        super().__init__(views)
+        self._owner = owner
+
+    def __setitem__(self, key, record):
+        entries = {k: (record if k == key else v) for k, v in self.items()}
+        entries.setdefault(key, record)
+        self._owner.input_embedders_parameters = entries
+        super().__setitem__(key, self._owner.input_embedders_parameters[key])
+
+
 class SchemeViews(object):
     """Mix into a network-parameters class.  _EMBEDDER_FIELDS: {'observation': field[, 'action': field]};
     _TUPLE_SCHEMES: the fields hold tuples of unit counts (actor-critic nets) instead of names / lists."""
@@ -61,9 +76,9 @@ class SchemeViews(object):
         names = self.__dict__.get("input_embedder_names")
         if names is not None:            # several Empty vector embedders over one concatenated observation (see the setter)
             field = self._EMBEDDER_FIELDS["observation"]
-            return {k: _SchemeView(self, field, self._TUPLE_SCHEMES) for k in names}
-        return {k: _SchemeView(self, f, self._TUPLE_SCHEMES) for k, f in self._EMBEDDER_FIELDS.items()
-                if hasattr(self, f)}
+            return _EmbedderViews(self, {k: _SchemeView(self, field, self._TUPLE_SCHEMES) for k in names})
+        return _EmbedderViews(self, {k: _SchemeView(self, f, self._TUPLE_SCHEMES)
+                                     for k, f in self._EMBEDDER_FIELDS.items() if hasattr(self, f)})
 
     @input_embedders_parameters.setter
     def input_embedders_parameters(self, value):
@@ -90,6 +105,30 @@ class SchemeViews(object):
         setattr(self, fields["observation"], scheme_to_native(next(iter(value.values())).scheme, self._TUPLE_SCHEMES))
         self.__dict__["input_embedder_names"] = tuple(sorted(value))
 
+    _LSTM_MIDDLEWARE = False         # the class's networks can be built with an LSTM cell (ActorCriticNetworkParameters)
+
     @property
     def middleware_parameters(self):
         return _SchemeView(self, self._MIDDLEWARE_FIELD, self._TUPLE_SCHEMES)
+
+    @middleware_parameters.setter
+    def middleware_parameters(self, record):
+        """`middleware_parameters = FCMiddlewareParameters(...) / LSTMMiddlewareParameters(...)` of a preset text: the
+        record's scheme and activation go to the flat fields, as through the view; an LSTM record also sets the flat
+        `lstm_cells`.  Refused by name: an LSTM record on a class whose networks have no recurrent form, and batchnorm
+        or dropout on an LSTM record (neither is built around the cell)."""
+        from .middleware_parameters import LSTMMiddlewareParameters
+        lstm = isinstance(record, LSTMMiddlewareParameters)
+        if lstm and not self._LSTM_MIDDLEWARE:
+            raise ValueError("LSTMMiddlewareParameters: the LSTM middleware is served under the Actor-Critic agent "
+                             "only, not under %s" % type(self).__name__)
+        if lstm and record.batchnorm:
+            raise ValueError("LSTMMiddlewareParameters(batchnorm=True) is not served")
+        if lstm and record.dropout_rate:
+            raise ValueError("LSTMMiddlewareParameters(dropout_rate=%r) is not served" % (record.dropout_rate,))
+        view = self.middleware_parameters
+        view.scheme = record.scheme
+        view.activation_function = record.activation_function
+        self.__dict__.pop("lstm_cells", None)
+        if lstm:
+            self.lstm_cells = int(record.number_of_lstm_cells)

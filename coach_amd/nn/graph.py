@@ -650,6 +650,77 @@ class NoisyDense(Layer):
             x.grad_is_dz = lower is not None
 
 
+class LSTM(Layer):
+    """LSTMMiddleware's cell (tensorflow_components/middlewares/lstm_middleware.py:58-80): tf BasicLSTMCell(cells,
+    state_is_tuple=True, forget_bias=1) over S independent sequences of T rows each (row s * T + t).  csrc/lstm.hip.
+
+    One kernel [in_features + cells, 4 * cells] (input rows first, gate blocks i, j, f, o), Glorot-uniform over the whole
+    matrix, and a zero bias, under `name`/kernel and `name`/bias.  A pass is three launches: the input projection of all
+    rows (rlx_gemm on the kernel's first in_features rows, a contiguous block), the recurrence (rlx_lstm_forward), and in
+    the backward pass rlx_lstm_backward followed by the two products every dense layer has, on [x | h_{t-1}] and dGates."""
+
+    def __init__(self, params, name, in_features, cells):
+        if cells % 16 or not 16 <= cells <= 256:
+            raise ValueError("LSTM: cells = %r is not served by csrc/lstm.hip (a multiple of 16 in [16, 256])" % (cells,))
+        self.name, self.K, self.H, self.N, self.act, self.T, self.params = name, in_features, cells, cells, None, 1, params
+        self.kname, self.bname = name + "/kernel", name + "/bias"
+        params.add_group([(self.kname, (in_features + cells, 4 * cells)), (self.bname, (4 * cells,))], 1)
+
+    def initialize(self, rng):
+        shape = (self.K + self.H, 4 * self.H)
+        self.params.w(self.kname).copy_(torch.from_numpy(xavier_uniform(rng, shape[0], shape[1], shape)))
+
+    def forward(self, ctx, x, tag="", weights=None, t0=0, nt=None, seq=None, state=None, final=None, previous=None,
+                save=True):
+        """seq = (S, T) with S * T = x.rows; state = (c0, h0) [S, cells] or None (zeros); final = (c, h) receives the state
+        after the last step (default: buffers of the context; may BE `state`, which then advances in place);
+        previous = (c, h) receives `state` as it was before the launch.  save=False (acting): nothing is kept for backward().
+        -> Tensor of h_t [1, S * T, cells]; .lstm carries what backward() reads and .lstm["final"]."""
+        self._range(t0, nt)
+        S, T = seq if seq is not None else (x.rows, 1)
+        if T < 1 or S < 1 or S * T != x.rows:
+            raise ValueError("%s: seq = (S = %d, T = %d) does not describe %d rows" % (self.name, S, T, x.rows))
+        assert x.towers in (0, 1) and x.cols == self.K and not x.u8, (self.name, x.towers, x.cols, self.K)
+        p, M, H, K = self.params, x.rows, self.H, self.K
+        kernel, bias = p.w(self.kname, 0, weights), p.w(self.bname, 0, weights)
+        gx = ctx.buffer(self.name + "/gx", (M, 4 * H), tag=tag)
+        _rlx.gemm(M, 4 * H, K, x.data, kernel, gx, bias=bias, workspace=ctx.ws.splitk)
+        y = ctx.buffer(self.name, (1, M, H), tag=tag)
+        if final is None:
+            final = (ctx.buffer(self.name + "/c_final", (S, H), tag=tag), ctx.buffer(self.name + "/h_final", (S, H), tag=tag))
+        c0, h0 = state if state is not None else (None, None)
+        pc, ph = previous if previous is not None else (None, None)
+        gates = cs = xh = None
+        if save:
+            gates, cs = ctx.buffer(self.name + "/gates", (M, 4 * H), tag=tag), ctx.buffer(self.name + "/c", (M, H), tag=tag)
+            xh = ctx.buffer(self.name + "/xh", (M, K + H), tag=tag)
+        ctx.lib.lstm_forward(x.data if save else None, K, gx, 4 * H, kernel[K:], 4 * H, c0, h0, y, H, gates, cs, xh, K + H, K,
+                             final[0], final[1], pc, ph, S, T, H, ctx.stream)
+        out = Tensor(y, M, H, 1, grad_key=(ctx, self.name, tag), act=None)
+        out.lstm = dict(seq=(S, T), c0=c0, gates=gates, c=cs, xh=xh, final=final, tag=tag)
+        return out
+
+    def backward(self, ctx, x, y, need_dx=True, weights=None, t0=0, nt=None, need_dw=True, overlap=False):
+        """y.grad holds dL/dh_t of every row; writes the kernel and bias gradients and (optionally) x.grad, which carries
+        the lower layer's activation derivative like Dense.backward's."""
+        saved = y.lstm
+        if saved["gates"] is None:
+            raise ValueError("%s: backward through a pass that ran with save=False" % self.name)
+        (S, T), p, M, H, K = saved["seq"], self.params, x.rows, self.H, self.K
+        kernel = p.w(self.kname, 0, weights)
+        dg = ctx.buffer(self.name + "/dgates", (M, 4 * H), tag=saved["tag"])
+        ctx.lib.lstm_backward(y.grad, H, saved["gates"], saved["c"], saved["c0"], kernel[K:], 4 * H, dg, S, T, H, ctx.stream)
+        if need_dw:            # dKernel = [x | h_{t-1}]^T dGates (both row blocks at once), dBias = its column sums
+            _rlx.gemm(K + H, 4 * H, M, saved["xh"], dg, p.g(self.kname), a_strides=(1, K + H), workspace=ctx.ws.splitk,
+                      colsum_out=p.g(self.bname))
+        if need_dx:            # dx = dGates kernel[0:K]^T: only the input rows of the kernel, no columns to throw away
+            assert x.towers == 1, "input gradients need a per-tower input"
+            lower = x.act if x.act in FUSED_ACTS else None
+            _rlx.gemm(M, K, 4 * H, dg, kernel, x.ensure_grad(), b_strides=(1, 4 * H), workspace=ctx.ws.splitk,
+                      deriv_aux=x.data if lower else None, aux_ld=K, deriv_kind=lower)
+            x.grad_is_dz = lower is not None
+
+
 class BatchNorm(Layer):
     """tf.layers.batch_normalization(x, training=is_training) + the activation, after a Dense layer built without one
     (BatchnormActivationDropout, tensorflow_components/layers.py:26-55, 138-152): momentum 0.99, epsilon 1e-3, gamma / beta

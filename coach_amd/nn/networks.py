@@ -70,17 +70,66 @@ class _NetBase:
         return G.input_tensor(obs, B, int(self.obs_shape[0]))
 
     # ---- the single-tower networks: one embedder + FC middleware trunk under one or more Dense heads -------------
-    def _build_trunk(self, obs_shape, activation, embedder, middleware):
+    lstm = None           # the LSTM middleware's cell behind the torso (G.LSTM), where the network was built with lstm_cells
+
+    def _build_trunk(self, obs_shape, activation, embedder, middleware, lstm_cells=None):
         """the constructor's prologue: the observation's shape, the flat parameters and the one-tower torso -> the width
-        of the torso's output, which the heads read"""
+        of the trunk's output, which the heads read.  lstm_cells: LSTMMiddleware (middlewares/lstm_middleware.py) -- the
+        middleware scheme's dense layers, then one LSTM cell of that width, whose h_t the heads read."""
         self.obs_shape, self.image = tuple(obs_shape), len(obs_shape) == 3
         self.params = G.FlatParams()
         self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware)
+        if lstm_cells is not None:
+            if self.image:
+                raise NotImplementedError("lstm_cells: the LSTM middleware is not built for image observations")
+            self.lstm = G.LSTM(self.params, "main/middleware/lstm", feat, int(lstm_cells))
+            self._lstm_states = {}
+            feat = self.lstm.H
         return feat
 
-    def trunk_forward(self, obs, B, tag, weights=None):
-        """the torso on obs -> its activations; the heads read the last one"""
-        return self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=weights)
+    def _trunk_modules(self):
+        """the trunk's part of `modules`, in the order the parameters were declared (the initialiser's draw order)"""
+        return [self.torso] + ([self.lstm] if self.lstm is not None else [])
+
+    def acting_state(self, n_env):
+        """-> ((c, h), (previous c, previous h)), each [n_env, cells]: the recurrent state the acting steps of n_env
+        environments advance in place, and that state as it was before the newest acting step"""
+        if n_env not in self._lstm_states:
+            z = lambda: torch.zeros(n_env, self.lstm.H, dtype=torch.float32, device=self.device)
+            self._lstm_states[n_env] = ((z(), z()), (z(), z()))
+        return self._lstm_states[n_env]
+
+    def reset_state(self, envs=None):
+        """zero the acting state of the given environments (None: all of them)"""
+        for (c, h), _ in self._lstm_states.values():
+            rows = slice(None) if envs is None else envs
+            c[rows] = 0.0
+            h[rows] = 0.0
+
+    def trunk_forward(self, obs, B, tag, weights=None, seq=None, initial_state=None):
+        """the torso on obs -> its activations; the heads read the last one.  A recurrent trunk: with seq = (S, T) the
+        rows are S sequences of T steps that start from initial_state = (c0, h0) (None: zeros) and everything the
+        backward pass needs is kept; without seq the B rows are ONE acting step of B environments, which advances
+        acting_state(B) in place and leaves the state it started from in its `previous` pair."""
+        acts = self.torso.forward(self.ctx, self.obs_tensor(obs, B), tag=tag, weights=weights)
+        if self.lstm is None:
+            if initial_state is not None:
+                raise ValueError("initial_state: this network has no LSTM middleware (lstm_cells)")
+            return acts
+        if seq is None:
+            state, previous = self.acting_state(B)
+            y = self.lstm.forward(self.ctx, acts[-1], tag=tag, weights=weights, seq=(B, 1), state=state, final=state,
+                                  previous=previous, save=False)
+        else:
+            y = self.lstm.forward(self.ctx, acts[-1], tag=tag, weights=weights, seq=seq, state=initial_state)
+        return acts + [y]
+
+    def trunk_backward(self, acts):
+        """the backward pass of trunk_forward(seq=...)'s activations, the heads' gradient in acts[-1].grad"""
+        if self.lstm is not None:
+            self.lstm.backward(self.ctx, acts[-2], acts[-1], need_dx=len(self.torso.layers) > 0)
+            acts = acts[:-1]
+        self.torso.backward(self.ctx, acts)
 
     def _fork(self, feat, heads, tag):
         """a training pass's [(head layer, the Tensor it reads)]: the first head reads feat, every other head a Tensor
@@ -1345,7 +1394,7 @@ class _WindowAccumulatingNet(_NetBase):
     def _finish_window(self, acts):
         """the tail of window_gradients behind the heads' backward pass: the torso backward, then the gradients clipped
         by their global norm or the norm alone (self.norm either way) -> the window's loss"""
-        self.torso.backward(self.ctx, acts)
+        self.trunk_backward(acts)
         if not self.clip_by_global_norm():
             self.grad_norm()
         return self.loss
@@ -1421,7 +1470,8 @@ class PolicyGradientNet(_WindowAccumulatingNet):
 def actor_critic_net_kwargs(np_, alg, seed):
     """ActorCriticNetworkParameters + the algorithm's beta_entropy -> the keywords of ActorCriticNet's constructor"""
     heads = {h.head_type: h for h in np_.heads_parameters}
-    return dict(policy_gradient_net_kwargs(np_, alg, seed), v_loss_weight=heads["VHead"].loss_weight)
+    return dict(policy_gradient_net_kwargs(np_, alg, seed), v_loss_weight=heads["VHead"].loss_weight,
+                lstm_cells=getattr(np_, "lstm_cells", None))
 
 
 class ActorCriticNet(_WindowAccumulatingNet):
@@ -1434,40 +1484,46 @@ class ActorCriticNet(_WindowAccumulatingNet):
 
     def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium", middleware="Medium",
                  learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=40.0,
-                 beta_entropy=0.0, v_loss_weight=0.5, seed=0):
+                 beta_entropy=0.0, v_loss_weight=0.5, seed=0, lstm_cells=None):
         self.A = discrete_policy_actions(n_actions)
         self.clip_gradients = clip_gradients
         self.beta_entropy, self.v_loss_weight = float(beta_entropy), float(v_loss_weight)
-        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware, lstm_cells)
         self.v_head = G.Dense(self.params, "main/v_values_head/output", feat, 1, None, 1, init=G.normalized_columns(1.0))
         self.pi_head = G.Dense(self.params, "main/policy_values_head/fc", feat, self.A, None, 1)
         self.heads = [self.v_head, self.pi_head]
-        self.modules = [self.torso] + self.heads
+        self.modules = self._trunk_modules() + self.heads
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
         # total loss, value loss, policy loss, mean entropy of the last window
         self._finish_accumulating(("loss", "value_loss", "policy_loss", "entropy"))
 
     def policy_values(self, obs, B, tag="act"):
-        """the policy head's Dense output [B, A] (logits of the action probabilities); the V head is not run"""
+        """the policy head's Dense output [B, A] (logits of the action probabilities); the V head is not run.
+        A recurrent network (lstm_cells): this IS one acting step of B environments -- every call, predict's too,
+        advances acting_state(B); call one of the two once per observation."""
         return self.pi_head.forward(self.ctx, self.trunk_forward(obs, B, tag)[-1], tag=tag)
 
     def predict(self, obs, B, tag="predict"):
-        """both heads -> (V [B], logits [B, A]) as buffers"""
+        """both heads -> (V [B], logits [B, A]) as buffers.  A recurrent network: one acting step, as policy_values"""
         feat = self.trunk_forward(obs, B, tag)[-1]
         v, z = self._heads_forward([(l, feat) for l in self.heads], tag)
         return v.data.view(B), z.data.view(B, self.A)
 
     def window_gradients(self, obs_rows, T, bootstrap, actions, targets, advantages, rewards=None, game_over=None,
-                         discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False):
+                         discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False,
+                         initial_state=None):
         """forward on the T states of one update window and, with bootstrap, on the last next state behind them (obs_rows
         has T + bootstrap rows); rlx_a3c_window_loss against (actions, rewards, the device's game-over flag), which
         leaves the fp64 value targets and advantages in targets / advantages [T] — or, with the default rescaler, reads
         them from there; both heads backward, their input gradients summed; the torso backward: the gradients in
         params.grads (clipped when clip_gradients is set), the four scalars in self.scalars, tf.global_norm of the raw
-        gradients in self.norm.  The context's buffers are keyed by shape; the means divide by T."""
+        gradients in self.norm.  The context's buffers are keyed by shape; the means divide by T.
+        A recurrent network (lstm_cells): the rows are ONE sequence that starts from initial_state = (c0, h0) [1, cells]
+        (None: zeros), a constant; the bootstrap row is its last step and gets a zero head gradient from the loss launch,
+        so back-propagation through time starts there with zero.  The acting state is not touched."""
         ctx, A = self.ctx, self.A
         rows = T + int(bool(bootstrap))
-        acts = self.trunk_forward(obs_rows, rows, "train")
+        acts = self.trunk_forward(obs_rows, rows, "train", seq=(1, rows), initial_state=initial_state)
         fork = self._fork(acts[-1], self.heads, "train")
         v, z = outs = self._heads_forward(fork, "train")
         self.values = v.data.view(rows)                  # the 'Values' samples are its first T entries
@@ -1526,7 +1582,8 @@ class _GaussianPolicyStreams:
         return mean, std
 
     def policy_values(self, obs, B, tag="act"):
-        """(mean, std) [B, D] of the policy on obs; a V head is not run"""
+        """(mean, std) [B, D] of the policy on obs; a V head is not run.  A recurrent network (lstm_cells): every call
+        is one acting step of B environments and advances acting_state(B)"""
         feat = self.trunk_forward(obs, B, tag)[-1]
         return self._mean_std(self._heads_forward([(l, feat) for l in self.policy_heads], tag), B, tag)
 
@@ -1566,29 +1623,32 @@ class ContinuousActorCriticNet(_GaussianPolicyStreams, ActorCriticNet):
 
     def __init__(self, device, obs_shape, action_dim, output_scale=None, learned_std=True, activation="relu",
                  embedder="Medium", middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99,
-                 optimizer_epsilon=1e-4, clip_gradients=40.0, beta_entropy=0.0, v_loss_weight=0.5, seed=0):
+                 optimizer_epsilon=1e-4, clip_gradients=40.0, beta_entropy=0.0, v_loss_weight=0.5, seed=0,
+                 lstm_cells=None):
         self.clip_gradients = clip_gradients
         self.beta_entropy, self.v_loss_weight = float(beta_entropy), float(v_loss_weight)
-        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware, lstm_cells)
         self.v_head = G.Dense(self.params, "main/v_values_head/output", feat, 1, None, 1, init=G.normalized_columns(1.0))
         self._build_policy_streams(feat, action_dim, learned_std)
         self.heads = [self.v_head] + self.policy_heads
-        self.modules = [self.torso] + self.heads
+        self.modules = self._trunk_modules() + self.heads
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
         self._finish_policy_streams(output_scale)
         self._finish_accumulating(("loss", "value_loss", "policy_loss", "entropy"))
 
     def predict(self, obs, B, tag="predict"):
-        """every head -> (V [B], mean [B, D], std [B, D]) as buffers"""
+        """every head -> (V [B], mean [B, D], std [B, D]) as buffers.  A recurrent network: one acting step, as
+        policy_values"""
         feat = self.trunk_forward(obs, B, tag)[-1]
         outs = self._heads_forward([(l, feat) for l in self.heads], tag)
         return (outs[0].data.view(B),) + self._mean_std(outs[1:], B, tag)
 
     def window_gradients(self, obs_rows, T, bootstrap, actions, targets, advantages, rewards=None, game_over=None,
-                         discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False):
+                         discount=0.0, gae_lambda=0.0, rescaler=_rlx.A3C_TARGETS_GIVEN, estimate_with_gae=False,
+                         initial_state=None):
         """ActorCriticNet.window_gradients with float actions [T, D]"""
         rows = T + int(bool(bootstrap))
-        acts = self.trunk_forward(obs_rows, rows, "train")
+        acts = self.trunk_forward(obs_rows, rows, "train", seq=(1, rows), initial_state=initial_state)
         fork = self._fork(acts[-1], self.heads, "train")
         outs = self._heads_forward(fork, "train")
         v = outs[0]

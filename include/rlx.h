@@ -1969,6 +1969,38 @@ int rlx_bcq_imitation_selector(const float *q_next_online, long long ld_q, const
                                unsigned int rank, const long long *event, float *sel_out, long long ld_sel,
                                float *familiarity_out, long long ld_f, int *zero_rows_out, void *stream);
 
+/* ------------------------------------------------------- LSTM middleware: recurrence and BPTT (csrc/lstm.hip) -- */
+/* LSTMMiddleware (architectures/tensorflow_components/middlewares/lstm_middleware.py:58-80): tf BasicLSTMCell(cells,
+ * state_is_tuple=True).  One kernel matrix [input_features + cells][4 * cells] (rows 0 .. input_features-1 multiply the
+ * input, the `recurrent` block below them multiplies h_{t-1}), one bias [4 * cells], gate column blocks i, j, f, o:
+ *   c_t = c_{t-1} * sigmoid(f + 1) + sigmoid(i) * tanh(j),   h_t = tanh(c_t) * sigmoid(o),   all fp32
+ * (sigmoid and tanh: csrc/lstm_math.hpp, the same two functions in both launches).  Entry points ADDED under ABI version
+ * 11.  S independent sequences of T steps, row s * T + t: a training window is S = 1, an acting step is T = 1.
+ * cells: a multiple of 16 in [16, 256]; anything else, T < 1 or S < 1 is RLX_ERR_INVALID_ARG naming the argument (never
+ * padded).  One workgroup per 16 sequences, cells / 16 waves; fixed summation orders: two launches give the same bits.
+ *
+ * rlx_lstm_forward: gx [S * T][ld_gx] = X kernel[0:input_features] + bias (an rlx_gemm of all rows), recurrent =
+ * kernel + input_features * ld_w.  c0, h0 [S][cells]: the state in front of the first step (both NULL: zeros).
+ * Writes h_out [S * T][ld_h] (the layer's output), c_final / h_final [S][cells] (may be c0 / h0: the state advances in
+ * place) and, where not NULL: gates [S * T][4 * cells] (ACTIVATED i, j, f, o) and c_out [S * T][cells] for
+ * rlx_lstm_backward (together); xh [S * T][ld_xh] = [x | h_{t-1}], the operand of the weight gradient (needs x);
+ * c_previous / h_previous [S][cells] = c0 / h0 as they were before the launch (together; must not overlap the state): an
+ * acting step captured in a graph keeps the state it started from without exchanging pointers.
+ * gx and recurrent 16-byte aligned, ld_gx and ld_w multiples of 4. */
+int rlx_lstm_forward(const float *x, long long ld_x, const float *gx, long long ld_gx, const float *recurrent,
+                     long long ld_w, const float *c0, const float *h0, float *h_out, long long ld_h, float *gates,
+                     float *c_out, float *xh, long long ld_xh, int input_features, float *c_final, float *h_final,
+                     float *c_previous, float *h_previous, int S, int T, int cells, void *stream);
+/* Back-propagation through time of the same windows, t = T-1 .. 0, from dh_out [S * T][ld_dh] = dL/dh_t of every row:
+ *   dh = dh_out[t] + dh_carry;  tc = tanh(c_t);  dc = dc_carry + dh * o * (1 - tc * tc);  dc_carry = dc * f
+ *   dgates[t] = [dc * j * i (1 - i) | dc * i * (1 - j * j) | dc * c_{t-1} * f (1 - f) | dh * tc * o (1 - o)]
+ *   dh_carry = dgates[t] recurrent^T
+ * dgates [S * T][4 * cells] is the gradient at the gate PRE-activations: kernel gradient = xh^T dgates, bias gradient its
+ * column sums, input gradient dgates kernel[0:input_features]^T (rlx_gemm).  c0 as given to the forward launch (NULL:
+ * zeros); the carried state is a constant, it gets no gradient. */
+int rlx_lstm_backward(const float *dh_out, long long ld_dh, const float *gates, const float *c, const float *c0,
+                      const float *recurrent, long long ld_w, float *dgates, int S, int T, int cells, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
