@@ -148,3 +148,14 @@ class MeasurementsPredictionHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='measurements_prediction_head_params',
                  rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class DNDQHeadParameters(HeadParameters):
+    """DNDQHeadParameters (head_parameters.py:88-95): no trainable parameters — Q[b, a] is the inverse-distance weighted
+    mean of the values of the k nearest keys of action a's table (heads/dnd_q_head.py:67-83).  The tables and every launch
+    on them belong to memories.non_episodic.differentiable_neural_dictionary.QDND (csrc/dnd.hip)."""
+    head_type = "DNDQHead"
+
+    def __init__(self, activation_function='relu', name='dnd_q_head_params', rescale_gradient_from_head_by_factor=1.0,
+                 loss_weight=1.0):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)

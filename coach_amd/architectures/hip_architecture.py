@@ -1037,8 +1037,11 @@ _BY_PARAMETER_CLASS = {"PolicyGradientNetworkParameters": PolicyGradientArchitec
 def _family_of(network_parameters):
     """The family is decided by the class of `agent_parameters.network_wrappers[name]`, as
     GeneralTensorFlowNetwork decides by the head parameter classes it is given."""
-    from .head_parameters import ClassificationHeadParameters
+    from .head_parameters import ClassificationHeadParameters, DNDQHeadParameters
     heads = list(getattr(network_parameters, "heads_parameters", ()) or ())
+    if any(isinstance(h, DNDQHeadParameters) for h in heads):
+        raise NotImplementedError("the backend interface does not serve a DNDQHead: its dictionary is written by the agent "
+                                  "(coach_amd.agents.nec_agent.NECAgent drives coach_amd.nn.networks.NECNet)")
     if len(heads) == 1 and isinstance(heads[0], ClassificationHeadParameters):
         return ClassificationArchitecture               # a wrapper of any class under a ClassificationHead
     for cls in type(network_parameters).__mro__:

@@ -401,6 +401,26 @@ __global__ void episode_nstep_returns_kernel(const float *__restrict__ rewards, 
     if (out) out[row(t)] = acc;
     if (compact) compact[t] = acc;
 }
+
+// The same column with Episode.update_discounted_rewards' bootstrap (core_types.py:793-798,
+// bootstrap_total_return_from_old_policy): + discount^n * max_action_value[t + n], nothing where t + n is past the end.
+// discount^n is the reference's running product (current_discount *= discount, n - 1 times), the sum is fp64.
+__global__ void episode_nstep_returns_bootstrapped_kernel(const float *__restrict__ rewards,
+                                                          const float *__restrict__ max_action_value,
+                                                          double *__restrict__ out, double *__restrict__ compact,
+                                                          long long s0, int T, int env, int n_env, long long ring_steps,
+                                                          double discount, int n_step) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    const int n = (n_step == -1 || n_step > T) ? T : n_step;
+    auto row = [&](int k) { return ((s0 + k) % ring_steps) * n_env + env; };
+    double acc = rlx::episode_nstep_return(rewards, t, T, n, discount, row);
+    double current_discount = discount;
+    for (int i = 1; i < n; ++i) current_discount *= discount;
+    if (t + n < T) acc = acc + current_discount * (double)max_action_value[row(t + n)];
+    if (out) out[row(t)] = acc;
+    if (compact) compact[t] = acc;
+}
 }  // namespace
 
 extern "C" {
@@ -464,6 +484,20 @@ int rlx_episode_nstep_returns(const float *rewards, double *out, double *compact
     RLX_REQUIRE(n_step == -1 || n_step >= 1,
                 "n-step should be an integer with value >= 1, or set to -1 for always setting to episode length.");
     RLX_LAUNCH((episode_nstep_returns_kernel), (length + 255) / 256, 256, 0, rlx::as_stream(stream), rewards, out, compact_out, first_step, length, env, n_env, ring_steps, discount, n_step);
+    RLX_LAUNCH_CHECK();
+    return RLX_OK;
+}
+
+int rlx_episode_nstep_returns_bootstrapped(const float *rewards, const float *max_action_value, double *out,
+                                           double *compact_out, long long first_step, int length, int env, int n_env,
+                                           long long ring_steps, double discount, int n_step, void *stream) {
+    RLX_REQUIRE(rewards && max_action_value && (out || compact_out), "rlx_episode_nstep_returns_bootstrapped: null pointer");
+    RLX_REQUIRE(length > 0 && n_env > 0 && env >= 0 && env < n_env && ring_steps >= length && first_step >= 0,
+                "rlx_episode_nstep_returns_bootstrapped: bad episode geometry (length=%d ring_steps=%lld)", length, ring_steps);
+    RLX_REQUIRE(n_step == -1 || n_step >= 1,
+                "n-step should be an integer with value >= 1, or set to -1 for always setting to episode length.");
+    RLX_LAUNCH((episode_nstep_returns_bootstrapped_kernel), (length + 255) / 256, 256, 0, rlx::as_stream(stream), rewards,
+               max_action_value, out, compact_out, first_step, length, env, n_env, ring_steps, discount, n_step);
     RLX_LAUNCH_CHECK();
     return RLX_OK;
 }

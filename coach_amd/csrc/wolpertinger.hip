@@ -11,7 +11,8 @@
 //                                                                           filters/action/partial_discrete_action_space_map.py
 //   * the per-row filter loop of WolpertingerAgent.learn_from_batch         agents/wolpertinger_agent.py:77-83
 //
-// rlx_knn_topk.  The squared distance is rlx_nn_min_distance's (csrc/bcq.hip), word for word: acc = 0; for w = 0 ..
+// rlx_knn_topk (the word, select_k and the merge pass are csrc/knn_select.hpp's, shared with dnd.hip).
+// The squared distance is rlx_nn_min_distance's (csrc/bcq.hip), word for word: acc = 0; for w = 0 ..
 // width-1 in this order t = q[w] - key[w], acc = acc + t * t, every operation rounded to fp32 on its own (this file is
 // compiled with -ffp-contract=off); never |q|^2 + |k|^2 - 2 q.k.  Every (query, key) pair becomes ONE 64-bit word,
 // (bit pattern of acc) << 32 | key index, a NaN's bit pattern replaced by 0xffffffff: acc is never negative, so the
@@ -36,77 +37,12 @@
 // rlx_wolpertinger_candidates is a launch of its own (the proto-actions' neighbours are known only after the last merge
 // pass, and the observation rows are wider than that pass's output); rlx_wolpertinger_select one thread per env;
 // rlx_discrete_to_box one thread per output word.
-#include "rlx_common.hpp"
+#include "knn_select.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kSlots = 8;                         // words of one thread
-constexpr int kKeyChunk = RLX_KNN_KEY_CHUNK;      // keys of one search workgroup = words of one merge workgroup
-constexpr int kQueryTile = 16;                    // queries of one search workgroup
+using namespace rlx::knn;                         // the word, select_k, the merge pass: csrc/knn_select.hpp
 constexpr int kMaxWidth = 64;
-constexpr int kMaxK = 64;
-static_assert(kKeyChunk == kThreads * kSlots, "eight words per thread");
-
-typedef unsigned long long u64;
-constexpr u64 kNone = ~0ull;                      // no word: above every (distance, index) word (index < 2^31 - 1)
-
-__device__ __forceinline__ u64 make_word(float acc, long long key) {
-    const unsigned bits = acc != acc ? 0xffffffffu : __float_as_uint(acc);
-    return ((u64)bits << 32) | (u64)(unsigned)key;
-}
-
-struct TopkOut {
-    u64 *lists;                                   // [n_queries][lists_out][k], or null: the final pass
-    long long lists_out;
-    int *idx; float *dist2;                       // [n_queries][k] (dist2 optional)
-    int k;
-};
-
-// the minimum of the wave's 64 * kSlots words, in every lane of the wave
-__device__ __forceinline__ u64 wave_min(const u64 (&w)[kSlots]) {
-    u64 m = w[0];
-#pragma unroll
-    for (int s = 1; s < kSlots; ++s) m = w[s] < m ? w[s] : m;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const u64 other = __shfl_xor(m, d);
-        m = other < m ? other : m;
-    }
-    return m;
-}
-
-// The k smallest of the workgroup's kThreads * kSlots words, ascending, to list `list` of query `q` (or to idx / dist2).
-// Every thread of the workgroup calls it; `red` is 2 x 4 words of LDS.
-__device__ __forceinline__ void select_k(u64 (&w)[kSlots], u64 (*red)[4], const TopkOut &o, int q, long long list) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    u64 wm = wave_min(w);            // kept across rounds: only the wave that held a round's winner has a new minimum
-    u64 mine = kNone;                // round tid's winner: thread r < k keeps round r's, and stores it after the last round
-    for (int r = 0; r < o.k; ++r) {
-        if (lane == 0) red[r & 1][wave] = wm;
-        __syncthreads();             // round r + 1 writes the other half; round r + 2 comes after the next barrier
-        u64 best = red[r & 1][0];
-#pragma unroll
-        for (int v = 1; v < kThreads / 64; ++v) best = red[r & 1][v] < best ? red[r & 1][v] : best;
-        if (tid == r) mine = best;   // (the k winners go out together below: one coalesced store per list)
-        if (wm == best && best != kNone) {        // uniform over the wave; words are unique: one wave, one owner
-#pragma unroll
-            for (int s = 0; s < kSlots; ++s)
-                if (w[s] == best) w[s] = kNone;
-            wm = wave_min(w);
-        }
-    }
-    if (tid < o.k) {
-        if (o.lists) {
-            o.lists[((size_t)q * (size_t)o.lists_out + (size_t)list) * (size_t)o.k + tid] = mine;
-        } else {
-            const unsigned hi = (unsigned)(mine >> 32);
-            o.idx[(size_t)q * o.k + tid] = (int)(unsigned)mine;
-            if (o.dist2) reinterpret_cast<unsigned *>(o.dist2)[(size_t)q * o.k + tid] = hi == 0xffffffffu ? 0x7fc00000u : hi;
-        }
-    }
-    __syncthreads();                 // the next query's first round writes red[0] again
-}
 
 struct SearchArgs {
     const float *q; long long ld_q; int n_queries, width;
@@ -125,17 +61,6 @@ __device__ __forceinline__ float4 load4(const float *base, long long ld, long lo
     if (w + 2 < width) v.z = p[2];
     if (w + 3 < width) v.w = p[3];
     return v;
-}
-
-__device__ __forceinline__ float dist4(float acc, const float4 &q, const float4 &k) {   // w in order: x, y, z, w
-    float t = q.x - k.x;
-    acc = acc + t * t;
-    t = q.y - k.y;
-    acc = acc + t * t;
-    t = q.z - k.z;
-    acc = acc + t * t;
-    t = q.w - k.w;
-    return acc + t * t;
 }
 
 __global__ void __launch_bounds__(kThreads) knn_search_kernel(const SearchArgs a) {
@@ -210,28 +135,6 @@ __global__ void __launch_bounds__(kThreads) knn_search_kernel(const SearchArgs a
     }
 }
 
-struct MergeArgs {
-    const u64 *in; long long lists_in;            // [n_queries][lists_in][k]
-    int fan;                                      // lists of one workgroup: fan * k <= kKeyChunk
-    TopkOut out;
-};
-
-__global__ void __launch_bounds__(kThreads) knn_merge_kernel(const MergeArgs a) {
-    __shared__ u64 red[2][4];
-    const int tid = threadIdx.x, q = blockIdx.y;
-    const long long group = blockIdx.x, first = group * a.fan;
-    const long long lists = min((long long)a.fan, a.lists_in - first);
-    const long long words = lists * a.out.k;      // <= kKeyChunk
-    const u64 *src = a.in + ((size_t)q * (size_t)a.lists_in + (size_t)first) * (size_t)a.out.k;
-    u64 w[kSlots];
-#pragma unroll
-    for (int s = 0; s < kSlots; ++s) {
-        const long long i = (long long)s * kThreads + tid;
-        w[s] = i < words ? src[i] : kNone;
-    }
-    select_k(w, red, a.out, q, group);
-}
-
 // critic inputs: row e * k + j <- (env e's observation, keys[idx[e][j]]); an index outside the table gives a zero key
 __global__ void __launch_bounds__(kThreads) wolpertinger_candidates_kernel(
         const int *idx, const float *keys, long long ld_k, long long n_keys, int width, const float *obs, long long ld_obs,
@@ -280,12 +183,6 @@ __global__ void __launch_bounds__(kThreads) discrete_to_box_kernel(const int *ac
     }
 }
 
-// lists left after one merge pass over `lists` lists of k words
-inline long long merged_lists(long long lists, int k) {
-    const int fan = kKeyChunk / k;
-    return (lists + fan - 1) / fan;
-}
-
 int check_topk_sizes(const char *who, int n_queries, long long n_keys, int k) {
     RLX_REQUIRE(k >= 1 && k <= kMaxK, "%s: k %d outside [1, %d]", who, k, kMaxK);
     RLX_REQUIRE(n_keys >= k && n_keys <= 0x7fffffffLL, "%s: n_keys %lld outside [k = %d, 2^31 - 1]", who, n_keys, k);
@@ -301,9 +198,7 @@ int rlx_knn_topk_scratch_bytes(int n_queries, long long n_keys, int k, long long
     RLX_REQUIRE(bytes_out, "rlx_knn_topk_scratch_bytes: null pointer");
     if (int rc = check_topk_sizes("rlx_knn_topk_scratch_bytes", n_queries, n_keys, k)) return rc;
     const long long chunks = (n_keys + kKeyChunk - 1) / kKeyChunk;
-    // the search's lists and the first merge pass's; later passes alternate between the two
-    const long long words = chunks > 1 ? (chunks + merged_lists(chunks, k)) * k * (long long)n_queries : 0;
-    *bytes_out = words * (long long)sizeof(u64);
+    *bytes_out = scratch_words(n_queries, chunks, k) * (long long)sizeof(u64);
     return RLX_OK;
 }
 
@@ -321,7 +216,7 @@ int rlx_knn_topk(const float *queries, long long ld_q, int n_queries, int width,
     hipStream_t s = rlx::as_stream(stream);
     const long long chunks = (n_keys + kKeyChunk - 1) / kKeyChunk;
     const int tiles = (n_queries + kQueryTile - 1) / kQueryTile;
-    u64 *buf[2] = {static_cast<u64 *>(scratch), static_cast<u64 *>(scratch) + chunks * k * (long long)n_queries};
+    u64 *const buf[2] = {static_cast<u64 *>(scratch), static_cast<u64 *>(scratch) + chunks * k * (long long)n_queries};
 
     SearchArgs a;
     a.q = queries; a.ld_q = ld_q; a.n_queries = n_queries; a.width = width;
@@ -329,25 +224,13 @@ int rlx_knn_topk(const float *queries, long long ld_q, int n_queries, int width,
     a.vec_q = ((uintptr_t)queries % 16 == 0 && ld_q % 4 == 0) ? 1 : 0;
     a.vec_k = ((uintptr_t)keys % 16 == 0 && ld_k % 4 == 0) ? 1 : 0;
     a.vec_keys4 = (width == 1 && ld_k == 1 && (uintptr_t)keys % 16 == 0) ? 1 : 0;
-    a.out.k = k; a.out.idx = idx_out; a.out.dist2 = dist2_out;
+    a.out.k = k; a.out.idx = idx_out; a.out.dist2 = dist2_out; a.out.skip = nullptr;
     a.out.lists = chunks > 1 ? buf[0] : nullptr;
     a.out.lists_out = chunks;
     RLX_LAUNCH((knn_search_kernel), dim3((unsigned)chunks, (unsigned)tiles), kThreads, 0, s, a);
     RLX_LAUNCH_CHECK();
 
-    long long lists = chunks;
-    for (int pass = 0; lists > 1; ++pass) {
-        MergeArgs m;
-        m.in = buf[pass & 1]; m.lists_in = lists; m.fan = kKeyChunk / k;
-        const long long left = merged_lists(lists, k);
-        m.out = a.out;
-        m.out.lists = left > 1 ? buf[(pass + 1) & 1] : nullptr;
-        m.out.lists_out = left;
-        RLX_LAUNCH((knn_merge_kernel), dim3((unsigned)left, (unsigned)n_queries), kThreads, 0, s, m);
-        RLX_LAUNCH_CHECK();
-        lists = left;
-    }
-    return RLX_OK;
+    return run_merges(buf, chunks, n_queries, a.out, s);
 }
 
 int rlx_wolpertinger_candidates(const int *idx, const float *keys, long long ld_k, long long n_keys, int width,

@@ -49,7 +49,7 @@ class EpisodicExperienceReplayParameters(ExperienceReplayParameters):        # :
 class EpisodicExperienceReplay(ExperienceReplay):
     def __init__(self, max_size, allow_duplicates_in_batch_sampling=True, n_step=-1, discount=0.99,
                  max_episode_length=None, measurements_dim=None, future_measurements=None, train_to_eval_ratio=1,
-                 action_probabilities=0, **device_kwargs):
+                 action_probabilities=0, embedding=0, max_action_value=False, **device_kwargs):
         """
         :param max_size: (MemoryGranularity.Transitions | Episodes, n)               (reference signature)
         :param n_step: steps summed into n_step_discounted_rewards (-1: to the episode end)   (reference signature)
@@ -65,6 +65,11 @@ class EpisodicExperienceReplay(ExperienceReplay):
         :param action_probabilities: A > 0 — keep an fp32 column [rows][A] of what the reference stores as a transition's
                                  info['all_action_probabilities'] (off-policy evaluation divides by it; store() then takes
                                  the step's rows); absent (0) unless asked for
+        :param embedding: W > 0 — keep an fp32 column [rows][W] of the state embedding the agent acted on (NEC: the key
+                                 its dictionary receives when the episode ends); absent (0) unless asked for
+        :param max_action_value: keep an fp32 column [rows] of ActionInfo.max_action_value (0 for a heat-up step) and
+                                 bootstrap n_step_discounted_rewards from it, as Episode.update_discounted_rewards does
+                                 with bootstrap_total_return_from_old_policy (rlx_episode_nstep_returns_bootstrapped)
         """
         if not isinstance(n_step, int) or (n_step < 1 and n_step != -1):
             raise ValueError("n-step should be an integer with value >= 1, or set to -1 for always setting to "
@@ -104,6 +109,12 @@ class EpisodicExperienceReplay(ExperienceReplay):
         if action_probabilities:
             self.action_probabilities = torch.zeros(self.rows, int(action_probabilities), dtype=torch.float32,
                                                     device=self.device)
+        self.embedding = self.max_action_value = None
+        if embedding:
+            self.embedding = torch.zeros(self.rows, int(embedding), dtype=torch.float32, device=self.device)
+        if max_action_value:
+            self.max_action_value = torch.zeros(self.rows, dtype=torch.float32, device=self.device)
+        self.episode_callback = None     # called with (env, the episode's rows in order) when an episode has been stored
         self._order = np.zeros(transitions + 2 * self.Tmax + 1, dtype=np.int64)   # ring of listed rows
         self.train_to_eval_ratio = train_to_eval_ratio            # used in batch-rl (:69-75)
         self.last_training_set_episode_id = None
@@ -145,7 +156,8 @@ class EpisodicExperienceReplay(ExperienceReplay):
 
     # ------------------------------------------------------------------------------ rollout side
     def store(self, actions, rewards, game_overs, next_obs, reset_obs, record=True, dones=None, defer=False,
-              episode_end=False, dones_host=None, measurements=None, action_probabilities=None):
+              episode_end=False, dones_host=None, measurements=None, action_probabilities=None, embedding=None,
+              max_action_value=None):
         """measurements: the STATES' measurements of this step's transitions (device fp64 [n_env][M]); required where
         the memory keeps the column.
         action_probabilities: the step's all_action_probabilities (device fp32 [n_env][A]); required where the memory keeps
@@ -184,6 +196,12 @@ class EpisodicExperienceReplay(ExperienceReplay):
                                  "without it without them")
             if action_probabilities is not None:
                 pairs.append((action_probabilities, self.action_probabilities))
+            for given, column, name in ((embedding, self.embedding, "embedding"),
+                                        (max_action_value, self.max_action_value, "max_action_value")):
+                if (given is None) != (column is None):
+                    raise ValueError("a memory with the %s column is stored with it, one without it without it" % name)
+                if given is not None:
+                    pairs.append((given, column))
             self.lib.copy_columns(_rlx.make_columns(pairs), len(pairs), None, None, 0, row0, self.n_env,
                                   self.rows, self.n_env, self.status, s)
         self.lib.select_rows(game_overs, reset_obs, next_obs, self.cur_state, self.n_env, self.obs_dim * 4, s)
@@ -213,8 +231,15 @@ class EpisodicExperienceReplay(ExperienceReplay):
         self._order_len += T
         self._episodes.append(T)
         self._episode_first_step.append(s0)
-        self.lib.episode_nstep_returns(self.reward, self.n_step_discounted_rewards, None, s0, T, e, self.n_env,
-                                       self._ring_steps, self.discount, self.n_step, _rlx.current_stream())
+        if self.max_action_value is not None:
+            self.lib.episode_nstep_returns_bootstrapped(self.reward, self.max_action_value, self.n_step_discounted_rewards,
+                                                        None, s0, T, e, self.n_env, self._ring_steps, self.discount,
+                                                        self.n_step, _rlx.current_stream())
+        else:
+            self.lib.episode_nstep_returns(self.reward, self.n_step_discounted_rewards, None, s0, T, e, self.n_env,
+                                           self._ring_steps, self.discount, self.n_step, _rlx.current_stream())
+        if self.episode_callback is not None:
+            self.episode_callback(e, rows)
         if self.future_measurements is not None:
             self.lib.dfp_future_measurements(self.measurements, self.future_measurements, self.future_scale, s0, T, e,
                                              self.n_env, self._ring_steps, self.future_steps, self.M,

@@ -1371,6 +1371,81 @@ class ClassificationNet(_NetBase):
         return self.loss
 
 
+def nec_net_kwargs(np_, alg, seed):
+    """NECNetworkParameters + NECAlgorithmParameters -> the keywords of NECNet's constructor"""
+    from ..architectures.head_parameters import DNDQHeadParameters
+    heads = list(np_.heads_parameters)
+    if len(heads) != 1 or not isinstance(heads[0], DNDQHeadParameters):
+        raise ValueError("NECNet serves a wrapper with exactly one DNDQHeadParameters head, got %s"
+                         % [type(h).__name__ for h in heads])
+    return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),
+                dnd_size=alg.dnd_size, number_of_knn=alg.number_of_knn, l2_norm_added_delta=alg.l2_norm_added_delta,
+                new_value_shift_coefficient=alg.new_value_shift_coefficient,
+                DND_key_error_threshold=alg.DND_key_error_threshold,
+                propagate_updates_to_DND=alg.propagate_updates_to_DND)
+
+
+class NECNet(_NetBase):
+    """NECNetworkParameters (agents/nec_agent.py:36-43): embedder -> FC middleware -> DNDQHead (heads/dnd_q_head.py).  The
+    head has no trainable parameters: it is the dictionary (memories.non_episodic.differentiable_neural_dictionary.QDND,
+    csrc/dnd.hip), keyed by the trunk's output.  No target copy.  Two passes: `q_values` — all A tables, for acting, the
+    embedding rows left where the caller can take them — and `learn_from_batch` — the taken action's table only, the Q
+    head's loss (rlx_dnd_head_loss_backward) into the trunk's gradient, clip, Adam."""
+
+    def __init__(self, device, obs_shape, n_actions, dnd_size=500000, number_of_knn=50, l2_norm_added_delta=0.001,
+                 new_value_shift_coefficient=0.1, DND_key_error_threshold=0.0, propagate_updates_to_DND=False,
+                 activation="relu", embedder="Medium", middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9,
+                 adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None, seed=0):
+        from ..memories.non_episodic.differentiable_neural_dictionary import QDND
+        self.A = int(n_actions)
+        self.clip_gradients = clip_gradients
+        if len(obs_shape) == 3:
+            raise NotImplementedError("NECNet: image observations are not served (vector observations only)")
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        self.modules = [self.torso]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self.dnd = QDND(dnd_size, feat, self.A, new_value_shift_coefficient=new_value_shift_coefficient,
+                        key_error_threshold=DND_key_error_threshold, num_neighbors=number_of_knn,
+                        l2_norm_added_delta=l2_norm_added_delta, propagate_updates_to_DND=propagate_updates_to_DND,
+                        device=device)
+        self.W = feat
+        self.loss = torch.zeros(1, dtype=torch.float32, device=device)
+
+    def state_embedding(self, obs, B, tag="act"):
+        """the trunk's output [B, W] (the dictionary's key), valid until the next pass under the same tag"""
+        return self.trunk_forward(obs, B, tag)[-1].data.view(B, self.W)
+
+    def q_values(self, obs, B, tag="act"):
+        """-> (Q [B, A] over all tables — zeros where a table has at most k entries —, the embedding rows [B, W]); the
+        lookup stamps what it read"""
+        e = self.state_embedding(obs, B, tag)
+        return self.dnd.query(e), e
+
+    def accumulate_gradients(self, obs, B, actions, targets):
+        """forward, Q of each row's taken action against `targets` (n_step_discounted_rewards), backward: the gradients in
+        params.grads (clipped when clip_gradients is set), the loss in self.loss, tf.global_norm of the raw gradients in
+        self.norm"""
+        acts = self.trunk_forward(obs, B, "train")
+        feat = acts[-1]
+        e = feat.data.view(B, self.W)
+        q, saved = self.dnd.train_query(e, actions)
+        _, scalars = self.dnd.loss_backward(e, actions, q, saved, targets, out=feat.ensure_grad().view(B, self.W))
+        feat.grad_is_dz = False
+        self.loss.copy_(scalars)
+        self.torso.backward(self.ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return self.loss
+
+    def learn_from_batch(self, obs, B, actions, targets, grad_scale=1.0, sync=None):
+        """one update: accumulate_gradients, then one Adam step"""
+        if sync is not None:
+            raise NotImplementedError("NECNet: data-parallel training is not served (one dictionary per worker)")
+        self.accumulate_gradients(obs, B, actions, targets)
+        self.apply_gradients(grad_scale)
+        return self.loss
+
+
 def policy_gradient_net_kwargs(np_, alg, seed):
     """PolicyGradientNetworkParameters + the algorithm's beta_entropy -> the keywords of PolicyGradientNet's constructor"""
     return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),

@@ -298,6 +298,14 @@ int rlx_episode_nstep_returns(const float *rewards, double *out, double *compact
                                                   fp64, the reference's summation order (bit-identical).  out: a
                                                   column indexed like `rewards` (or NULL); compact_out: [length]
                                                   (or NULL) — the 'Discounted Return' signal's samples */
+/* The same column with the bootstrap of Episode.update_discounted_rewards (core_types.py:793-798,
+ * bootstrap_total_return_from_old_policy; NEC): step t gets + discount^n * max_action_value[t + n], n = min(n_step,
+ * length), and nothing where t + n is past the end.  max_action_value: fp32, indexed like `rewards` (a heat-up step
+ * carries 0: ActionInfo's default action_value).  discount^n is the reference's running product; the product and the
+ * sum are fp64 (the reference rounds the product to fp32 when every bootstrap of the episode is an fp32 network value). */
+int rlx_episode_nstep_returns_bootstrapped(const float *rewards, const float *max_action_value, double *out,
+                                           double *compact_out, long long first_step, int length, int env, int n_env,
+                                           long long ring_steps, double discount, int n_step, void *stream);
 int rlx_standardize(const double *x, long long n, float *out32, double *out64, double *mean_std,
                     void *stream);                                   /* clipped_ppo_agent.py:201 (no epsilon) */
 int rlx_episode_stats_init(double *ep_return, int *ep_len, int n_env, double *acc, void *stream);
@@ -2000,6 +2008,67 @@ int rlx_lstm_forward(const float *x, long long ld_x, const float *gx, long long 
  * zeros); the carried state is a constant, it gets no gradient. */
 int rlx_lstm_backward(const float *dh_out, long long ld_dh, const float *gates, const float *c, const float *c0,
                       const float *recurrent, long long ld_w, float *dgates, int S, int T, int cells, void *stream);
+
+/* ------------------------------- NEC: differentiable neural dictionary — lookup, Q head, writes (csrc/dnd.hip) -- */
+/* QDND / AnnoyDictionary (memories/non_episodic/differentiable_neural_dictionary.py) and DNDQHead
+ * (architectures/tensorflow_components/heads/dnd_q_head.py) with the exact nearest neighbours in place of the Annoy
+ * forest.  Entry points ADDED under ABI version 11.  The dictionary is the caller's device memory: keys [A][cap][ld_k]
+ * fp32 (table a at keys + a * cap * ld_k), values [A][cap] fp32, stamps [A][cap] int64 (LRU time stamps, never
+ * negative), size [A] int32 (entries of each table), one int64 clock.  Rows of keys, queries, embeddings and gradients
+ * are 16-byte aligned with leading dimensions that are multiples of 4.  width: a multiple of 16 in [16, 512]; k in
+ * [1, 64]; anything else is RLX_ERR_INVALID_ARG naming the argument.  No call allocates or synchronises: capturable.
+ *
+ * rlx_dnd_lookup: for each query row the k nearest keys of a table, idx_out int32 [n_queries][n_lists][k] and (optional)
+ * dist2_out fp32 of the same shape, ascending in (squared distance, index) — rlx_knn_topk's distance, word and order,
+ * one definition (csrc/knn_select.hpp).  actions [n_queries] (NULL: all -1): n_lists = A gives a list per table, a query
+ * of action -1 searching all A tables and a query of action a only table a (list a); n_lists = 1 gives the list of the
+ * query's own table.  Table a takes part with min(size[a], max_keys) keys; max_keys <= cap is an upper bound of every
+ * size that the host knows (it fixes the number of chunks: the sizes themselves are read on the device).  A (query, list)
+ * whose table has fewer than min_keys (>= k) keys, or that names no table, gets flags_out [n_queries][n_lists] = 1 and
+ * its idx / dist2 are NOT written; every other pair gets 0.  QDND.query's has_enough_entries(k) is min_keys = k + 1.
+ * One workgroup per (chunk of RLX_KNN_KEY_CHUNK keys, tile of 16 queries, table), then merge passes as rlx_knn_topk:
+ * 1 + ceil(log_{CHUNK / k}(ceil(max_keys / CHUNK))) launches.  n_queries * n_lists <= 65535. */
+int rlx_dnd_lookup_scratch_bytes(int n_queries, int n_lists, long long max_keys, int k, long long *bytes_out);
+int rlx_dnd_lookup(const float *queries, long long ld_q, int n_queries, int width, const float *keys, long long ld_k,
+                   long long cap, const int *size, int A, long long max_keys, const int *actions, int n_lists, int k,
+                   int min_keys, int *idx_out, float *dist2_out, int *flags_out, void *scratch, long long scratch_bytes,
+                   void *stream);
+/* DNDQHead._q_value (dnd_q_head.py:67-83) over the lists of rlx_dnd_lookup (same rows, n_lists, actions):
+ *   d_j = sum_w (key_j[w] - e[w])^2 + l2_norm_added_delta,  w_j = 1 / d_j,  q_out[row][list] = sum_j v_j w_j / sum_j w_j
+ * A flagged pair gives 0 (QDND.query's zeros).  The same launch stamps the neighbours it read: row b stamps
+ * max(stamp, *clock + b) (an atomic maximum: "later wins"), and a second launch of one thread advances *clock by `rows`.
+ * d_out [rows][n_lists][k] and sumw_out [rows][n_lists] (optional, together) keep d_j and sum_j w_j for the backward
+ * pass.  One wave per (row, list). */
+int rlx_dnd_head_forward(const float *embedding, long long ld_e, int rows, int width, const float *keys, long long ld_k,
+                         long long cap, const float *values, long long *stamps, int A, const int *idx, const int *flags,
+                         const int *actions, int n_lists, int k, float l2_norm_added_delta, long long *clock, float *q_out,
+                         long long ld_q, float *d_out, float *sumw_out, void *stream);
+/* The Q head's loss as NECAgent.learn_from_batch sets it up (agents/nec_agent.py:137-150: the targets equal the
+ * prediction except at the taken action, which carries `targets`), normalised as rlx_dqn_head_loss normalises:
+ * scalars[0] = sum_b (q[b] - targets[b])^2 / rows (a flagged row counts with its q = 0, as in the reference, and has no
+ * gradient), and the gradient through the taken
+ * action's k neighbours (n_lists = 1 lists of that action: idx [rows][k], flags [rows], d, sumw, q [rows] ld_q apart):
+ *   de_out[b][:] = grad_scale * 2 (q_b - t_b) / rows * sum_j 2 (v_j - q_b) / (sumw_b d_j^2) * (key_j - e_b)
+ * zeros for a flagged row.  One workgroup per row, fixed neighbour order, no atomics. */
+int rlx_dnd_head_loss_backward(const float *embedding, long long ld_e, int rows, int width, const float *keys,
+                               long long ld_k, long long cap, const float *values, int A, const int *idx, const int *flags,
+                               const int *actions, int k, const float *d, const float *sumw, const float *q, long long ld_q,
+                               const float *targets, float grad_scale, float *de_out, long long ld_de, float *scalars,
+                               void *stream);
+/* AnnoyDictionary.add (:60-102) with override_existing_keys and a rebuild at the end of every call, for all tables at
+ * once: T embeddings with their actions and returns, in episode order.  nn_idx / nn_dist2 / nn_flags [T]: rlx_dnd_lookup
+ * of the embeddings against the tables as they are before the call (k = 1, n_lists = 1, min_keys = 1).  A key whose
+ * nearest entry lies within sqrt(dist2) <= key_error_threshold writes no slot: value += new_value_shift_coefficient *
+ * (return - value), in episode order, and the entry is stamped.  Every other key takes slot size++ while its table has
+ * room, and evicts afterwards: the m keys left over take the m entries of smallest (stamp, index) from before the call
+ * (counting passes over the stamps, one per bit of stamp << 22 | index).  Every stamp written is *clock; a second launch
+ * advances *clock by 1.  One workgroup per action.  slot_scratch: int32 [(A + 1) * T].  *status |= 1: a row's action
+ * lies outside [0, A), that row is written nowhere.  *status |= 2: *clock >= 2^40 (an eviction word would overflow), the
+ * whole call is dropped: no value, stamp, key or size changes (the clock still advances).  1 <= T <= cap <= 2^22. */
+int rlx_dnd_add(const float *embedding, long long ld_e, int T, int width, const int *actions, const float *returns,
+                const int *nn_idx, const float *nn_dist2, const int *nn_flags, float *keys, long long ld_k, long long cap,
+                float *values, long long *stamps, int *size, int A, long long *clock, float key_error_threshold,
+                float new_value_shift_coefficient, int *slot_scratch, int *status, void *stream);
 
 #ifdef __cplusplus
 }
