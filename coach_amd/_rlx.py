@@ -285,7 +285,7 @@ STRUCT_NAMES = {          # rlx.h structure -> its class in this module (bound b
     "rlx_small_dense_problem": "SmallDenseProblem", "rlx_mlp_dqn_desc": "MlpDqnDesc", "rlx_mlp3": "Mlp3",
     "rlx_fused_net": "FusedNet", "rlx_td3_fused_desc": "Td3FusedDesc", "rlx_sac_fused_desc": "SacFusedDesc",
     "rlx_ppo_fc_heads_desc": "PpoFcHeadsDesc", "rlx_ppo_rows_desc": "PpoRowsDesc", "rlx_observe_desc": "ObserveDesc",
-    "rlx_signal_source": "SignalSource", "rlx_adam_split_desc": "AdamSplitDesc",
+    "rlx_signal_source": "SignalSource", "rlx_adam_split_desc": "AdamSplitDesc", "rlx_cil_desc": "CilDesc",
 }
 _TEXT = header_text()
 STRUCTS = parse_structs(_TEXT, STRUCT_NAMES)
@@ -298,7 +298,7 @@ Mlp3, FusedNet = STRUCTS["rlx_mlp3"], STRUCTS["rlx_fused_net"]
 Td3FusedDesc, SacFusedDesc = STRUCTS["rlx_td3_fused_desc"], STRUCTS["rlx_sac_fused_desc"]
 PpoFcHeadsDesc, PpoRowsDesc = STRUCTS["rlx_ppo_fc_heads_desc"], STRUCTS["rlx_ppo_rows_desc"]
 ObserveDesc, SignalSource = STRUCTS["rlx_observe_desc"], STRUCTS["rlx_signal_source"]
-AdamSplitDesc = STRUCTS["rlx_adam_split_desc"]
+AdamSplitDesc, CilDesc = STRUCTS["rlx_adam_split_desc"], STRUCTS["rlx_cil_desc"]
 
 
 class SplitkJob(STRUCTS["rlx_splitk_job"]):

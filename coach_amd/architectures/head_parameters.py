@@ -159,3 +159,44 @@ class DNDQHeadParameters(HeadParameters):
     def __init__(self, activation_function='relu', name='dnd_q_head_params', rescale_gradient_from_head_by_factor=1.0,
                  loss_weight=1.0):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+
+
+class RegressionHeadParameters(HeadParameters):
+    """RegressionHeadParameters (head_parameters.py:88-97): `scheme` -- the reference's default is [Dense(256), Dense(256)],
+    layers WITHOUT an activation -- then Dense(A) named 'output' (heads/cil_head.py:47-56), MSE or Huber against the
+    targets.  CIL carries num_output_head_copies of it, one per high-level command: nn.networks.CILNet builds them as one
+    G.BranchStack (csrc/cil.hip)."""
+    head_type = "RegressionHead"
+
+    def __init__(self, activation_function='relu', name='q_head_params', num_output_head_copies=1,
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0, dense_layer=None, scheme=None,
+                 output_bias_initializer=None):
+        super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+        if dense_layer is not None or output_bias_initializer is not None:
+            raise ValueError("RegressionHeadParameters: dense_layer and output_bias_initializer are not served")
+        self.num_output_head_copies = num_output_head_copies
+        self.scheme = scheme
+
+    def native_scheme(self):
+        """-> ((H1, H2), (dropout rate behind each), the hidden layers' activation or None): two Dense layers, each
+        optionally followed by one BatchnormActivationDropout; both activations equal; no batch normalisation."""
+        from .layers import BatchnormActivationDropout, Dense
+        scheme = [Dense(256), Dense(256)] if self.scheme is None else list(self.scheme)
+        units, follow = [], []
+        for layer in scheme:
+            if isinstance(layer, (Dense, int)):
+                units.append(layer.units if isinstance(layer, Dense) else int(layer))
+                follow.append(None)
+            elif isinstance(layer, BatchnormActivationDropout) and units and follow[-1] is None:
+                follow[-1] = layer
+            else:
+                raise ValueError("RegressionHeadParameters: unsupported layer in the scheme: {!r}".format(layer))
+        if len(units) != 2:
+            raise ValueError("RegressionHeadParameters: the scheme has two Dense layers (got {})".format(len(units)))
+        if any(f is not None and f.batchnorm for f in follow):
+            raise ValueError("RegressionHeadParameters: batchnorm=True inside the regression head is not served")
+        acts = [f.activation_function if f is not None else None for f in follow]
+        if acts[0] != acts[1]:
+            raise ValueError("RegressionHeadParameters: both hidden layers take the same activation (got {})".format(acts))
+        rates = tuple(float(f.dropout_rate or 0.0) if f is not None else 0.0 for f in follow)
+        return tuple(units), rates, acts[0]

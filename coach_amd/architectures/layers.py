@@ -22,6 +22,16 @@ class NoisyNetDense(Dense):
         self.sigma0 = sigma0
 
 
+class BatchnormActivationDropout(object):
+    """rl_coach/architectures/layers.py:124-165: what follows a Dense layer of a scheme.  Read by the regression heads of
+    CIL (RegressionHeadParameters.native_scheme), the one place where dropout is built (csrc/cil.hip)."""
+    def __init__(self, batchnorm=False, activation_function=None, dropout_rate=0):
+        self.batchnorm, self.activation_function, self.dropout_rate = batchnorm, activation_function, dropout_rate
+
+    def __repr__(self):
+        return "BatchnormActivationDropout({}, {!r}, {})".format(self.batchnorm, self.activation_function, self.dropout_rate)
+
+
 class Conv2d(object):
     def __init__(self, num_filters, kernel_size, strides):
         self.num_filters, self.kernel_size, self.strides = int(num_filters), int(kernel_size), int(strides)

@@ -721,6 +721,112 @@ class LSTM(Layer):
             x.grad_is_dz = lower is not None
 
 
+class BranchStack(Layer):
+    """CIL's command-branched regression heads (heads/cil_head.py RegressionHead x num_output_head_copies): `branches`
+    copies of Dense(H1) act dropout(rate1), Dense(H2) act dropout(rate2), Dense(units) over one shared input.
+    csrc/cil.hip: `forward` is the clean pass of all branches in one launch (optionally the rows' own branch, by command),
+    `train` the reference's predict + training forward + head losses, `backward` the chain down to the hidden
+    pre-activations followed by the batched weight-gradient products every dense layer has.
+
+    Each layer is one FlatParams group of `branches` towers under `name`/dense0, /dense1, /output.  The dropout masks
+    come from the device generator under (seed, rank) at a draw index the train launch advances (self.draw); they are
+    never stored, the backward pass regenerates them from the index the launch used (self.draw_used)."""
+    MIN_BRANCHES, MAX_BRANCHES = 2, _rlx.CONSTANTS["RLX_CIL_MAX_BRANCHES"]
+
+    def __init__(self, params, name, in_features, hidden, units, branches, activation=None, dropout_rates=(0.0, 0.0),
+                 seed=0, rank=0):
+        H1, H2 = (int(h) for h in hidden)
+        F, A, K = int(in_features), int(units), int(branches)
+        ok16 = lambda v, hi: v % 16 == 0 and 16 <= v <= hi
+        if not (self.MIN_BRANCHES <= K <= self.MAX_BRANCHES and ok16(F, 512) and ok16(H1, 256) and ok16(H2, 256) and 1 <= A <= 16):
+            raise ValueError("BranchStack: (in_features %d, hidden %d, %d, units %d, branches %d) is not served by "
+                             "csrc/cil.hip (in_features a multiple of 16 in [16, 512], hidden widths multiples of 16 in "
+                             "[16, 256], units in [1, 16], branches in [2, %d])" % (F, H1, H2, A, K, self.MAX_BRANCHES))
+        if activation not in FUSED_ACTS:
+            raise NotImplementedError("BranchStack: csrc/cil.hip implements %s, not %r" % (FUSED_ACTS, activation))
+        self.rates = tuple(float(r) for r in dropout_rates)
+        if len(self.rates) != 2 or not all(0.0 <= r < 1.0 for r in self.rates):
+            raise ValueError("BranchStack: dropout_rates = %r (one rate in [0, 1) per hidden layer)" % (dropout_rates,))
+        self.name, self.K, self.N, self.act, self.T, self.params = name, F, A, activation, K, params
+        self.H1, self.H2, self.seed, self.rank = H1, H2, int(seed) & 0xFFFFFFFF, int(rank) & 0xFFFFFFFF
+        self.shapes = [(F, H1), (H1, H2), (H2, A)]
+        self.names = [name + "/dense0", name + "/dense1", name + "/output"]
+        for n, (k, u) in zip(self.names, self.shapes):
+            params.add_group([(n + "/kernel", (k, u)), (n + "/bias", (u,))], K)
+        self.kname, self.bname = self.names[0] + "/kernel", self.names[0] + "/bias"
+        self.draw = self.draw_used = None
+
+    def initialize(self, rng):
+        for n, (k, u) in zip(self.names, self.shapes):
+            for t in range(self.T):
+                self.params.w(n + "/kernel", t).copy_(torch.from_numpy(xavier_uniform(rng, k, u, (k, u))))
+        # the draw index lives as long as the weights: allocated here, never inside a pass (a captured zero-fill would
+        # reset it at every replay)
+        dev = self.params.weights.device
+        self.draw = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.draw_used = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _desc(self, x, weights=None):
+        assert x.towers in (0, 1) and x.cols == self.K and not x.u8, (self.name, x.towers, x.cols, self.K)
+        p, d = self.params, _rlx.CilDesc()
+        d.x, d.ld_x = x.data.data_ptr(), self.K
+        for i, n in enumerate(self.names, 1):
+            setattr(d, "w%d" % i, p.w(n + "/kernel", 0, weights).data_ptr())
+            setattr(d, "b%d" % i, p.w(n + "/bias", 0, weights).data_ptr())
+            setattr(d, "stride%d" % i, p.stride(n + "/kernel"))
+        d.B, d.F, d.H1, d.H2, d.A, d.K, d.activation = x.rows, self.K, self.H1, self.H2, self.N, self.T, _rlx.ACT[self.act]
+        return d
+
+    def forward(self, ctx, x, tag="", weights=None, commands=None, status=None):
+        """-> (y [branches, rows, units], values [rows, units] or None): the clean pass; commands (int32 [rows]) selects
+        each row's own branch into values, a command outside [0, branches) raising the status bit (its row is kept)."""
+        B = x.rows
+        y = ctx.buffer(self.name, (self.T, B, self.N), tag=tag)
+        values = ctx.buffer(self.name + "/values", (B, self.N), tag=tag) if commands is not None else None
+        ctx.lib.cil_branches_forward(ctypes.byref(self._desc(x, weights)), commands, y, values, self.N, status, ctx.stream)
+        return y, values
+
+    def train(self, ctx, x, commands, actions, status, huber=False, loss_weight=1.0, grad_scale=1.0, training=True,
+              tag="train", want_y_train=False):
+        """the update's forward half -> dict(y, y_train, dy, h1, h2, losses [branches + 1]); training=False runs it
+        without dropout (Context.bn_training off).  backward(ctx, x, saved) continues from the dict."""
+        B, K = x.rows, self.T
+        if self.draw is None:
+            raise RuntimeError("%s: initialize() allocates the draw index; call it before the first update" % self.name)
+        buf = lambda n, shape, dtype=torch.float32: ctx.buffer(self.name + "/" + n, shape, dtype, tag=tag)
+        s = dict(y=buf("y", (K, B, self.N)), dy=buf("dy", (K, B, self.N)), h1=buf("h1", (K, B, self.H1)),
+                 h2=buf("h2", (K, B, self.H2)), losses=buf("losses", (K + 1,)), tag=tag,
+                 y_train=buf("y_train", (K, B, self.N)) if want_y_train else None,
+                 rates=self.rates if training else (0.0, 0.0))
+        ctx.lib.cil_branches_train(ctypes.byref(self._desc(x)), commands, actions, self.N, s["rates"][0], s["rates"][1],
+                                   int(bool(huber)), float(loss_weight), float(grad_scale), self.seed, self.rank, self.draw,
+                                   self.draw_used, s["y"], s["y_train"], s["dy"], s["h1"], s["h2"], s["losses"],
+                                   buf("partials", (K * ((B + 15) // 16),), torch.float64), status, ctx.stream)
+        return s
+
+    def backward(self, ctx, x, saved, need_dx=True):
+        """writes the six parameter gradients and (optionally) x.grad = sum over branches, in branch order, of
+        dz1_k W1_k^T, carrying the lower layer's activation derivative like Dense.backward's."""
+        B, K, p, tag = x.rows, self.T, self.params, saved["tag"]
+        dz2 = ctx.buffer(self.name + "/dz2", (K, B, self.H2), tag=tag)
+        dz1 = ctx.buffer(self.name + "/dz1", (K, B, self.H1), tag=tag)
+        ctx.lib.cil_branches_backward(ctypes.byref(self._desc(x)), saved["dy"], saved["h1"], saved["h2"], saved["rates"][0],
+                                      saved["rates"][1], self.seed, self.rank, self.draw_used, dz2, dz1, ctx.stream)
+        operands = [(x.data, 0, dz1), (saved["h1"], B * self.H1, dz2), (saved["h2"], B * self.H2, saved["dy"])]
+        for n, (k, u), (a, a_stride, dz) in zip(self.names, self.shapes, operands):      # dW_k = a_k^T dz_k, db_k its column sums
+            _rlx.gemm(k, u, B, a, dz, p.g(n + "/kernel"), a_strides=(1, k), batch=K, a_batch_stride=a_stride,
+                      b_batch_stride=B * u, c_batch_stride=p.stride(n + "/kernel"), workspace=ctx.ws.splitk,
+                      colsum_out=p.g(n + "/bias"), colsum_batch_stride=p.stride(n + "/bias"))
+        if need_dx:
+            lower = x.act if x.act in FUSED_ACTS else None
+            dx = x.ensure_grad()
+            for t in range(K):
+                _rlx.gemm(B, self.K, self.H1, dz1[t], p.w(self.kname, t), dx, b_strides=(1, self.H1),
+                          workspace=ctx.ws.splitk, deriv_aux=x.data if lower else None, aux_ld=self.K, deriv_kind=lower,
+                          accumulate=t > 0)
+            x.grad_is_dz = lower is not None
+
+
 class BatchNorm(Layer):
     """tf.layers.batch_normalization(x, training=is_training) + the activation, after a Dense layer built without one
     (BatchnormActivationDropout, tensorflow_components/layers.py:26-55, 138-152): momentum 0.99, epsilon 1e-3, gamma / beta

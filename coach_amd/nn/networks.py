@@ -1371,6 +1371,96 @@ class ClassificationNet(_NetBase):
         return self.loss
 
 
+def cil_net_kwargs(np_, seed):
+    """CILNetworkParameters -> the keywords of CILNet's constructor (the head's scheme: RegressionHeadParameters.native_scheme)"""
+    from ..architectures.head_parameters import RegressionHeadParameters
+    heads = list(np_.heads_parameters)
+    if len(heads) != 1 or not isinstance(heads[0], RegressionHeadParameters):
+        raise ValueError("CILNet serves a wrapper with exactly one RegressionHeadParameters head, got %s"
+                         % [type(h).__name__ for h in heads])
+    head = heads[0]
+    if head.rescale_gradient_from_head_by_factor != 1.0:
+        raise ValueError("CILNet: rescale_gradient_from_head_by_factor = %r on the regression head is not served"
+                         % (head.rescale_gradient_from_head_by_factor,))
+    hidden, rates, act = head.native_scheme()
+    extras = getattr(np_, "_view_extras", {})
+    return dict(common_net_kwargs(np_, seed), clip_gradients=getattr(np_, "clip_gradients", None),
+                branches=head.num_output_head_copies, hidden=hidden, dropout_rates=rates,
+                head_activation=act, loss_weight=head.loss_weight,
+                replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss,
+                embedder_dropout_rate=extras.get("embedder_scheme", {}).get("dropout_rate", 0.0),
+                middleware_dropout_rate=extras.get("middleware_scheme", {}).get("dropout_rate", 0.0))
+
+
+class CILNet(_NetBase):
+    """CILNetworkParameters (agents/cil_agent.py:38-47): vector embedder -> FC middleware -> `branches` RegressionHead
+    copies (heads/cil_head.py), one per high-level command, as one G.BranchStack (csrc/cil.hip).  No target copy.
+    `predict` and `action_values` never drop; an update draws dropout masks while ctx.bn_training is set
+    (set_is_training, the reference's is_training placeholder).  The loss of head k is the batch mean of the per-row
+    summed MSE / Huber terms against targets that equal the stored action in the row's own branch and the clean
+    prediction elsewhere (CILAgent.learn_from_batch)."""
+
+    def __init__(self, device, obs_shape, action_dim, branches, hidden=(256, 256), head_activation=None,
+                 dropout_rates=(0.0, 0.0), activation="relu", embedder="Medium", middleware="Medium", learning_rate=2.5e-4,
+                 adam_beta1=0.9, adam_beta2=0.99, optimizer_epsilon=1e-4, clip_gradients=None, loss_weight=1.0,
+                 replace_mse_with_huber_loss=False, embedder_dropout_rate=0.0, middleware_dropout_rate=0.0, seed=0):
+        if len(obs_shape) == 3:
+            raise NotImplementedError("CILNet: image observations are not served (vector observations only)")
+        for part, rate in (("input embedder", embedder_dropout_rate), ("middleware", middleware_dropout_rate)):
+            if rate:
+                raise ValueError("CILNet: dropout_rate = %r on the %s is not served (dropout is built in the regression "
+                                 "heads only)" % (rate, part))
+        self.A, self.K = int(action_dim), int(branches)
+        self.clip_gradients, self.huber, self.loss_weight = clip_gradients, bool(replace_mse_with_huber_loss), float(loss_weight)
+        feat = self._build_trunk(obs_shape, activation, embedder, middleware)
+        self.stack = G.BranchStack(self.params, "main/regression_head", feat, hidden, self.A, self.K, head_activation,
+                                   dropout_rates, seed=seed)
+        self.modules = [self.torso, self.stack]
+        self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon, has_target=False)
+        self.ctx.bn_training = True                       # learn_from_batch trains; predict never drops
+        self.losses = torch.zeros(self.K + 1, dtype=torch.float32, device=device)      # the K head losses, their total
+        self.loss = self.losses[self.K:]
+
+    def _input(self, obs, B, tag):
+        acts = self.trunk_forward(obs, B, tag)
+        return acts, acts[-1]
+
+    def predict(self, obs, B, tag="predict"):
+        """the K heads' outputs, fp32 [K, B, A], without dropout"""
+        return self.stack.forward(self.ctx, self._input(obs, B, tag)[1], tag=tag)[0]
+
+    def action_values(self, obs, B, commands, tag="act"):
+        """each row's output of its command's head, fp32 [B, A] (extract_action_values); a command outside [0, K) raises
+        a status bit (check_status) and leaves that row as it was"""
+        return self.stack.forward(self.ctx, self._input(obs, B, tag)[1], tag=tag, commands=commands, status=self.status)[1]
+
+    def accumulate_gradients(self, obs, B, commands, actions, grad_scale=1.0, want_y_train=False):
+        """forward, the K head losses against (commands int32 [B], actions fp32 [B, A]), backward: the gradients in
+        params.grads (clipped when clip_gradients is set), the head losses and their total in self.losses,
+        tf.global_norm of the raw gradients in self.norm.  -> what the head launch saved"""
+        ctx = self.ctx
+        acts, x = self._input(obs, B, "train")
+        saved = self.stack.train(ctx, x, commands, actions, self.status, huber=self.huber, loss_weight=self.loss_weight,
+                                 grad_scale=grad_scale, training=getattr(ctx, "bn_training", True),
+                                 want_y_train=want_y_train)
+        self.losses.copy_(saved["losses"])
+        has_trunk = len(self.torso.layers) > 0
+        self.stack.backward(ctx, x, saved, need_dx=has_trunk)
+        if has_trunk:
+            self.torso.backward(ctx, acts)
+        if not self.clip_by_global_norm():
+            self.grad_norm()
+        return saved
+
+    def learn_from_batch(self, obs, B, commands, actions, grad_scale=1.0, sync=None):
+        """one update: accumulate_gradients, then one Adam step"""
+        if sync is not None:
+            raise NotImplementedError("CILNet: data-parallel training is not served")
+        self.accumulate_gradients(obs, B, commands, actions)
+        self.apply_gradients(grad_scale)
+        return self.loss
+
+
 def nec_net_kwargs(np_, alg, seed):
     """NECNetworkParameters + NECAlgorithmParameters -> the keywords of NECNet's constructor"""
     from ..architectures.head_parameters import DNDQHeadParameters

@@ -2070,6 +2070,72 @@ int rlx_dnd_add(const float *embedding, long long ld_e, int T, int width, const 
                 float *values, long long *stamps, int *size, int A, long long *clock, float key_error_threshold,
                 float new_value_shift_coefficient, int *slot_scratch, int *status, void *stream);
 
+/* ---------------------- Conditional Imitation Learning: command-branched regression heads (csrc/cil.hip) -- */
+/* CILAgent's network head (agents/cil_agent.py, heads/cil_head.py RegressionHead with num_output_head_copies = K): K
+ * copies of the MLP  y_k = (act(act(x W1_k + b1_k) W2_k + b2_k)) W3_k + b3_k  over the middleware's output x [B][ld_x],
+ * with dropout behind either hidden activation while training (layers.py BatchnormActivationDropout).  Entry points
+ * ADDED under ABI version 11.  Branch k's tensors sit `stride` floats behind branch k - 1's (a FlatParams group of K
+ * towers): W1 [F][H1], W2 [H1][H2], W3 [H2][A] row-major, biases [H1], [H2], [A].
+ * Served: K in [2, RLX_CIL_MAX_BRANCHES]; F a multiple of 16 in [16, 512]; H1, H2 multiples of 16 in [16, 256]; A in
+ * [1, 16]; B in [1, 1024]; activation NONE, RELU or TANH; x, w1, b1, w2, b2 16-byte aligned with ld_x, stride1 and stride2
+ * multiples of 4; every stride at least its layer's kernel (F * H1, H1 * H2, H2 * A floats).  Anything else is RLX_ERR_INVALID_ARG naming the argument (never padded).
+ * One workgroup (4 waves) per (branch, tile of 16 rows) carries the tile through all three layers: x and both hidden
+ * activations stay in LDS, a wave owns 64 output columns (lane (k, n) the four ADJACENT columns 4 n .. 4 n + 3 of rows
+ * 4 k .. 4 k + 3, one 16-byte weight load per row of W feeding four v_mfma_f32_16x16x4_f32 chains), every sum has one
+ * order: two launches give the same bits.  Rows beyond B and columns beyond A are masked, nothing is read past an operand. */
+#define RLX_CIL_MAX_BRANCHES 8
+#define RLX_CIL_STATUS_BAD_COMMAND 1
+/* Philox stream ids of the dropout masks, behind rlx_normal_fill's 0..4 and rlx_noisy_sample's 5..100 (above):
+ * RLX_CIL_STREAM0 + 2 * branch + layer (layer 0: behind the first hidden activation, 1: behind the second). */
+#define RLX_CIL_STREAM0 128
+typedef struct rlx_cil_desc {
+    const float *x; long long ld_x;
+    const float *w1, *b1; long long stride1;
+    const float *w2, *b2; long long stride2;
+    const float *w3, *b3; long long stride3;
+    int B, F, H1, H2, A, K, activation;
+} rlx_cil_desc;
+/* The clean pass (no dropout; `predict` and acting): y [K][B][A] (may be NULL with values).  commands int32 [B] with
+ * values [B][ld_values] (together, or both NULL): values[b][:] = y[commands[b]][b][:], CILAgent.extract_action_values.
+ * A command outside [0, K) raises RLX_CIL_STATUS_BAD_COMMAND in *status and leaves that row of values untouched. */
+int rlx_cil_branches_forward(const rlx_cil_desc *desc_host, const int *commands, float *y, float *values,
+                             long long ld_values, int *status, void *stream);
+/* CILAgent.learn_from_batch (:75-87) up to the head's gradient: the clean prediction, the training forward and the K
+ * head losses.  Layer 1's pre-activation is shared; from layer 2 on a tile keeps a clean and a dropped accumulator fed
+ * by the same weight loads (with rate1 = rate2 = 0 the dropped ones do not exist).  Target of (branch k, row b): actions
+ * [b][:] (fp32 [B][ld_actions]) if commands[b] == k, otherwise the CLEAN prediction y_k[b][:] -- the reference's
+ * behaviour: under dropout a non-selected branch is regressed towards its own no-dropout output, with rate 0 its error
+ * is exactly 0.  e = y_train - target; head k's loss (heads/head.py:170-177) = loss_weight / B * sum_b sum_a l(e), l = e^2
+ * or, huber != 0, Huber with delta 1; dy [K][B][A] = grad_scale * loss_weight / B * l'(e).  losses [K + 1]: the K head
+ * losses and their total, summed in fp64 in tile, then branch order (a second launch of one wave, no atomics) from
+ * workspace (>= K * ceil(B / 16) doubles).  A command outside [0, K) raises RLX_CIL_STATUS_BAD_COMMAND; the row then
+ * selects no branch.
+ * Dropout: element (row b, column c) of branch k's layer l is kept iff word c % 4 of Philox4x32-10 under the key
+ * (seed, rank) at the counter (b * 64 + c / 4, RLX_CIL_STREAM0 + 2 k + l, draw low word, draw high word ^ 0x4E4F4953 --
+ * rlx_normal_fill's counter layout) is >= floor(rate * 2^32); kept values are multiplied by fp32 1 / (1 - rate).  The
+ * masks are never stored.  *draw (device int64) is READ by the launch, copied to *draw_used and advanced by one by the
+ * second launch: every replay of a captured update draws new masks.  rates in [0, 1).
+ * y [K][B][A]: the clean prediction; y_train (NULL: not wanted): the dropped one; h1 [K][B][H1], h2 [K][B][H2]: the hidden
+ * activations of the training pass after dropout, which rlx_cil_branches_backward and the weight gradients read. */
+int rlx_cil_branches_train(const rlx_cil_desc *desc_host, const int *commands, const float *actions,
+                           long long ld_actions, float rate1, float rate2, int huber, float loss_weight, float grad_scale,
+                           unsigned int seed, unsigned int rank, long long *draw, long long *draw_used, float *y,
+                           float *y_train, float *dy, float *h1, float *h2, float *losses, double *workspace, int *status,
+                           void *stream);
+/* dy -> dz2 [K][B][H2] -> dz1 [K][B][H1], the gradients at the two hidden PRE-activations, per (branch, tile of 16 rows):
+ *   dz2 = (dy W3^T) * mask2 / (1 - rate2) * act'(a2),   dz1 = (dz2 W2^T) * mask1 / (1 - rate1) * act'(a1)
+ * the masks regenerated from *draw_used, a = h * (1 - rate) the activation in front of the dropout (exact where rate = 0).
+ * The weight, bias and input gradients are ordinary products of x, h1, h2, dz1, dz2 and dy (rlx_gemm, batch = K). */
+int rlx_cil_branches_backward(const rlx_cil_desc *desc_host, const float *dy, const float *h1, const float *h2,
+                              float rate1, float rate2, unsigned int seed, unsigned int rank,
+                              const long long *draw_used, float *dz2, float *dz1, void *stream);
+/* CILAgent's view of an observation vector whose width-1 slice `class_column` carries the high-level command
+ * (state_key_with_the_class_index): x [B][ld_x] = the other D - 1 columns of obs [B][ld_obs] in their order (what the
+ * embedder reads), commands [B] = the class column as an integer.  A value that is negative, not integral, not finite
+ * or beyond int32 becomes -1, which the launches above report as RLX_CIL_STATUS_BAD_COMMAND.  B >= 1, D in [2, 4096]. */
+int rlx_cil_split_observation(const float *obs, long long ld_obs, int B, int D, int class_column, float *x,
+                              long long ld_x, int *commands, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
