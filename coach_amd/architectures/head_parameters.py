@@ -22,10 +22,16 @@ class HeadParameters(object):
 
 class QHeadParameters(HeadParameters):
     head_type = "QHead"
+    # the constant the output layer's bias starts from (head_parameters.py:120-130 `output_bias_initializer`; the
+    # reference's Acrobot_DDQN_BCQ_BatchRL.py:37,80 gives constant_initializer(-100)); None: zeros, as everywhere else.
+    # A class default, so that only a head that sets it carries the field
+    output_bias_initializer = None
 
     def __init__(self, activation_function='relu', name='q_head_params',
-                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0):
+                 rescale_gradient_from_head_by_factor=1.0, loss_weight=1.0, output_bias_initializer=None):
         super().__init__(activation_function, name, rescale_gradient_from_head_by_factor, loss_weight)
+        if output_bias_initializer is not None:
+            self.output_bias_initializer = float(output_bias_initializer)
 
 
 class DuelingQHeadParameters(HeadParameters):

@@ -6,7 +6,8 @@ gym, ALE and MuJoCo cannot be installed in this image (no network), so `create(.
 SPACES — observation shape, action space, episode time limit, as gym registers them — and builds the
 device-resident synthetic environment with those spaces (coach_amd/environments/synthetic_vector_environment.py;
 SURVEY.md §8(d) "synthetic fixed-length episodes") — except CartPole-v0 / -v1, whose simulator is restated on the device
-(coach_amd/environments/cartpole_vector_environment.py, gym 0.12.5's physics bit for bit).  The agent, memory, filter and schedule side of a preset is
+(coach_amd/environments/cartpole_vector_environment.py, gym 0.12.5's physics bit for bit), and Pendulum-v0 / Acrobot-v1
+(coach_amd/environments/classic_control_vector_environment.py).  The agent, memory, filter and schedule side of a preset is
 exactly what would run against the real simulator; swapping the simulator in is the (f)3 front end
 (coach_amd/environments/emulator_frontend.py) once gym exists.  An unknown level raises instead of guessing.
 """
@@ -155,9 +156,9 @@ def exploration_chain_parameters(env_params):
 
 def create(env_params, device, rank=0):
     """The `path` target of the parameter classes above: build the environment of a preset on `device`.  CartPole,
-    BitFlip and ExplorationChain are the levels whose simulators exist on the device (csrc/cartpole.hip,
-    csrc/bit_flip.hip, csrc/exploration_chain.hip); every other level gets the synthetic environment with the level's
-    spaces."""
+    Pendulum-v0, Acrobot-v1, BitFlip and ExplorationChain are the levels whose simulators exist on the device
+    (csrc/cartpole.hip, csrc/classic_control.hip, csrc/bit_flip.hip, csrc/exploration_chain.hip); every other level gets
+    the synthetic environment with the level's spaces (and so do the first three under `env_params.synthetic`)."""
     from .synthetic_vector_environment import SyntheticVectorEnvironment
     name = env_params.level_name()
     if name in ('CartPole-v0', 'CartPole-v1') and not getattr(env_params, "synthetic", False):
@@ -165,6 +166,11 @@ def create(env_params, device, rank=0):
         return CartPoleVectorEnvironment(
             CartPoleVectorEnvironmentParameters(env_params.num_envs, name, env_params.seed, env_params.episode_length),
             device, rank=rank)
+    if name in ('Pendulum-v0', 'Acrobot-v1') and not getattr(env_params, "synthetic", False):
+        from . import classic_control_vector_environment as cc
+        env, par = (cc.PendulumVectorEnvironment, cc.PendulumVectorEnvironmentParameters) if name == 'Pendulum-v0' \
+            else (cc.AcrobotVectorEnvironment, cc.AcrobotVectorEnvironmentParameters)
+        return env(par(env_params.num_envs, name, env_params.seed, env_params.episode_length), device, rank=rank)
     if name == BIT_FLIP_LEVEL:
         from .bit_flip_vector_environment import BitFlipVectorEnvironment
         return BitFlipVectorEnvironment(bit_flip_parameters(env_params), device, rank=rank)

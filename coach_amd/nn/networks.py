@@ -538,10 +538,12 @@ def dqn_net_kwargs(np_, seed):
     """a DQN-family network's parameters object (DQNNetworkParameters and its subclasses) -> the keywords of DQNNet's
     constructor; `noisy` and a subclass's own arguments (atoms, heads) are the caller's."""
     head = np_.heads_parameters[0]
+    bias = getattr(head, "output_bias_initializer", None)       # QHeadParameters alone has it; passed on only when set
     return dict(common_net_kwargs(np_, seed), replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss,
                 dueling=isinstance(head, DuelingQHeadParameters), head_activation=head.activation_function,
                 head_gradient_rescale=head.rescale_gradient_from_head_by_factor,
-                clip_gradients=getattr(np_, "clip_gradients", None))
+                clip_gradients=getattr(np_, "clip_gradients", None),
+                **({} if bias is None else {"output_bias": float(bias)}))
 
 
 class DQNNet(_NetBase):
@@ -555,8 +557,12 @@ class DQNNet(_NetBase):
     def __init__(self, device, obs_shape, n_actions, activation="relu", embedder="Medium",
                  middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99,
                  optimizer_epsilon=1e-4, replace_mse_with_huber_loss=True, seed=0, dueling=False,
-                 head_activation="relu", head_gradient_rescale=1.0, clip_gradients=None, noisy=False):
-        """noisy: ParameterNoise's network — every dense layer (embedder, middleware, head) is a G.NoisyDense."""
+                 head_activation="relu", head_gradient_rescale=1.0, clip_gradients=None, noisy=False,
+                 output_bias=None):
+        """noisy: ParameterNoise's network — every dense layer (embedder, middleware, head) is a G.NoisyDense.
+        output_bias: the constant the plain Q head's output bias starts from, online and target (None: zeros)."""
+        if output_bias is not None and (dueling or noisy):
+            raise ValueError("output_bias_initializer is served by the plain QHead only (not dueling, not noisy)")
         self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, n_actions
         self.huber = replace_mse_with_huber_loss
         self.dueling = dueling
@@ -587,6 +593,9 @@ class DQNNet(_NetBase):
             self.q_head = self._q_head_layer(feat, n_actions)
             self.modules = [self.torso, self.q_head]
         self._finish(device, seed, learning_rate, adam_beta1, adam_beta2, optimizer_epsilon)
+        if output_bias is not None:
+            for buf in (self.params.weights, self.target):
+                self.params.w(self.q_head.bname, 0, buf).fill_(float(output_bias))
         self.loss = torch.zeros(1, dtype=torch.float32, device=device)
         self.l2_norm = torch.zeros(1, dtype=torch.float32, device=device)
         mids = FC_MIDDLEWARE[middleware] if isinstance(middleware, str) else middleware

@@ -1348,6 +1348,30 @@ int rlx_cartpole_step(const int *action, double *state, int *episode, int *steps
 /* sin / cos rounded like the host libm's (csrc/libm_sincos.hpp) — exposed for tests/test_cartpole.py */
 int rlx_libm_sincos(const double *x, double *sin_out, double *cos_out, int n, int *status, void *stream);
 
+/* ------------------------------------------------------------ Pendulum-v0 / Acrobot-v1 (classic_control.hip) -- */
+/* N Pendulum / Acrobot environments per GPU: gym 0.12.5's physics (gym/envs/classic_control/pendulum.py, acrobot.py with
+ * "book" dynamics, one RK4 step of 0.2 s, no torque noise) in fp64 behind gym's TimeLimit (max_episode_steps: 200 /
+ * 500), shaped like rlx_cartpole_*: the same arguments with the same meaning.
+ * Pendulum: state fp64[n_env][2] (th, thdot), th never wrapped; action fp32[n_env][1], clipped to [-2, 2]; observations
+ * fp32[n_env][3] (cos th, sin th, thdot); reward = -cost; game_over by the time limit only.
+ * Acrobot: state fp64[n_env][4] (theta1, theta2, dtheta1, dtheta2); action int32[n_env] in {0, 1, 2} (torque -1, 0, +1);
+ * observations fp32[n_env][6] (cos t1, sin t1, cos t2, sin t2, dt1, dt2); reward -1, 0 on the terminal step.
+ * status: bit 0 = a sin / cos argument outside rlx::libm_sin_full's range (|x| < 2^20), bit 1 = an Acrobot action outside
+ * {0, 1, 2} or a non-finite Pendulum action: that env keeps its state on that step (reward 0) and the step counts. */
+int rlx_pendulum_reset(double *state, float *obs, int *episode, int *steps, int n_env, unsigned int seed,
+                       unsigned int env_id0, int next_episode, void *stream);
+int rlx_pendulum_step(const float *action, double *state, int *episode, int *steps, float *next_obs, float *reset_obs,
+                      double *next_state64, float *reward, unsigned char *game_over, int n_env,
+                      int max_episode_steps, unsigned int seed, unsigned int env_id0, int *status, void *stream);
+int rlx_acrobot_reset(double *state, float *obs, int *episode, int *steps, int n_env, unsigned int seed,
+                      unsigned int env_id0, int next_episode, void *stream);
+int rlx_acrobot_step(const int *action, double *state, int *episode, int *steps, float *next_obs, float *reset_obs,
+                     double *next_state64, float *reward, unsigned char *game_over, int n_env, int max_episode_steps,
+                     unsigned int seed, unsigned int env_id0, int *status, void *stream);
+/* full-range sin / cos rounded like the host libm's (csrc/libm_sincos_full.hpp) — exposed for
+ * tests/test_classic_control.py.  status bit 0: an argument with |x| >= 2^20 (the ordinary sin / cos is returned) */
+int rlx_libm_sincos_full(const double *x, double *sin_out, double *cos_out, int n, int *status, void *stream);
+
 
 /* ------------------------------------------------------------ fused continuous-control updates (ac_fused.hip) -- */
 /* A 2-hidden-layer MLP inside a flat parameter buffer: float offsets of the three layers' kernels ([in][out], TF layout)
