@@ -117,6 +117,8 @@ class ClippedPPOAgent(object):
     def __init__(self, agent_parameters, environment, device=None, dist=None, use_graphs=None):
         self.ap = agent_parameters
         refuse_lstm_middleware(agent_parameters, type(self).__name__)
+        from .vector_agent import check_network_precision
+        check_network_precision(type(self).__name__, agent_parameters, environment, dist)     # (bf16: refused by name)
         self.env = environment
         self.device = device or environment.device
         self.dist = dist if (dist is not None and dist.enabled) else None

@@ -306,6 +306,7 @@ class DQNAgent(VectorOffPolicyAgent):
         # (ParameterNoise: the record's epsilon-greedy draws do not exist; act() + train() run as they are)
         return (self.use_graphs and self.dist is None and self.phase == RunPhase.TRAIN and not self.image
                 and not self.parameter_noise and not self.store_action_probabilities
+                and getattr(self.networks["main"], "precision", "fp32") == "fp32"     # (a bf16 update is a graph of its own)
                 and type(self.memory) is ExperienceReplay and self.signal_stats is None
                 and self.debug_draws is None and self.debug_losses is None
                 and hasattr(self.env, "launch_step") and hasattr(self.env, "host_tick"))

@@ -245,6 +245,31 @@ class _HostDrawsAhead(object):
         self._t.join()
 
 
+BF16_AGENTS = ("DQNAgent", "DDQNAgent")
+
+
+def check_network_precision(agent_name, agent_parameters, environment, dist):
+    """network_wrappers[...].precision (base_parameters.NetworkParameters), checked before anything touches the device: an
+    unknown value is rejected; "bf16" is served where the network is DQNNet with the plain Q head on a vector
+    observation, one GPU, epsilon-greedy — and refused by name everywhere else."""
+    from ..architectures.head_parameters import DuelingQHeadParameters
+    from ..exploration_policies.parameter_noise import ParameterNoiseParameters
+    from ..nn.graph import check_precision
+    from ..nn.networks import BF16_SERVED
+    for wrapper in agent_parameters.network_wrappers.values():
+        if check_precision(getattr(wrapper, "precision", "fp32")) == "fp32":
+            continue
+        heads = getattr(wrapper, "heads_parameters", None) or [None]
+        for what, refused in ((agent_name, agent_name not in BF16_AGENTS),
+                              ("image observations", environment.p.kind == "image"),
+                              ("the ParameterNoise exploration policy",
+                               isinstance(getattr(agent_parameters, "exploration", None), ParameterNoiseParameters)),
+                              ("the dueling head", isinstance(heads[0], DuelingQHeadParameters)),
+                              ("data-parallel training", dist is not None and dist.enabled)):
+            if refused:
+                raise ValueError("%s, not for %s" % (BF16_SERVED, what))
+
+
 class VectorOffPolicyAgent(GraphRunner):
     continuous = False
     # signals every agent registers (agent.py:187-192), in registration order; subclasses append their own.
@@ -259,6 +284,7 @@ class VectorOffPolicyAgent(GraphRunner):
         if not self.LSTM_MIDDLEWARE:
             refuse_lstm_middleware(agent_parameters, type(self).__name__)
         self.noise_source = self._resolve_noise_source()          # (checked before anything touches the device)
+        check_network_precision(type(self).__name__, agent_parameters, environment, dist)
         self.env = environment
         self.device = device or environment.device
         self.dist = dist if (dist is not None and dist.enabled) else None

@@ -3,6 +3,7 @@
 presets reach into NetworkParameters (base_parameters.py:226-305, embedder_parameters.py, middleware_parameters.py).
 The device network parameter classes keep flat fields (`embedder_scheme`, `middleware_scheme`, ...); this mixin
 gives them the reference's nested access path as live views onto those fields."""
+from ..base_parameters import NetworkParameters
 from .layers import scheme_to_native
 
 
@@ -64,7 +65,7 @@ class _EmbedderViews(dict):
         super().__setitem__(key, self._owner.input_embedders_parameters[key])
 
 
-class SchemeViews(object):
+class SchemeViews(NetworkParameters):
     """Mix into a network-parameters class.  _EMBEDDER_FIELDS: {'observation': field[, 'action': field]};
     _TUPLE_SCHEMES: the fields hold tuples of unit counts (actor-critic nets) instead of names / lists."""
     _EMBEDDER_FIELDS = {"observation": "embedder_scheme"}

@@ -51,6 +51,14 @@ class Parameters(object):
         return "\"{}\" {}\n".format(self.__class__.__name__, json.dumps(self.__dict__, indent=4, default=repr))
 
 
+class NetworkParameters(object):
+    """What every network-parameters class of this engine shares (they keep flat fields and mix in
+    architectures/scheme_views.SchemeViews, which derives from this).  Device-engine addition, no reference counterpart:
+    `precision` — "fp32" (default) or "bf16": the dense layers' products on the bf16 matrix pipe with fp32 sums, weights
+    and optimizer state in fp32 as before; served for vector-observation DQN / Double DQN, refused by name elsewhere."""
+    precision = "fp32"
+
+
 class VisualizationParameters(Parameters):
     def __init__(self, print_networks_summary=False, dump_csv=True, dump_signals_to_csv_every_x_episodes=5,
                  dump_gifs=False, dump_mp4=False, video_dump_methods=None, dump_in_episode_signals=False,

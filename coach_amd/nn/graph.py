@@ -400,14 +400,44 @@ class Layer:
 FUSED_ACTS = (None, "relu", "tanh")
 
 
-class Dense(Layer):
-    """y = act(x W + b), tf.layers.dense (layers.py:168-185).  `towers` copies in one launch."""
+PRECISIONS = ("fp32", "bf16")
 
-    def __init__(self, params, name, in_features, units, activation=None, towers=1, init=None):
+
+def check_precision(precision):
+    """-> precision, one of PRECISIONS: the format of a dense layer's PRODUCTS (memory stays fp32 either way)."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (", ".join(map(repr, PRECISIONS)), precision))
+    return precision
+
+
+def _fp32_only(layer, option):
+    """a launch that computes a Dense layer inside another kernel declines a bf16 layer by name"""
+    if getattr(layer, "precision", "fp32") != "fp32":
+        raise ValueError("%s: layer %s has precision=%r, which takes the plain layer-by-layer launches only"
+                         % (option, layer.name, layer.precision))
+
+
+class Dense(Layer):
+    """y = act(x W + b), tf.layers.dense (layers.py:168-185).  `towers` copies in one launch.
+    precision="bf16": the three products of the layer (forward, input gradient, weight gradient) run on the bf16 matrix
+    pipe with fp32 sums (csrc/gemm_bf16.hip: operands rounded once on their way into LDS; weights, activations,
+    gradients and the Adam state stay fp32 in memory) as launches of their own, one tower."""
+
+    def __init__(self, params, name, in_features, units, activation=None, towers=1, init=None, precision="fp32"):
         self.name, self.K, self.N, self.act, self.T = name, in_features, units, activation, towers
+        self.set_precision(precision)
         self.init, self.params = init, params
         self.kname, self.bname = name + "/kernel", name + "/bias"
         params.add_group([(self.kname, (in_features, units)), (self.bname, (units,))], towers)
+
+    def set_precision(self, precision):
+        """which launches forward and backward take; memory, parameters and initialisation are the same either way"""
+        if check_precision(precision) != "fp32":
+            if self.T != 1:
+                raise ValueError("towers=%d: a %s Dense layer has one tower" % (self.T, precision))
+            if self.act not in FUSED_ACTS:
+                raise ValueError("activation=%r: a %s Dense layer serves none, relu and tanh" % (self.act, precision))
+        self.precision = precision
 
     def group_range(self):
         """[lo, hi) of the flat buffers: kernel and bias of ALL towers (the layer's FlatParams group, contiguous)."""
@@ -430,6 +460,16 @@ class Dense(Layer):
         p = self.params
         M = x.rows
         assert x.cols == self.K, (self.name, x.cols, self.K)
+        if self.precision == "bf16":
+            for option, asked in (("pair", pair), ("row_heads", row_heads), ("launch=False", not launch)):
+                if asked:
+                    _fp32_only(self, option)
+            if x.u8 or x.towers not in (0, 1):
+                raise ValueError("a bf16 Dense layer reads one tower of fp32 rows (layer %s)" % self.name)
+            y = ctx.buffer(self.name, (1, M, self.N), tag=tag)
+            ctx.lib.dense_bf16_forward(x.data, self.K, p.w(self.kname, t0, weights), self.N, p.w(self.bname, t0, weights),
+                                       y, self.N, M, self.K, self.N, _rlx.ACT[self.act], ctx.stream)
+            return Tensor(y, M, self.N, 1, grad_key=(ctx, self.name, tag), act=self.act)
         wstride, bstride = p.stride(self.kname), p.stride(self.bname)
         kw = {}
         if pair:
@@ -502,6 +542,21 @@ class Dense(Layer):
         overlap = overlap and ctx.overlap
         dz = y.grad
         own_act = self.act if (self.act is not None and not y.grad_is_dz) else None
+        if self.precision == "bf16":
+            # the activation's derivative stays a launch of its own on dz (this layer's here; the lower layer applies its
+            # own: x.grad_is_dz stays False), then dW + db and dX as the two bf16 products.  Deliberately left aside:
+            # `overlap` (one stream) and Context.early_adam -- the gradients ARE final after the launch, but nothing is
+            # appended to ea.final: an armed early Adam step never counts this layer's range among the early ones
+            if own_act is not None:
+                ctx.lib.act_backward(dz, y.data, M * self.N, _rlx.ACT[own_act], ctx.stream)
+            if need_dw:
+                ctx.lib.dense_bf16_weight_grad(x.data, self.K, dz, self.N, p.g(self.kname, t0), self.N,
+                                               p.g(self.bname, t0), M, self.K, self.N, ctx.stream)
+            if need_dx:
+                ctx.lib.dense_bf16_input_grad(dz, self.N, p.w(self.kname, t0, weights), self.N, x.ensure_grad(), self.K,
+                                              M, self.K, self.N, ctx.stream)
+                x.grad_is_dz = False
+            return
         lower = x.act if need_dx else None           # fuse the lower layer's act' into dx
         shared_dx = need_dx and x.towers == 0 and T > 1     # T streams fed by ONE input: dx sums them
         if need_dx and not shared_dx:
@@ -1074,6 +1129,8 @@ class Conv2d(Layer):
 def row_head_problems(ctx, row_heads, y, M, N, tag, weights=None):
     """rlx_gemm_desc.row_heads for [(narrow Dense layer, tower index of the wide layer's output it reads)]: the ctypes
     array and the heads' output Tensors (what small_dense_forward_multi would have returned)."""
+    for item in row_heads:
+        _fp32_only(item[0], "row_heads")
     if row_heads and row_heads[0][1] == "pair":
         # [(layer, "pair")]: the wide layer ran the online and the target copy as batch entries 0 and 1 (Dense.forward
         # pair=True); the head does the same — ONE output Tensor with two towers, as its own pair launch returns
@@ -1121,6 +1178,7 @@ def small_dense_forward_multi(ctx, items, tag="", weights=None):
     arr = (_rlx.SmallDenseProblem * len(items))()
     outs = []
     for i, (l, x) in enumerate(items):
+        _fp32_only(l, "small_dense_forward_multi")
         assert l.N <= SMALL_N and not x.u8 and x.cols == l.K and x.towers in (0, l.T)
         M, p = x.rows, l.params
         y = ctx.buffer(l.name, (l.T, M, l.N), tag=tag)
@@ -1137,6 +1195,7 @@ def small_dense_forward_multi(ctx, items, tag="", weights=None):
 
 def _small_backward_problem(q, l, x, y):
     """rlx_small_dense_problem of one narrow layer's backward pass (y.grad = gradient w.r.t. its output)."""
+    _fp32_only(l, "the narrow layers' one-launch backward pass")
     M, p = x.rows, l.params
     assert l.N <= SMALL_N and M * l.N <= 1024 and x.towers == l.T
     own = l.act if (l.act is not None and not y.grad_is_dz) else None
@@ -1187,6 +1246,8 @@ def ppo_fc_rows(ctx, layer, x, v_head, pi_head, value_targets, actions, advantag
     (nothing launched).  The all-rows part (the heads' dW / db, the loss scalars) is left pending on the context:
     Context.flush_deferred takes it along with the backward pass's reductions; tail_now: launched here (a caller that
     reads the heads' gradients before the torso's backward pass has ended)."""
+    for l in (layer, v_head, pi_head):
+        _fp32_only(l, "ppo_fc_rows")
     p, hp = layer.params, v_head.params
     if not (layer.T == 2 and x.towers == 2 and not x.u8 and x.cols == layer.K and v_head.T == 1 and pi_head.T == 1 and
             v_head.N == 1 and 2 <= pi_head.N <= SMALL_N and v_head.K == layer.N and pi_head.K == layer.N and
@@ -1238,6 +1299,8 @@ def ppo_fc_rows(ctx, layer, x, v_head, pi_head, value_targets, actions, advantag
 def ppo_fc_heads_supported(ctx, layer, x, v_head, pi_head):
     """Can rlx_ppo_fc_heads run `layer` (the torso's last Dense, two towers) + both discrete heads + losses + the heads'
     backward pass as one launch?"""
+    for l in (layer, v_head, pi_head):
+        _fp32_only(l, "ppo_fc_heads")
     return (isinstance(layer, Dense) and layer.act in FUSED_ACTS and layer.T == 2 and x.towers == 2 and not x.u8 and v_head.T == 1 and pi_head.T == 1 and
             v_head.N == 1 and v_head.K == layer.N and pi_head.K == layer.N and v_head.act is None and pi_head.act is None and
             x.data.data_ptr() % 16 == 0 and layer.params.stride(layer.kname) % 4 == 0 and
@@ -1249,6 +1312,8 @@ def ppo_fc_heads(ctx, layer, x, v_head, pi_head, value_targets, actions, advanta
     """-> (mid, v, logits): the layer's output Tensor with mid.grad = d loss / d pre-activation (grad_is_dz), the heads'
     outputs with their gradients; the heads' weight gradients are in params.grads (rlx_ppo_fc_heads: one launch)."""
     import ctypes
+    for l in (layer, v_head, pi_head):
+        _fp32_only(l, "ppo_fc_heads")
     p, B, N, K = layer.params, x.rows, layer.N, layer.K
     y = ctx.buffer(layer.name, (2, B, N), tag=tag)
     mid = Tensor(y, B, N, 2, grad_key=(ctx, layer.name, tag), act=layer.act)
@@ -1292,10 +1357,18 @@ def ppo_fc_heads(ctx, layer, x, v_head, pi_head, value_targets, actions, advanta
 
 
 class Sequential:
-    """A chain of Dense / Conv2d layers replicated over `towers` identical copies."""
+    """A chain of Dense / Conv2d layers replicated over `towers` identical copies.
+    precision: given, it is handed to every layer of the chain — "bf16" asks for a chain of plain Dense layers (no other
+    layer class has bf16 products) and switches them to the bf16 launches; None leaves the layers as they were built."""
 
-    def __init__(self, layers):
+    def __init__(self, layers, precision=None):
         self.layers = layers
+        if precision is not None and check_precision(precision) != "fp32":
+            for l in layers:
+                if type(l) is not Dense:
+                    raise ValueError("precision=%r is served for Dense layers only, not %s" % (precision, type(l).__name__))
+            for l in layers:
+                l.set_precision(precision)
 
     def initialize(self, rng):
         for l in self.layers:

@@ -19,10 +19,15 @@ VECTOR_EMBEDDER = {"Medium": [256], "Shallow": [128], "Empty": []}
 FC_MIDDLEWARE = {"Medium": [512], "Shallow": [64], "Empty": []}
 
 
-def build_torso(params, prefix, obs_shape, activation, towers, embedder="Medium", middleware="Medium", noisy=False):
+BF16_SERVED = "precision='bf16' is served for vector-observation DQN / Double DQN only"
+
+
+def build_torso(params, prefix, obs_shape, activation, towers, embedder="Medium", middleware="Medium", noisy=False,
+                precision="fp32"):
     """input embedder + FC middleware.  obs_shape (H, W, C) -> image embedder on uint8 frames
     (input / 255, embedder_parameters.py:33-36), (D,) -> vector embedder.
-    noisy: every dense layer is a factorised NoisyNet layer (G.NoisyDense; the convolutions stay)."""
+    noisy: every dense layer is a factorised NoisyNet layer (G.NoisyDense; the convolutions stay).
+    precision: "bf16" hands the chain to G.Sequential with it (plain Dense layers only: a vector observation, not noisy)."""
     layers = []
     Dense = G.NoisyDense if noisy else G.Dense
     if len(obs_shape) == 3:
@@ -43,6 +48,8 @@ def build_torso(params, prefix, obs_shape, activation, towers, embedder="Medium"
     for i, u in enumerate(mids):
         layers.append(Dense(params, "%s/middleware/dense%d" % (prefix, i), feat, u, activation, towers))
         feat = u
+    if precision != "fp32":
+        return G.Sequential(layers, precision=precision), feat
     return G.Sequential(layers), feat
 
 
@@ -518,9 +525,12 @@ class ClippedPPONet(_NetBase):
         return self.scalars
 
 
-def common_net_kwargs(np_, seed):
+def common_net_kwargs(np_, seed, serves_bf16=False):
     """a network parameters object -> the constructor keywords every network here takes: the torso's schemes and
-    activation, Adam's constants and the seed"""
+    activation, Adam's constants and the seed.  A network class without bf16 layers refuses the parameter here, by name
+    (dqn_net_kwargs hands it to DQNNet, which serves it)."""
+    if G.check_precision(getattr(np_, "precision", "fp32")) != "fp32" and not serves_bf16:
+        raise ValueError("%s (got it in %s)" % (BF16_SERVED, type(np_).__name__))
     return dict(activation=np_.activation_function, embedder=np_.embedder_scheme, middleware=np_.middleware_scheme,
                 learning_rate=np_.learning_rate, adam_beta1=np_.adam_optimizer_beta1, adam_beta2=np_.adam_optimizer_beta2,
                 optimizer_epsilon=np_.optimizer_epsilon, seed=seed)
@@ -539,11 +549,13 @@ def dqn_net_kwargs(np_, seed):
     constructor; `noisy` and a subclass's own arguments (atoms, heads) are the caller's."""
     head = np_.heads_parameters[0]
     bias = getattr(head, "output_bias_initializer", None)       # QHeadParameters alone has it; passed on only when set
-    return dict(common_net_kwargs(np_, seed), replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss,
+    precision = getattr(np_, "precision", "fp32")               # passed on only when set, as output_bias
+    return dict(common_net_kwargs(np_, seed, serves_bf16=True), replace_mse_with_huber_loss=np_.replace_mse_with_huber_loss,
                 dueling=isinstance(head, DuelingQHeadParameters), head_activation=head.activation_function,
                 head_gradient_rescale=head.rescale_gradient_from_head_by_factor,
                 clip_gradients=getattr(np_, "clip_gradients", None),
-                **({} if bias is None else {"output_bias": float(bias)}))
+                **({} if bias is None else {"output_bias": float(bias)}),
+                **({} if precision == "fp32" else {"precision": precision}))
 
 
 class DQNNet(_NetBase):
@@ -558,11 +570,20 @@ class DQNNet(_NetBase):
                  middleware="Medium", learning_rate=2.5e-4, adam_beta1=0.9, adam_beta2=0.99,
                  optimizer_epsilon=1e-4, replace_mse_with_huber_loss=True, seed=0, dueling=False,
                  head_activation="relu", head_gradient_rescale=1.0, clip_gradients=None, noisy=False,
-                 output_bias=None):
+                 output_bias=None, precision="fp32"):
         """noisy: ParameterNoise's network — every dense layer (embedder, middleware, head) is a G.NoisyDense.
-        output_bias: the constant the plain Q head's output bias starts from, online and target (None: zeros)."""
+        output_bias: the constant the plain Q head's output bias starts from, online and target (None: zeros).
+        precision: "bf16" — every Dense of the torso and the Q head multiplies on the bf16 matrix pipe (G.Dense), online
+        and target alike; the update goes layer by layer (no one-launch MLP update or acting step, no paired launches)."""
         if output_bias is not None and (dueling or noisy):
             raise ValueError("output_bias_initializer is served by the plain QHead only (not dueling, not noisy)")
+        self.precision = G.check_precision(precision)
+        if precision != "fp32":
+            for what, refused in (("a %s" % type(self).__name__, type(self) is not DQNNet),
+                                  ("image observations", len(obs_shape) == 3),
+                                  ("noisy layers (ParameterNoise)", noisy), ("the dueling head", dueling)):
+                if refused:
+                    raise ValueError("%s, not for %s" % (BF16_SERVED, what))
         self.obs_shape, self.image, self.A = tuple(obs_shape), len(obs_shape) == 3, n_actions
         self.huber = replace_mse_with_huber_loss
         self.dueling = dueling
@@ -571,7 +592,7 @@ class DQNNet(_NetBase):
         self.clip_gradients = clip_gradients
         self.params = G.FlatParams()
         self.torso, feat = build_torso(self.params, "main", obs_shape, activation, 1, embedder, middleware,
-                                       noisy=self.noisy)
+                                       noisy=self.noisy, precision=precision)
         if dueling and self.noisy:
             # the same head from noisy layers: the two fc1 streams are layers of their own (a NoisyDense has one tower:
             # each stream draws its own noise), so the towers-of-one-launch and multi-problem shortcuts are declined
@@ -606,6 +627,8 @@ class DQNNet(_NetBase):
 
     def _q_head_layer(self, feat, units):
         """the plain head's output layer (a subclass with its own initialisation builds its own)"""
+        if self.precision != "fp32":
+            return G.Dense(self.params, "main/q_head/dense", feat, units, None, 1, precision=self.precision)
         return (G.NoisyDense if self.noisy else G.Dense)(self.params, "main/q_head/dense", feat, units, None, 1)
 
     # ---------------------------------------------------------------- noisy layers (ParameterNoise)
@@ -645,6 +668,8 @@ class DQNNet(_NetBase):
         csrc/mlp_fused.hip take -> ((obs_dim, h1, h2), the six offsets of w1, b1, w2, b2, w3, b3 in the flat buffer),
         or None for any other network."""
         ls = self.torso.layers
+        if self.precision != "fp32":          # (the one-launch kernels multiply in fp32: a bf16 network goes layer by layer)
+            return None
         if self.image or self.dueling or len(ls) != 2 or \
                 any(not isinstance(l, G.Dense) or l.act != "relu" or l.T != 1 for l in ls):
             return None
@@ -810,7 +835,7 @@ class DQNNet(_NetBase):
         """the target network on s' and the online network on s -> (acts, q, saved, q_next): the online pass as the
         backward pass needs it (saved: the dueling head's tensors, else None) and the target's head output [B, width]."""
         ctx, saved = self.ctx, None
-        if states_pair is not None and not self.dueling and not self.noisy:
+        if states_pair is not None and not self.dueling and not self.noisy and self.precision == "fp32":
             # parallel_prediction (dqn_agent.py:86-89): online(s) and target(s') as two towers of the
             # same launches — the replay collates states / next_states into one [2, B, ...] buffer
             cols = int(np.prod(self.obs_shape))
@@ -873,6 +898,8 @@ class DQNNet(_NetBase):
         caller's own select_actions (DDQN-BCQ's masked online Q values, agents/ddqn_bcq_agent.py).  With it the update
         goes layer by layer (the one-launch small-MLP update computes its own selection) and double_dqn is not read."""
         ctx = self.ctx
+        if self.precision != "fp32" and sync is not None:
+            raise ValueError("%s, not for data-parallel training" % BF16_SERVED)
         if selector is None and self._fused is not None and sync is None and B <= 32 and obs.is_contiguous() and \
                 next_obs.is_contiguous():
             w = importance_weights
@@ -897,7 +924,7 @@ class DQNNet(_NetBase):
             feat = acts[-1]
             if self.HEAD_LOSS_BACKWARD_ONE_LAUNCH and not self.dueling and self.head_gradient_rescale == 1.0 and \
                     self.q_head.T == 1 and self.A <= G.SMALL_N and B * self.A <= 1024 and B <= 256 and not feat.u8 and \
-                    feat.towers == 1 and not self.noisy:
+                    feat.towers == 1 and not self.noisy and self.precision == "fp32":
                 # TD targets, |TD errors|, loss, dQ AND the Q head's backward pass (dW, db, dz of the last dense layer) in
                 # one launch (rlx_dqn_head_loss_backward): what the two calls of the other branch compute, bit for bit
                 import ctypes

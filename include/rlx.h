@@ -618,6 +618,24 @@ int rlx_conv_tables(int *rowbase, int *koff, int batch, int H, int W, int C, int
 int rlx_col2im(const float *dcol, float *dx, const float *x_out, int deriv_kind, int batch, int H,
                int W, int C, int KH, int KW, int stride, void *stream); /* conv input gradient */
 
+/* ------------------------------------- dense layer, bf16 products (bf16 MFMA) -- */
+/* tf.layers.dense and its gradients (architectures/tensorflow_components/layers.py:168-185) on the bf16 matrix pipe
+ * (csrc/gemm_bf16.hip; the reference has no mixed-precision path: an opt-in of this engine, G.Dense(precision="bf16")).
+ *   rlx_dense_bf16_forward      y[M, N]  = act(x[M, K] w[K, N] + bias[N])     activation <= RLX_ACT_TANH; bias NULL: none
+ *   rlx_dense_bf16_input_grad   dx[M, K] = dz[M, N] w^T
+ *   rlx_dense_bf16_weight_grad  dw[K, N] = x^T dz,  db[N] = column sums of dz (fp32 sums of the fp32 values; NULL: not wanted)
+ * Everything in memory is fp32, rows ld* elements apart (ld >= the row's width).  Each operand element of a product is
+ * rounded to bf16 (nearest even; NaN and Inf kept) once, on its way into LDS; products are exact, sums are fp32, in an
+ * order fixed by (M, K, N): no atomics, no partial sums in memory, so two launches agree bit for bit.  dz is taken as
+ * given: the caller multiplies by the activation's derivative first (rlx_act_backward).  1 <= M <= 4096,
+ * 1 <= K, N <= 8192, any raggedness; nothing is padded by the caller. */
+int rlx_dense_bf16_forward(const float *x, long long ldx, const float *w, long long ldw, const float *bias, float *y,
+                           long long ldy, int M, int K, int N, int activation, void *stream);
+int rlx_dense_bf16_input_grad(const float *dz, long long lddz, const float *w, long long ldw, float *dx, long long lddx,
+                              int M, int K, int N, void *stream);
+int rlx_dense_bf16_weight_grad(const float *x, long long ldx, const float *dz, long long lddz, float *dw, long long lddw,
+                               float *db, int M, int K, int N, void *stream);
+
 /* Batch normalisation after a dense layer — the `use_batchnorm=True` DDPG networks (agents/ddpg_agent.py:37-60;
  * architectures/tensorflow_components/layers.py:26-55 -> tf.layers.batch_normalization: momentum 0.99, epsilon 1e-3).
  * x, y, dy, dx: [batch][channels] fp32, rows contiguous; gamma, beta, statistics: [channels].
