@@ -119,6 +119,8 @@ class ClippedPPOAgent(object):
         refuse_lstm_middleware(agent_parameters, type(self).__name__)
         from .vector_agent import check_network_precision
         check_network_precision(type(self).__name__, agent_parameters, environment, dist)     # (bf16: refused by name)
+        from ..exploration_policies import check_exploration_served
+        check_exploration_served(type(self).__name__, agent_parameters)
         self.env = environment
         self.device = device or environment.device
         self.dist = dist if (dist is not None and dist.enabled) else None

@@ -16,6 +16,7 @@ from .. import _rlx
 from ..architectures.head_parameters import QHeadParameters
 from ..architectures.scheme_views import SchemeViews
 from ..core_types import DeviceBatch, EnvironmentSteps, RunPhase
+from ..exploration_policies import Boltzmann, BoltzmannParameters, Greedy, GreedyParameters
 from ..exploration_policies.e_greedy import EGreedy, EGreedyParameters
 from ..exploration_policies.parameter_noise import ParameterNoise, ParameterNoiseParameters, network_is_noisy
 from ..memories.non_episodic.experience_replay import ExperienceReplayParameters
@@ -135,9 +136,23 @@ class DQNAgent(VectorOffPolicyAgent):
             net = self.networks["main"]
             net.noise_seed, net.noise_rank = self._noise_seed, self._noise_rank
 
+    value_policy = False          # (class default: a subclass with a policy of its own never has one)
+
     def _make_exploration_policy(self):
+        """EGreedy, ParameterNoise, or a policy that reads the Q rows itself (Boltzmann, Greedy: `value_policy`).  Those
+        act layer by layer — the Q forward, then the policy's launch — never through the fused one-launch acting step or
+        the one-graph step, whose records carry epsilon-greedy draws; they do not combine with ParameterNoise (a noisy
+        network is refused above with any policy but ParameterNoise)."""
+        p = self.ap.exploration
+        self.value_policy = isinstance(p, (BoltzmannParameters, GreedyParameters))
+        if self.value_policy and self.store_action_probabilities:
+            raise ValueError("should_get_softmax_probabilities is served with the EGreedy exploration policy")
+        if isinstance(p, BoltzmannParameters):
+            return Boltzmann(self.A, self.n_env, self.device, p)
+        if isinstance(p, GreedyParameters):
+            return Greedy(self.n_env, self.device, self.A)
         cls = ParameterNoise if self.parameter_noise else EGreedy
-        return cls(self.A, self.n_env, self.device, self.ap.exploration)
+        return cls(self.A, self.n_env, self.device, p)
 
     # ----------------------------------------------------------- all_action_probabilities (off-policy evaluation)
     store_action_probabilities = False        # (class defaults: a subclass with a constructor of its own never stores them)
@@ -220,6 +235,10 @@ class DQNAgent(VectorOffPolicyAgent):
         if self.parameter_noise:
             # noisy forward pass (fresh noise, read from the device counters) + np.argmax: no host draw at all
             self._run(("q_argmax", self.n_env), lambda: (self._q_forward(states), self._argmax_actions()))
+            return self.actions
+        if self.value_policy:
+            self._run(("q", self.n_env), lambda: self._q_forward(states))
+            self.exploration_policy.act(self._q_act, self.A, self.actions)
             return self.actions
         draws = self.exploration_policy.draw()                       # host RNG, per env, in order
         if net.can_act_fused(self.n_env):
@@ -305,7 +324,7 @@ class DQNAgent(VectorOffPolicyAgent):
         from ..memories.non_episodic.experience_replay import ExperienceReplay
         # (ParameterNoise: the record's epsilon-greedy draws do not exist; act() + train() run as they are)
         return (self.use_graphs and self.dist is None and self.phase == RunPhase.TRAIN and not self.image
-                and not self.parameter_noise and not self.store_action_probabilities
+                and not self.parameter_noise and not self.value_policy and not self.store_action_probabilities
                 and getattr(self.networks["main"], "precision", "fp32") == "fp32"     # (a bf16 update is a graph of its own)
                 and type(self.memory) is ExperienceReplay and self.signal_stats is None
                 and self.debug_draws is None and self.debug_losses is None

@@ -98,11 +98,20 @@ class NStepQAgent(PolicyOptimizationAgent):
         return NStepQNet(self.device, obs_shape, self.A, **n_step_q_net_kwargs(wrapper, self.ap.seed or 0))
 
     def _make_exploration_policy(self):
-        return EGreedy(self.A, self.n_env, self.device, self.ap.exploration)
+        from ..exploration_policies import Boltzmann, BoltzmannParameters, Greedy, GreedyParameters
+        p = self.ap.exploration
+        if isinstance(p, BoltzmannParameters):
+            return Boltzmann(self.A, self.n_env, self.device, p)
+        if isinstance(p, GreedyParameters):
+            return Greedy(self.n_env, self.device, self.A)
+        return EGreedy(self.A, self.n_env, self.device, p)
 
     # --------------------------------------------------------------------------------- acting
     def _act_device(self, states, draws):
         q = self.networks["main"].q_values(states, self.n_env, tag="act")
+        if draws is None:                                            # Boltzmann / Greedy read the Q rows themselves
+            self._q_act_rows = q.data
+            return
         eps, d = draws
         self.lib.egreedy(q.data, self.A, d["u"], d["ra"], d["tie"], float(eps), self.n_env, self.A, self.actions,
                          _rlx.current_stream())
@@ -110,6 +119,10 @@ class NStepQAgent(PolicyOptimizationAgent):
     def choose_action(self, states):
         pol = self.exploration_policy
         pol.phase = self.phase
+        if not isinstance(pol, EGreedy):
+            self._run(("q", states.data_ptr()), lambda: self._act_device(states, None))
+            pol.act(self._q_act_rows, self.A, self.actions)
+            return self.actions
         staged = pol.stage(pol.draw())                               # host RNG, per env, in order
         self._run(("act", states.data_ptr()), lambda: self._act_device(states, staged))
         return self.actions

@@ -285,6 +285,8 @@ class VectorOffPolicyAgent(GraphRunner):
             refuse_lstm_middleware(agent_parameters, type(self).__name__)
         self.noise_source = self._resolve_noise_source()          # (checked before anything touches the device)
         check_network_precision(type(self).__name__, agent_parameters, environment, dist)
+        from ..exploration_policies import check_exploration_served
+        check_exploration_served(type(self).__name__, agent_parameters)
         self.env = environment
         self.device = device or environment.device
         self.dist = dist if (dist is not None and dist.enabled) else None
@@ -935,6 +937,9 @@ class VectorOffPolicyAgent(GraphRunner):
         self.memory.check_status()
         for net in self.networks.values():
             net.check_status()
+        pol = getattr(self, "exploration_policy", None)
+        if hasattr(pol, "check"):                  # (Boltzmann, TruncatedNormal: what numpy / scipy would have refused)
+            pol.check()
 
 
 class BoxActionAgent(VectorOffPolicyAgent):
@@ -951,7 +956,15 @@ class BoxActionAgent(VectorOffPolicyAgent):
     def _make_exploration(self):
         from ..exploration_policies.additive_noise import AdditiveNoise
         from ..exploration_policies.ou_process import OUProcess, OUProcessParameters
+        from ..exploration_policies import Greedy, GreedyParameters, TruncatedNormal, TruncatedNormalParameters
         p = self.ap.exploration
+        if isinstance(p, GreedyParameters):
+            return Greedy(self.n_env, self.device)
+        if isinstance(p, TruncatedNormalParameters):
+            pol = TruncatedNormal(self.low, self.high, self.n_env, self.device, p)
+            if self.noise_source == "device":        # the uniforms come from the agent's generator, on a stream of their own
+                pol.device_key = (self._noise_seed, self._noise_rank)
+            return pol
         cls = OUProcess if isinstance(p, OUProcessParameters) else AdditiveNoise
         return cls(self.low, self.high, self.n_env, self.device, p)
 

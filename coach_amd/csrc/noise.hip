@@ -20,11 +20,10 @@
 
 namespace {
 
-constexpr uint32_t kNoiseTag = 0x4E4F4953u;          // "NOIS"
+using rlx::kNoiseTag;
 constexpr int kNoiseStreams = 5;                     // of rlx_normal_fill: 0 TD3 smoothing, 1-3 SAC draws 0-2, 4 acting;
                                                      // 5 and up: the NoisyNet layers (noisy_sample_kernel)
 
-constexpr double kTwoM53 = 1.1102230246251565e-16;   // 2^-53
 constexpr double kTwoM51 = 4.440892098500626e-16;    // 2^-51
 constexpr double kSqrt2 = 1.4142135623730951;
 constexpr double kLn2Hi = 0.6931471803691238;        // 0x1.62e42feep-1 (20 trailing zero bits: e * kLn2Hi is exact)
@@ -88,9 +87,8 @@ __device__ __forceinline__ double cos_quarter(double f) {
 }
 
 __device__ __forceinline__ void box_muller(const rlx::U4 w, double &z0, double &z1) {
-    const unsigned long long m1 = ((unsigned long long)(w.x >> 5) << 26) | (w.y >> 6);
     const unsigned long long m2 = ((unsigned long long)(w.z >> 5) << 26) | (w.w >> 6);
-    const double u1 = (double)(m1 + 1ull) * kTwoM53;
+    const double u1 = rlx::philox_unit(w.x, w.y);
     const double r = __builtin_sqrt(-2.0 * ln_unit(u1));   // llvm.sqrt.f64: correctly rounded
     // 2 pi u2 = pi/2 (k + f): k the nearest quarter turn, f the rest — exact in integers
     const unsigned long long k = (m2 + (1ull << 50)) >> 51;

@@ -28,4 +28,14 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
     return U4{c0, c1, c2, c3};
 }
 
+// Counter word 3 of the noise generators is the draw's high word ^ this tag (noise.hip's opening comment says why).
+constexpr uint32_t kNoiseTag = 0x4E4F4953u;          // "NOIS"
+
+// The 53-bit uniform of two output words: m = hi[31:5] lo[31:6], u = (m + 1) 2^-53 in (0, 1] -- exact in fp64.  The u1 of
+// noise.hip's Box-Muller pair and the truncated-normal draw of explore_dist.hip (uniforms() of tests/noise_ref.py).
+__device__ __forceinline__ double philox_unit(uint32_t hi, uint32_t lo) {
+    const unsigned long long m = ((unsigned long long)(hi >> 5) << 26) | (lo >> 6);
+    return (double)(m + 1ull) * 1.1102230246251565e-16;      // 2^-53
+}
+
 }  // namespace rlx

@@ -995,6 +995,39 @@ int rlx_gaussian_action(const float *mean, const float *std_per_dim, const float
                         const double *standard_normals, const float *action_low,
                         const float *action_high, int n_env, int action_dim, float *actions,
                         void *stream);                              /* exploration_policies/additive_noise.py:75-111 */
+/* Boltzmann.get_action (exploration_policies/boltzmann.py:52-62) for n_env rows in ONE launch, one wave per row (lane l
+ * holds actions l, l + 64, ..; n_actions <= RLX_BOLTZMANN_MAX_ACTIONS), in numpy's types and order: x = q / fp32(T),
+ * e = expf(x), s = np.sum(e) in numpy's pairwise fp32 order, p = e / s, p[-1] = 1 - np.sum(p[:-1]), then
+ * np.random.choice(p=p): the fp64 cumulative sum in index order divided by its last entry, action = the number of entries
+ * <= uniforms[row] (tests/boltzmann_ref.py restates every rounding; the device expf differs from numpy's by a few ulp).
+ * q_values [n_env][ld]; uniforms fp64 [n_env] and *temperature (fp64) are READ FROM DEVICE MEMORY; probs_out
+ * [n_env][ld_out] fp32 and actions int32 [n_env] are both written.  A row whose probabilities hold a NaN, an infinity or
+ * a negative entry (numpy raises) sets RLX_EXPLORE_STATUS_BAD_PROBABILITIES in *status and takes np.argmax of its q. */
+#define RLX_BOLTZMANN_MAX_ACTIONS 1024
+#define RLX_EXPLORE_STATUS_BAD_PROBABILITIES 1
+#define RLX_EXPLORE_STATUS_BAD_WINDOW 2
+int rlx_boltzmann_sample(const float *q_values, long long ld, const double *uniforms, const double *temperature,
+                         int n_env, int n_actions, float *probs_out, long long ld_out, int *actions, int *status,
+                         void *stream);
+/* TruncatedNormal.get_action (exploration_policies/truncated_normal.py:78-112): scipy's truncnorm(a, b, loc, scale) drawn
+ * by inverse CDF in fp64, one thread per element of mean [n_env][action_dim]: a = (low - mean) / std, b = (high - mean) /
+ * std, x = ndtri(ndtr(a) + u (ndtr(b) - ndtr(a))), through the upper tail (x = -ndtri(Q(a) - u (Q(a) - Q(b))), Q = 1 - ndtr
+ * without cancellation) where a > 0; action = mean + std x clamped into [low, high] (csrc/normal_cdf.hpp).  stddev: one value
+ * (RLX_TN_STD_SCALAR), [action_dim] (RLX_TN_STD_PER_DIM) or [n_env][action_dim] (RLX_TN_STD_PER_ELEMENT); clip_low /
+ * clip_high [action_dim].  u: uniforms fp64 [n_env][action_dim] if given (host draws; scipy's own draw sequence is not
+ * claimed), else the 53-bit uniform in (0, 1] of Philox4x32-10 under the key (seed, rank) at the counter (element,
+ * RLX_TN_STREAM, draw low word, draw high word ^ 0x4E4F4953 -- rlx_normal_fill's layout) with draw = draw_state[0]
+ * (device int64 [2], the second word a ticket left at zero), which the launch READS and then advances by one: every
+ * replay of a captured graph draws new values.  std <= 0 (or NaN) or low >= high sets RLX_EXPLORE_STATUS_BAD_WINDOW and
+ * gives the clipped mean; so does, silently, a window whose mass underflows (beyond 38 std).  actions_f64 is optional. */
+#define RLX_TN_STD_SCALAR 0
+#define RLX_TN_STD_PER_DIM 1
+#define RLX_TN_STD_PER_ELEMENT 2
+#define RLX_TN_STREAM 192
+int rlx_truncated_normal_sample(const float *mean, const float *stddev, int std_kind, const float *clip_low,
+                                const float *clip_high, const double *uniforms, long long *draw_state,
+                                unsigned int seed, unsigned int rank, int n_env, int action_dim, float *actions,
+                                double *actions_f64, int *status, void *stream);
 
 /* ------------------------------------------------------------- Quantile-Regression DQN -- */
 /* QuantileRegressionDQNAgent.learn_from_batch + the QuantileRegressionQHead loss (agents/qr_dqn_agent.py:99-137,
